@@ -9,8 +9,16 @@ A step = every rank pushes ONE frame through the whole path. The DB (default 1M 
 top-2 keys over RCCL (cubesat-apds_amd/pipeline.py). Per-GPU work per step is constant in N (1 frame detected,
 Q_total x N_db/N pairs matched), so scaling is "weak" and value = N frames / step time.
 
-Prints ONE JSON line (rank 0). roofline is for the dominant kernel (hamming_topk); cpu_baseline times the oracle
-("port") on the host cores for a bounded sample of the same workload.
+Prints ONE JSON line (rank 0). roofline is for the dominant kernel (hamming_topk), from the timed steps' own kernel timers.
+
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs DIR) and prints the line. Everything that takes
+runs of its own is behind --full: the stand-alone, two-in-flight and batched extraction figures (detect_roofline), the same steps with
+frames from pinned host memory (value_host_frames), the main scan alone on an idle GPU and the other matcher backend (roofline.solo,
+roofline.integer_path), the vector-ALU microbenchmark (roofline.mix_ceiling) and cpu_baseline, which times the oracle ("port") on the
+host cores for a bounded sample of the same workload.
+
+--dump-outputs DIR: what the timed path returned for its last step, as DIR/<name>.npy (float64 / float32; the inputs are seeded, so
+two builds given the same arguments can be compared array for array).
 """
 import argparse
 import ctypes as C
@@ -47,6 +55,27 @@ def detect_algorithmic_bytes(w, h):
         if o + 1 < len(sizes):
             total += 5.0 * px
     return total
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def frame_outputs(n_keypoints, n_matches, n_inliers, H):
+    """One frame's result as --dump-outputs writes it: the homography (zeros when none was found) and the frame's counts."""
+    found = H is not None
+    return {"homography": np.asarray(H, np.float64).reshape(3, 3) if found else np.zeros((3, 3), np.float64),
+            "frame_counts": np.array([n_keypoints, n_matches, n_inliers, found], np.float64)}    # n_keypoints, n_matches, n_inliers, found
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy; float32 / float64 only, DUMP_LIMIT_BYTES at most in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def spawn_ranks(n):
@@ -109,11 +138,15 @@ def main():
     ap.add_argument("--l2-queries", type=int, default=1_048_576)
     ap.add_argument("--l2-mode", choices=["exact", "screen"], default="exact",
                     help="exact: every distance in f32 MFMA. screen: bf16 MFMA screen (proved bound) + f32 re-rank of the candidates; same keys")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: extraction probes, host frames, solo / other-backend launches, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned for its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
     ap.add_argument("--reserve-cus", type=int, default=0, help="CUs masked out of the match stream so the other stages overlap it")
     ap.add_argument("--serial", action="store_true", help="one frame at a time (no cross-frame overlap of the three stages)")
-    ap.add_argument("--host-frames", action="store_true", default=True,
-                    help="(default) additionally time the streamed pipeline with every step's frame coming from pinned HOST memory (hipMemcpyAsync on "
+    ap.add_argument("--host-frames", action="store_true", default=None,
+                    help="(default with --full) additionally time the streamed pipeline with every step's frame coming from pinned HOST memory (hipMemcpyAsync on "
                          "the extraction stream): reported as value_host_frames next to the resident `value` (the reference's bench times Mat "
                          "construction + extraction, benchmarks/benches/feature_extraction.rs:35-45)")
     ap.add_argument("--no-host-frames", dest="host_frames", action="store_false", help="skip the host-frames leg")
@@ -124,6 +157,8 @@ def main():
                          "fresh set of ranks on torch if that set exits non-zero")
     ap.add_argument("--transport-fallback-from", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.host_frames is None:
+        args.host_frames = args.full
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # started bare (`python bench.py --gpus N`): this process becomes the launcher. Nothing has touched the GPU yet (no torch import,
@@ -174,7 +209,9 @@ def main():
 
     # ---- setup (untimed): frames, and a DB holding the descriptors of a shifted copy of every frame + random rows
     shift = (37, 52)   # (dy, dx): DB images are np.roll'ed frames, so the true homography is a translation
-    frames_np = [synth.make_tile(T, T, frame_index=rank * args.frames + i) for i in range(args.frames)]
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max(1, min(args.frames, 4))) as pool:      # the tile generator's array passes release the GIL
+        frames_np = list(pool.map(lambda i: synth.make_tile(T, T, frame_index=rank * args.frames + i), range(args.frames)))
     frames = [torch.from_numpy(f).to(dev) for f in frames_np]
     cap = pkg.feature_extraction.MAX_POINTS
     kps = torch.empty((cap, 7), dtype=torch.float32, device=dev)
@@ -259,32 +296,34 @@ def main():
     # stand-alone extraction time (no other stage on the GPU) for the detect roofline: BEFORE the pipeline and its streams exist. (The
     # runtime maps streams onto a few hardware queues; once the pipeline's eight streams are around, the extraction's side stream shares
     # a queue with its main stream and the same call takes 2.2 ms instead of 1.9: measured both ways, profiles/r02.)
-    solo = pl.FramePipeline(db_local[:4096].contiguous(), db_xy, index_base=0, group=None, device=str(dev))
-    with torch.cuda.stream(solo.stream):
-        nk = C.c_int(0)
+    akaze_solo_ms, akaze_solo_n = None, 0
+    if args.full:
+        solo = pl.FramePipeline(db_local[:4096].contiguous(), db_xy, index_base=0, group=None, device=str(dev))
+        with torch.cuda.stream(solo.stream):
+            nk = C.c_int(0)
 
-        def extract_once(rep):
-            f = frames[rep % len(frames)]
-            check(L.apds_dev_akaze_extract(f.data_ptr(), T, T, f.shape[2], f.stride(0), solo.cap, solo.kps.data_ptr(), solo.desc.data_ptr(), solo.cap,
-                                           C.byref(nk), pl.torch_stream()))
-        for rep in range(3):
-            extract_once(rep)
-        torch.cuda.synchronize()
-        akaze_solo_n = 10
-
-        def timed_solo():
-            ts = time.perf_counter()
-            for rep in range(akaze_solo_n):
+            def extract_once(rep):
+                f = frames[rep % len(frames)]
+                check(L.apds_dev_akaze_extract(f.data_ptr(), T, T, f.shape[2], f.stride(0), solo.cap, solo.kps.data_ptr(), solo.desc.data_ptr(), solo.cap,
+                                               C.byref(nk), pl.torch_stream()))
+            for rep in range(3):
                 extract_once(rep)
             torch.cuda.synchronize()
-            return (time.perf_counter() - ts) * 1e3
-        akaze_solo_ms = timed_solo()
-    del solo
+            akaze_solo_n = 10
+
+            def timed_solo():
+                ts = time.perf_counter()
+                for rep in range(akaze_solo_n):
+                    extract_once(rep)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - ts) * 1e3
+            akaze_solo_ms = timed_solo()
+        del solo
     # The same stage as THROUGHPUT: two host threads, each with its own stream and output buffers, extract alternate frames, so one
     # frame's latency-bound phases (the small octaves' launch chain, the suppression rounds) run beside the other frame's bandwidth-bound
     # ones - what the streamed pipeline's two extraction workers do. Informational: `frac` stays the one-call-at-a-time figure.
     akaze_pair_ms = None
-    if not args.serial:
+    if args.full and not args.serial:
         import threading
 
         def pair_worker(tid, reps, errs):
@@ -324,24 +363,26 @@ def main():
     # launch chain that bounds a single frame is paid once per four). Informational as well; the batch's workspace is given back afterwards.
     akaze_batch4_ms = None
     if not args.serial and world == 1 and T * T * 4 * 24 * 4 < 40e9:
-        with torch.cuda.stream(setup_stream):
-            bimgs = torch.stack([frames[i % len(frames)] for i in range(4)]).contiguous()
-            bcap = 1 << 16
-            bk = torch.empty((4, bcap, 7), dtype=torch.float32, device=dev)
-            bd = torch.empty((4, bcap, 64), dtype=torch.uint8, device=dev)
-            bcounts = (C.c_int * 4)()
-            try:
-                for rep in range(4):
-                    torch.cuda.synchronize()
-                    tb = time.perf_counter()
-                    check(L.apds_dev_akaze_extract_batch(bimgs.data_ptr(), 4, bimgs.stride(0), T, T, bimgs.shape[3], bimgs.stride(1), bcap, bk.data_ptr(), bd.data_ptr(),
-                                                         bcap, bcounts, pl.torch_stream()))
-                    torch.cuda.synchronize()
-                    akaze_batch4_ms = (time.perf_counter() - tb) * 1e3 / 4
-            except pkg._lib.ApdsError as e:   # (e.g. more keypoints per frame than the probe's capacity: the line is informational)
-                print(f"[bench] batched extraction probe skipped: {e}", file=sys.stderr, flush=True)
-                akaze_batch4_ms = None
-            del bimgs, bk, bd
+        if args.full:
+            with torch.cuda.stream(setup_stream):
+                bimgs = torch.stack([frames[i % len(frames)] for i in range(4)]).contiguous()
+                bcap = 1 << 16
+                bk = torch.empty((4, bcap, 7), dtype=torch.float32, device=dev)
+                bd = torch.empty((4, bcap, 64), dtype=torch.uint8, device=dev)
+                bcounts = (C.c_int * 4)()
+                try:
+                    for rep in range(4):
+                        torch.cuda.synchronize()
+                        tb = time.perf_counter()
+                        check(L.apds_dev_akaze_extract_batch(bimgs.data_ptr(), 4, bimgs.stride(0), T, T, bimgs.shape[3], bimgs.stride(1), bcap, bk.data_ptr(), bd.data_ptr(),
+                                                             bcap, bcounts, pl.torch_stream()))
+                        torch.cuda.synchronize()
+                        akaze_batch4_ms = (time.perf_counter() - tb) * 1e3 / 4
+                except pkg._lib.ApdsError as e:   # (e.g. more keypoints per frame than the probe's capacity: the line is informational)
+                    print(f"[bench] batched extraction probe skipped: {e}", file=sys.stderr, flush=True)
+                    akaze_batch4_ms = None
+                del bimgs, bk, bd
+        # with or without the probe: the set-up's library context (its streams among them) is gone before the pipeline's streams exist
         check(L.apds_thread_release())
         check(L.apds_release_cached_memory())
         check(L.apds_set_device(dev_index))
@@ -378,6 +419,7 @@ def main():
         elapsed = time.perf_counter() - t0
         check(L.apds_dev_timing_enable(0))
         timers = {n: pkg._lib.kernel_ms(n) for n in ("hamming_topk", "hamming_topk_sample", "akaze_extract", "ransac_score")}
+        last_out = frame_outputs(stats[-1]["n_keypoints"], stats[-1]["n_matches"], stats[-1]["n_inliers"], stats[-1]["H"])
     else:
         # The library's own pipeline (apds_pipeline_*, csrc/pipeline.cpp): the timed loop below makes C calls only - submit K frames, poll K
         # results - no torch op, no python thread; the stage threads, streams, events and slots live inside libapds_hip.so.
@@ -393,7 +435,7 @@ def main():
                 if res.status != 0:
                     raise RuntimeError(f"frame {res.frame} failed in the pipeline: status {res.status}")
                 out.append(dict(n_keypoints=res.n_keypoints, n_matches=res.n_matches, n_inliers=res.n_inliers, H=True if res.homography_found else None))
-            return out
+            return out, res      # res: the last frame's whole result (its H included)
 
         def timed_stream(frame_list, warm):
             handle = pipe.prepare(frame_list[0].shape, filter_strength=args.filter_strength, timing=True)
@@ -406,11 +448,12 @@ def main():
             pipe.stats(reset=True)
             fence()
             t_start = time.perf_counter()
-            got = stream_frames(handle, fargs, args.steps)
+            got, last = stream_frames(handle, fargs, args.steps)
             fence()
-            return time.perf_counter() - t_start, got, pipe.stats(reset=True)
+            return time.perf_counter() - t_start, got, pipe.stats(reset=True), last
 
-        elapsed, stats, st = timed_stream(frames, args.warmup)
+        elapsed, stats, st, last = timed_stream(frames, args.warmup)
+        last_out = frame_outputs(last.n_keypoints, last.n_matches, last.n_inliers, list(last.H) if last.homography_found else None)
         timers = {"hamming_topk": (st.hamming_topk_ms, st.hamming_topk_launches), "hamming_topk_sample": (st.hamming_topk_sample_ms, st.hamming_topk_sample_launches),
                   "akaze_extract": (st.akaze_extract_ms, st.akaze_extract_calls), "ransac_score": (st.ransac_score_ms, st.ransac_score_launches)}
         split_scan = bool(st.split_scan)
@@ -424,7 +467,7 @@ def main():
         # the same K steps with every frame coming from pinned host memory: an extraction worker uploads it (hipMemcpyAsync on its own
         # stream, into a per-slot device buffer) in front of the extraction, so frame i+1's PCIe copy travels under frame i's match
         host_frames = [torch.from_numpy(f).pin_memory() for f in frames_np]
-        elapsed_host, stats_host, _ = timed_stream(host_frames, max(args.warmup, 2))
+        elapsed_host, stats_host, _, _ = timed_stream(host_frames, max(args.warmup, 2))
         assert [s["n_keypoints"] for s in stats_host] == [s["n_keypoints"] for s in stats], "host-frame run differs from the resident run"
 
     def max_over_ranks(v):
@@ -440,7 +483,7 @@ def main():
     # merge, and the extraction, share the GPU with it, so its live launch time reads longer than the kernel needs by itself.
     solo_launch_ms = None
     other_launch_ms, other_keys_equal = None, None
-    if rank == 0 and not args.serial and stats and stats[0]["n_keypoints"] > 0:
+    if args.full and rank == 0 and not args.serial and stats and stats[0]["n_keypoints"] > 0:
         with torch.cuda.stream(setup_stream):
             n_solo = C.c_int(0)
             check(L.apds_dev_akaze_extract(frames[0].data_ptr(), T, T, frames[0].shape[2], frames[0].stride(0), cap, kps.data_ptr(), desc.data_ptr(), cap,
@@ -489,7 +532,7 @@ def main():
         mfma_backend = C.c_int(0)
         check(L.apds_dev_match_backend(C.byref(mfma_backend)))
         peak = C.c_double(0)
-        if not mfma_backend.value:   # the xor + popcount ceiling of the vector-ALU matcher (a register-only microbenchmark: 4 x 32 ms)
+        if args.full and not mfma_backend.value:   # the xor + popcount ceiling of the vector-ALU matcher (a register-only microbenchmark: 4 x 32 ms)
             check(L.apds_dev_valu_popcount_peak(C.byref(peak)))
         traffic, traffic_source = None, None
         tpath = os.path.join(ROOT, "profiles", "traffic.json")
@@ -562,7 +605,7 @@ def main():
             # profiles/r02/valu_calib_*.log). north_star's "% of HBM" is the sub-object `hbm`.
             roofline = {"kernel": f"hamming_topk_kernel<{4 if Q_step >= 16384 else (2 if Q_step >= 8192 else 1)},2>", "bound": "int32-valu",
                          "achieved": achieved_tops, "peak": VALU_FP32_LANE_RATE_SPEC / 1e12, "unit": "T lane-op/s", "frac": achieved_tops / (VALU_FP32_LANE_RATE_SPEC / 1e12),
-                         "mix_ceiling": peak.value / 1e12, "frac_of_mix_ceiling": achieved_tops / (peak.value / 1e12) if peak.value else None,
+                         "mix_ceiling": peak.value / 1e12 if peak.value else None, "frac_of_mix_ceiling": achieved_tops / (peak.value / 1e12) if peak.value else None,
                          "mix_ceiling_source": "apds_dev_valu_popcount_peak in this run (xor at the full VALU rate + half-rate bcnt = 6 issue cycles per dword pair); calibration of every instruction kind: profiles/r02/valu_calib_patterns.log, valu_calib_modes.log",
                          "traffic": traffic, "traffic_source": traffic_source, "launches_per_step": launches_per_step, "avg_launch_ms": avg_launch_ms,
                          "solo": ({"avg_launch_ms": solo_launch_ms, "queries": int(stats[0]["n_keypoints"]),
@@ -602,21 +645,22 @@ def main():
             "roofline": roofline,
             "stages_ms_per_step": {"akaze_extract": akaze_ms / max(args.steps, 1), "hamming_topk": topk_ms_step,
                                    "hamming_topk_sample": sample_ms / max(args.steps, 1), "ransac_score": score_ms / max(args.steps, 1)},
-            "detect_roofline": {"bound": "hbm", "algorithmic_bytes_per_frame": detect_algorithmic_bytes(T, T),
-                                "achieved": detect_algorithmic_bytes(T, T) / (akaze_solo_ms / max(akaze_solo_n, 1) * 1e-3) / 1e9 if akaze_solo_n else 0.0,
-                                "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                                "frac": detect_algorithmic_bytes(T, T) / (akaze_solo_ms / max(akaze_solo_n, 1) * 1e-3) / 1e9 / HBM_PEAK_GBPS if akaze_solo_n else 0.0,
-                                "ms_standalone": akaze_solo_ms / max(akaze_solo_n, 1),
-                                "two_in_flight": ({"ms_per_frame": akaze_pair_ms, "frac": detect_algorithmic_bytes(T, T) / (akaze_pair_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                                                   "note": "throughput form: two host threads / streams extracting alternate frames (20 frames, wall clock); the "
-                                                           "Hessian kernels are not forked to a side stream in this mode"} if akaze_pair_ms else None),
-                                "batch_of_4": ({"ms_per_frame": akaze_batch4_ms, "frac": detect_algorithmic_bytes(T, T) / (akaze_batch4_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                                                "note": "throughput form: one apds_dev_akaze_extract_batch call over four resident frames (wall clock / 4)"}
-                                               if akaze_batch4_ms else None),
-                                "library_contexts_alive": int(L.apds_live_contexts()),
-                                "note": "whole extraction (incl. orientation, descriptors, the count read-back), 10 back-to-back calls on resident frames timed by the wall clock with nothing else on the GPU, before the pipeline's streams are created, against the detect stages' algorithmic bytes; stages_ms_per_step.akaze_extract is its wall span while overlapped with the match (two frames are extracted concurrently, so the span may exceed the step time)"},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["detect_roofline"] = {"bound": "hbm", "algorithmic_bytes_per_frame": detect_algorithmic_bytes(T, T),
+                                      "achieved": detect_algorithmic_bytes(T, T) / (akaze_solo_ms / max(akaze_solo_n, 1) * 1e-3) / 1e9 if akaze_solo_n else 0.0,
+                                      "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                      "frac": detect_algorithmic_bytes(T, T) / (akaze_solo_ms / max(akaze_solo_n, 1) * 1e-3) / 1e9 / HBM_PEAK_GBPS if akaze_solo_n else 0.0,
+                                      "ms_standalone": akaze_solo_ms / max(akaze_solo_n, 1),
+                                      "two_in_flight": ({"ms_per_frame": akaze_pair_ms, "frac": detect_algorithmic_bytes(T, T) / (akaze_pair_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                                                         "note": "throughput form: two host threads / streams extracting alternate frames (20 frames, wall clock); the "
+                                                                 "Hessian kernels are not forked to a side stream in this mode"} if akaze_pair_ms else None),
+                                      "batch_of_4": ({"ms_per_frame": akaze_batch4_ms, "frac": detect_algorithmic_bytes(T, T) / (akaze_batch4_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                                                      "note": "throughput form: one apds_dev_akaze_extract_batch call over four resident frames (wall clock / 4)"}
+                                                     if akaze_batch4_ms else None),
+                                      "library_contexts_alive": int(L.apds_live_contexts()),
+                                      "note": "whole extraction (incl. orientation, descriptors, the count read-back), 10 back-to-back calls on resident frames timed by the wall clock with nothing else on the GPU, before the pipeline's streams are created, against the detect stages' algorithmic bytes; stages_ms_per_step.akaze_extract is its wall span while overlapped with the match (two frames are extracted concurrently, so the span may exceed the step time)"}
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the GPU's keypoints and descriptors of frame 0, for the baseline's equality check against the oracle's
             n0 = C.c_int(0)
             with torch.cuda.stream(setup_stream):
@@ -626,6 +670,8 @@ def main():
             gpu_kps = kps[:n0.value].cpu().numpy()
             gpu_desc = desc[:n0.value, :61].cpu().numpy()
             out["cpu_baseline"] = cpu_baseline(pkg, frames_np[0], db_local, int(K), args.filter_strength, db_xy, gpu_kps, gpu_desc)
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, last_out)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
@@ -701,6 +747,16 @@ def bench_l2(args, pkg, pl, torch, dev, world):
         roof = {"kernel": "l2_topk_kernel<2,true,128>", "bound": "mfma", "achieved": achieved, "peak": 157.3, "unit": "TFLOP/s", "frac": achieved / 157.3,
                 "traffic": None, "avg_launch_ms": ms / max(n, 1), "algorithmic_flops_per_launch": flops}
         dtype = "f32 (v_mfma_f32_16x16x4_f32, f32 accumulate)"
+    if args.dump_outputs:
+        # the keys of the last step (f32 bits of the squared distance << 32 | train index), 32 bytes per query as written; a fixed,
+        # seeded sample of the queries when all of them would pass the limit
+        keys = out.cpu().numpy().view(np.uint64)
+        rows = np.arange(nq)
+        if nq * 32 > DUMP_LIMIT_BYTES:
+            rows = np.sort(np.random.default_rng(0x4C32).choice(nq, DUMP_LIMIT_BYTES // 32, replace=False))
+        k = keys[rows]
+        write_outputs(args.dump_outputs, {"l2_query_rows": rows.astype(np.float64), "l2_train_index": (k & np.uint64(0xFFFFFFFF)).astype(np.float64),
+                                          "l2_sq_distance": (k >> np.uint64(32)).astype(np.uint32).view(np.float32)})
     print(json.dumps({
         "metric": "Mmatches/sec (L2 brute-force top-2, float descriptors 128-d, vs 1M-row DB)", "value": nq * args.steps / elapsed / 1e6, "unit": "Mmatches/s",
         "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",

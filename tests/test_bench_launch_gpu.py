@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -55,7 +56,7 @@ def test_a_failing_first_transport_is_retried_on_the_second(gpu_pkg):
 
 
 def test_single_gpu_line_carries_the_contract_fields(gpu_pkg):
-    rc, lines, err = _run(["--steps", "3", "--warmup", "1", "--tile", "1024", "--db-rows", "100000", "--no-cpu-baseline", "--host-frames"])
+    rc, lines, err = _run(["--steps", "3", "--warmup", "1", "--tile", "1024", "--db-rows", "100000", "--no-cpu-baseline", "--host-frames", "--full"])
     assert rc == 0, err[-3000:]
     assert len(lines) == 1
     out = json.loads(lines[0])
@@ -65,3 +66,31 @@ def test_single_gpu_line_carries_the_contract_fields(gpu_pkg):
     assert out["n_gpus"] == 1 and out["collectives"]["world"] == 1
     assert out["value_host_frames"] and out["value_host_frames"] > 0          # frames uploaded from pinned host memory every step
     assert out["config"]["homography_found"] is True
+    assert out["detect_roofline"]["ms_standalone"] > 0                         # --full: the stand-alone extraction probe ran
+
+
+def test_plain_line_times_the_steps_and_dumps_the_last_step(gpu_pkg, tmp_path):
+    """A plain run (no --full) times exactly --steps steps and leaves out what takes runs of its own; --dump-outputs writes the last
+    step's result, and a second run with the same arguments writes the same arrays."""
+    args = ["--steps", "4", "--warmup", "1", "--tile", "1024", "--db-rows", "100000"]
+    runs = []
+    for d in ("a", "b"):
+        rc, lines, err = _run(args + ["--dump-outputs", str(tmp_path / d)])
+        assert rc == 0, err[-3000:]
+        assert len(lines) == 1, lines
+        runs.append(json.loads(lines[0]))
+    out = runs[0]
+    assert out["steps"] == 4 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert abs(out["value"] - 1e3 / out["ms_per_step"]) <= 1e-6 * out["value"]            # one frame per step on one GPU
+    for key in ("metric", "unit", "higher_is_better", "dtype"):
+        assert out[key] == runs[1][key], key
+    assert "cpu_baseline" not in out and "detect_roofline" not in out and out["value_host_frames"] is None
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["frame_counts.npy", "homography.npy"] and sorted(os.listdir(tmp_path / "b")) == names
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    counts = np.load(tmp_path / "a" / "frame_counts.npy")
+    assert counts[0] > 0 and counts[3] == 1.0 and out["config"]["homography_found"] is True
+    H = np.load(tmp_path / "a" / "homography.npy")
+    assert H.shape == (3, 3) and abs(H[2, 2] - 1.0) < 1e-9

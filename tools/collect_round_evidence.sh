@@ -4,8 +4,8 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/evidence
 rm -rf $O && mkdir -p $O
 cd $R
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
-python3 bench.py --db real --no-cpu-baseline > $O/bench_db_real.json 2>/dev/null
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full --db real --no-cpu-baseline > $O/bench_db_real.json 2>/dev/null
 python3 bench.py --workload l2 --steps 2 --warmup 1 > $O/bench_l2_exact.json 2>/dev/null
 python3 bench.py --workload l2 --l2-mode screen --steps 3 --warmup 1 > $O/bench_l2_screen.json 2>/dev/null
 bash tools/profile_bench.sh > $O/profile_bench.log 2>&1

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/prof
 rm -rf $OUT && mkdir -p $OUT
-ARGS="--steps 5 --warmup 2 --no-cpu-baseline"
+ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline"
 # serial run first: per-kernel durations without cross-stage overlap (the streamed run stretches the short kernels)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_serial -- python3 $R/bench.py --serial $ARGS > $OUT/bench_stats_serial.log 2>&1
 echo "serial stats rc=$?"
