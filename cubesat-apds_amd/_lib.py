@@ -26,12 +26,13 @@ SYMBOLS = [
     "apds_dev_pack_descriptors", "apds_dev_hamming_topk", "apds_dev_merge_topk", "apds_dev_match_lds_cap", "apds_dev_match_last_launch_lds", "apds_dev_match_backend", "apds_dev_hamming_topk_backend", "apds_dev_ratio_filter",
     "apds_dev_cross_check", "apds_dev_akaze_extract", "apds_dev_points_from_matches", "apds_dev_find_homography",
     "apds_dev_valu_popcount_peak", "apds_dev_valu_peak", "apds_dev_valu_peak_modes", "apds_dev_last_kernel_ms", "apds_dev_timing_enable", "apds_akaze_debug_plane", "apds_stream_create", "apds_stream_destroy",
-    "apds_band_merger", "apds_dev_band_merger", "apds_warp_perspective", "apds_warp_perspective_f32", "apds_pnp_solver_ransac", "apds_pnp_hypotheses", "apds_pnp_sqpnp", "apds_pnp_ippe", "apds_get_world_coordinates", "apds_l2_knn_match", "apds_dev_l2_topk", "apds_dev_l2_topk_ex",
+    "apds_band_merger", "apds_dev_band_merger", "apds_warp_perspective", "apds_warp_perspective_f32", "apds_pnp_solver_ransac", "apds_dev_pnp_solver_ransac", "apds_dev_pnp_correspondences", "apds_pnp_hypotheses", "apds_pnp_sqpnp", "apds_pnp_ippe", "apds_get_world_coordinates", "apds_l2_knn_match", "apds_dev_l2_topk", "apds_dev_l2_topk_ex",
     "apds_db_create", "apds_db_destroy", "apds_db_rows", "apds_db_insert_image", "apds_db_select", "apds_db_view", "apds_db_view_download", "apds_db_knn_match",
     "apds_comm_id_create", "apds_shard_create", "apds_shard_destroy", "apds_shard_info", "apds_shard_counts", "apds_shard_knn", "apds_shard_knn_replicated", "apds_shard_slot_create",
     "apds_shard_slot_destroy", "apds_shard_gather", "apds_shard_scan", "apds_shard_exchange_merge", "apds_db_shard",
     "apds_dev_alloc", "apds_dev_release", "apds_dev_upload", "apds_dev_download", "apds_stream_synchronize",
-    "apds_pipeline_create", "apds_pipeline_submit", "apds_pipeline_poll", "apds_pipeline_stats", "apds_pipeline_destroy",
+    "apds_pipeline_create", "apds_pipeline_submit", "apds_pipeline_poll", "apds_pipeline_stats", "apds_pipeline_destroy", "apds_pipeline_enable_pose",
+    "apds_pipeline_poll_pose",
     "apds_dev_topk_state_create", "apds_dev_topk_state_destroy", "apds_dev_topk_prepass", "apds_dev_topk_scan", "apds_dev_topk_merge",
 ]
 
@@ -84,6 +85,18 @@ class PipelineCounters(C.Structure):
                 ("match_gap_mean_ms", C.c_double), ("match_gaps", C.c_int), ("match_gaps_first_ms", C.c_float * 16),
                 ("match_lds_cap_bytes", C.c_int), ("match_lds_cap_set_at_frame", C.c_int), ("match_lds_cap_gaps_ms", C.c_float * 6),
                 ("extract_workers", C.c_int), ("slots", C.c_int), ("split_scan", C.c_int), ("world", C.c_int)]
+
+
+class PipelinePoseParams(C.Structure):
+    """apds_pipeline_pose_params"""
+    _fields_ = [("db_xyz_dev", C.c_void_p), ("origin", C.c_double * 3), ("camera_intrinsic", C.c_double * 9), ("method", C.c_int), ("iter_count", C.c_int),
+                ("reproj_thres", C.c_float), ("confidence", C.c_double)]
+
+
+class FramePose(C.Structure):
+    """apds_frame_pose"""
+    _fields_ = [("frame", C.c_int64), ("status", C.c_int), ("found", C.c_int), ("n_correspondences", C.c_int), ("n_inliers", C.c_int),
+                ("rvec", C.c_double * 3), ("tvec", C.c_double * 3)]
 
 
 PIPELINE_NOT_READY = 1
@@ -168,6 +181,8 @@ def lib():
             "apds_warp_perspective": (i, [vp, i, i, i, vp, i, i, vp]),
             "apds_warp_perspective_f32": (i, [vp, i, i, i, vp, i, i, vp]),
             "apds_pnp_solver_ransac": (i, [vp, vp, i, vp, i, f, d, i, vp, vp, vp, ip, ip]),
+            "apds_dev_pnp_solver_ransac": (i, [vp, vp, i, vp, i, f, d, i, vp, vp, vp, ip, ip, vp]),
+            "apds_dev_pnp_correspondences": (i, [vp, i, vp, i64, vp, vp, i, vp, vp, vp]),
             "apds_pnp_hypotheses": (i, [vp, vp, i, vp, vp, i, i, vp]),
             "apds_pnp_sqpnp": (i, [vp, vp, i, vp, vp, vp, vp]),
             "apds_pnp_ippe": (i, [vp, vp, i, vp, vp, vp, vp]),
@@ -206,6 +221,8 @@ def lib():
             "apds_pipeline_poll": (i, [vp, C.POINTER(FrameResult), i]),
             "apds_pipeline_stats": (i, [vp, C.POINTER(PipelineCounters), i]),
             "apds_pipeline_destroy": (i, [vp]),
+            "apds_pipeline_enable_pose": (i, [vp, C.POINTER(PipelinePoseParams)]),
+            "apds_pipeline_poll_pose": (i, [vp, C.POINTER(FrameResult), C.POINTER(FramePose), i]),
             "apds_dev_topk_state_create": (i, [pp]),
             "apds_dev_topk_state_destroy": (i, [vp]),
             "apds_dev_topk_prepass": (i, [vp, vp, i, vp, i64, u32, i, vp]),

@@ -17,6 +17,43 @@ int apds_pnp_solver_ransac(const double* obj_xyz, const double* img_xy, int n, c
     });
 }
 
+int apds_dev_pnp_solver_ransac(const void* obj_xyz_dev, const void* img_xy_dev, int n, const double* camera_intrinsic, int iter_count, float reproj_thres,
+                               double confidence, int method, double* rvec, double* tvec, int32_t* inliers, int* n_inliers, int* found, void* stream) {
+    APDS_RANGE("apds_dev_pnp_solver_ransac");
+    return guarded([&] {
+        APDS_REQUIRE(found && n_inliers, APDS_ERR_BAD_ARG, "null argument");
+        *found = 0;
+        *n_inliers = 0;
+        APDS_REQUIRE(obj_xyz_dev && img_xy_dev && camera_intrinsic && rvec && tvec, APDS_ERR_BAD_ARG, "null argument");
+        (void)pnp_checked_method(n, method);   // (argument errors before any device work)
+        hipStream_t s = pick_stream(stream);
+        ctx().ws_reset(s);   // (every solve starts from an empty workspace: a pipeline thread calls this once per frame)
+        *found = pnp_ransac_core(static_cast<const float*>(obj_xyz_dev), static_cast<const float*>(img_xy_dev), n, camera_intrinsic, iter_count, reproj_thres,
+                                 confidence, method, rvec, tvec, inliers, n_inliers, s);
+    });
+}
+
+int apds_dev_pnp_correspondences(const void* kps, int n_kps, const void* db_xyz, int64_t n_db, const double* origin, const void* matches, int n_matches,
+                                 void* img_xy, void* obj_xyz, void* stream) {
+    APDS_RANGE("apds_dev_pnp_correspondences");
+    return guarded([&] {
+        APDS_REQUIRE(n_kps >= 0 && n_db >= 0 && n_matches >= 0, APDS_ERR_ASSERT, "negative count");
+        if (n_matches == 0) return;
+        APDS_REQUIRE(kps && db_xyz && origin && matches && img_xy && obj_xyz, APDS_ERR_BAD_ARG, "null argument");
+        ThreadCtx& c = ctx();
+        hipStream_t s = pick_stream(stream);
+        c.ws_reset(s);
+        int* err = c.alloc_n<int>(1);
+        HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int), s));
+        pnp_correspondences_device(static_cast<const apds_keypoint*>(kps), n_kps, static_cast<const double*>(db_xyz), (long long)n_db, origin,
+                                   static_cast<const apds_dmatch*>(matches), n_matches, static_cast<float*>(img_xy), static_cast<float*>(obj_xyz), err, s);
+        int* herr = c.pinned_ints(1);
+        HIP_CHECK(hipMemcpyAsync(herr, err, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        APDS_REQUIRE(herr[0] == 0, APDS_ERR_OUT_OF_RANGE, "match index outside the keypoint vector or the DB's world points");
+    });
+}
+
 int apds_pnp_hypotheses(const double* obj_xyz, const double* img_xy, int n, const double* camera_intrinsic, const int32_t* idx5, int n_samples,
                         int model_points, double* models) {
     return guarded([&] {

@@ -86,6 +86,12 @@ int find_homography_rho_device(const float* src, const float* dst, int n, double
 // pnp.hip
 int pnp_ransac_device(const double* obj_xyz, const double* img_xy, int n, const double* K, int iterations, float reproj_thr, double confidence, int method,
                       double* rvec, double* tvec, int32_t* inliers, int* n_inliers, hipStream_t s);
+// the RANSAC loop on float correspondences already on the device (pnp_ransac_device is its host-array front); inliers may be null
+int pnp_ransac_core(const float* obj_dev, const float* img_dev, int n, const double* K, int iterations, float reproj_thr, double confidence, int method,
+                    double* rvec, double* tvec, int32_t* inliers, int* n_inliers, hipStream_t s);
+int pnp_checked_method(int n, int method);   // APDS_ERR_ASSERT for n < 4, APDS_ERR_NOT_IMPLEMENTED past cv::SolvePnPMethod; DLS / UPNP -> EPNP
+void pnp_correspondences_device(const apds_keypoint* kps, int n_kps, const double* db_xyz, long long n_db, const double* origin, const apds_dmatch* m, int nm,
+                                float* img_xy, float* obj_xyz, int* err_flag, hipStream_t s);
 void pnp_hypotheses_device(const double* obj_xyz, const double* img_xy, int n, const double* K, const int32_t* idx5, int B, int model_points,
                            double* models_host, hipStream_t s);
 int pnp_ippe_host(const double* obj_xyz, const double* img_xy, int n, const double* K, double* rvec, double* tvec);

@@ -9,12 +9,14 @@
 //                            frames follow each other without the pre-pass, the merge and the dependent-launch gaps between them;
 //                            with a row-sharded DB (apds_shard_*): query gather of frame i+1 before the key exchange of frame i
 //   homography worker (1)    frame i-1: ratio filter, point gather, RANSAC (its host round trips hide behind the other two stages)
+//   pose worker (opt-in, 1)  frame i-2: world-point gather, PnP RANSAC (apds_pipeline_enable_pose; overlaps the next frame's homography)
 //
 // Every worker owns a HIP stream and a device workspace (the per-thread context every entry point uses), stages hand frames over
 // through HIP events, results leave in frame order. The reference only chains these steps inside unit tests
 // (feature_extraction/src/lib.rs:197-249) and never calls find_homography_mat on the result; this is the composed path the
 // north-star metric (frames/s) is measured on. The Python class cubesat-apds_amd/pipeline.py:StreamedFramePipeline is a front of this.
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstring>
 #include <deque>
@@ -97,6 +99,11 @@ struct Slot {
     int K = 0, status = APDS_OK;
     std::string error;
     std::vector<int> counts;
+    // the pose stage (apds_pipeline_enable_pose): the frame's 2D-3D pairs, and the homography stage's result handed on with the slot
+    float *pose_img = nullptr, *pose_obj = nullptr;
+    hipEvent_t ev_homography = nullptr;
+    apds_frame_result res{};
+    std::string res_why;
 };
 
 struct Pipeline {
@@ -117,14 +124,18 @@ struct Pipeline {
     std::vector<std::unique_ptr<Slot>> slots;
     std::vector<std::unique_ptr<Chan<Slot*>>> q_free, q_jobs, q_ext;
     Chan<int> q_any;          // which worker finished a frame (arrival order; one GPU)
-    Chan<Slot*> q_homography;
+    Chan<Slot*> q_homography, q_pose;
     std::vector<std::thread> threads;
     hipStream_t st_extract[8] = {}, st_match = nullptr, st_pre = nullptr, st_merge = nullptr, st_homography = nullptr, st_gather = nullptr, st_counts = nullptr;
+    hipStream_t st_pose = nullptr;
+    std::atomic<bool> pose_on{false};   // set once, before the first submit
+    apds_pipeline_pose_params pose{};
 
     std::mutex m;   // results, counters, errors
     std::condition_variable cv;
     std::map<int64_t, apds_frame_result> results;
     std::map<int64_t, std::string> result_errors;
+    std::map<int64_t, apds_frame_pose> poses;
     int64_t next_submit = 0, next_result = 0, done = 0;
     bool failed = false, closing = false;
     int fail_code = 0;
@@ -155,6 +166,7 @@ struct Pipeline {
         for (auto& q : q_ext) q->close();
         q_any.close();
         q_homography.close();
+        q_pose.close();
     }
     void add_timer(const char* name, double ms, int n) {
         std::lock_guard<std::mutex> g(m);
@@ -198,10 +210,11 @@ struct Pipeline {
         (void)apds_thread_release();   // this worker's stream + workspace go back to the process-wide cache
     }
 
-    void finish(Slot* s, const apds_frame_result& r, const std::string& why) {
+    void finish(Slot* s, const apds_frame_result& r, const std::string& why, const apds_frame_pose* fp = nullptr) {
         {
             std::lock_guard<std::mutex> g(m);
             results[s->index] = r;
+            if (fp) poses[s->index] = *fp;
             if (r.status != APDS_OK) result_errors[s->index] = why;
             done++;
         }
@@ -419,10 +432,51 @@ struct Pipeline {
                 r.status = e.code;
                 why = e.msg;
             }
-            finish(s, r, why);
+            if (pose_on) {   // the pose worker finishes the frame: its ratio-filtered matches are ordered on this stream
+                s->res = r;
+                s->res_why = why;
+                HIP_CHECK(hipEventRecord(s->ev_homography, st));
+                q_pose.push(s);
+            } else {
+                finish(s, r, why);
+            }
         }
         (void)hipFree(count_dev);
         collect({"ransac_score"});
+        q_pose.close();
+    }
+
+    // ---- stage 4 (opt-in): world-point gather, PnP RANSAC ------------------------------------------------------------------------------
+    // Frame i's pose runs here while frame i + 1's homography runs on the stage before. Both calls start from an empty workspace of this
+    // thread (they reset it themselves), so nothing grows with the frame count. A frame whose pose fails reports it in its pose status.
+    void pose_worker() {
+        hipStream_t st = st_pose;
+        Slot* s = nullptr;
+        while (q_pose.pop(s)) {
+            const apds_frame_result& r = s->res;
+            apds_frame_pose fp{};
+            fp.frame = s->index;
+            fp.status = r.status;
+            if (r.status == APDS_OK) {
+                const int M = r.n_matches;
+                fp.n_correspondences = M;
+                try {
+                    HIP_CHECK(hipStreamWaitEvent(st, s->ev_homography, 0));
+                    PIPE_OK(apds_dev_pnp_correspondences(s->kps, s->K, pose.db_xyz_dev, n_db_total, pose.origin, s->matches, M, s->pose_img, s->pose_obj, st));
+                    // fewer than four pairs: the one-call entry's APDS_ERR_ASSERT, without device work
+                    fp.status = apds_dev_pnp_solver_ransac(s->pose_obj, s->pose_img, M, pose.camera_intrinsic, pose.iter_count, pose.reproj_thres, pose.confidence,
+                                                          pose.method, fp.rvec, fp.tvec, nullptr, &fp.n_inliers, &fp.found, st);
+                } catch (const StageError& e) {
+                    fp.status = e.code;
+                }
+                if (fp.status != APDS_OK) {   // (as the serial front reports a failed solve: nothing but the status and the pair count)
+                    fp.found = fp.n_inliers = 0;
+                    std::memset(fp.rvec, 0, sizeof(fp.rvec));
+                    std::memset(fp.tvec, 0, sizeof(fp.tvec));
+                }
+            }
+            finish(s, r, s->res_why, &fp);
+        }
     }
 };
 
@@ -431,7 +485,8 @@ void destroy_pipeline(Pipeline* P) {
         std::lock_guard<std::mutex> g(P->m);
         P->closing = true;
     }
-    // the stages drain in order: no more jobs -> extraction ends -> match ends (closes the homography queue) -> homography ends
+    // the stages drain in order: no more jobs -> extraction ends -> match ends (closes the homography queue) -> homography ends (closes the
+    // pose queue) -> pose ends
     for (auto& q : P->q_jobs) q->close();
     for (auto& q : P->q_free) q->close();
     for (size_t e = 0; e < P->threads.size() && e < (size_t)P->E; e++)
@@ -446,9 +501,10 @@ void destroy_pipeline(Pipeline* P) {
     (void)hipDeviceSynchronize();
     for (auto& up : P->slots) {
         Slot* s = up.get();
-        for (void* ptr : {(void*)s->kps, (void*)s->desc, (void*)s->keys, (void*)s->matches, (void*)s->p1, (void*)s->p2, (void*)s->mask, (void*)s->frame_dev})
+        for (void* ptr : {(void*)s->kps, (void*)s->desc, (void*)s->keys, (void*)s->matches, (void*)s->p1, (void*)s->p2, (void*)s->mask, (void*)s->frame_dev,
+                          (void*)s->pose_img, (void*)s->pose_obj})
             if (ptr) (void)hipFree(ptr);
-        for (hipEvent_t ev : {s->ev_extract, s->ev_pre, s->ev_scan, s->ev_match, s->ev_mstart, s->ev_mend})
+        for (hipEvent_t ev : {s->ev_extract, s->ev_pre, s->ev_scan, s->ev_match, s->ev_mstart, s->ev_mend, s->ev_homography})
             if (ev) (void)hipEventDestroy(ev);
         if (s->topk_state) topk_split_destroy(s->topk_state);
         if (s->shard_slot && P->shard) (void)apds_shard_slot_destroy(P->shard, s->shard_slot);
@@ -456,7 +512,7 @@ void destroy_pipeline(Pipeline* P) {
     if (P->db_expanded) hm_train_destroy(P->db_expanded);
     P->db_expanded = nullptr;
     if (!P->own_match_stream) P->st_match = nullptr;
-    for (hipStream_t st : {P->st_match, P->st_pre, P->st_merge, P->st_homography, P->st_gather, P->st_counts})
+    for (hipStream_t st : {P->st_match, P->st_pre, P->st_merge, P->st_homography, P->st_gather, P->st_counts, P->st_pose})
         if (st) (void)hipStreamDestroy(st);
     for (hipStream_t st : P->st_extract)
         if (st) (void)hipStreamDestroy(st);
@@ -604,7 +660,9 @@ int apds_pipeline_submit(void* pipe, const void* frame, size_t stride_bytes, int
     });
 }
 
-int apds_pipeline_poll(void* pipe, apds_frame_result* result, int wait) {
+int apds_pipeline_poll(void* pipe, apds_frame_result* result, int wait) { return apds_pipeline_poll_pose(pipe, result, nullptr, wait); }
+
+int apds_pipeline_poll_pose(void* pipe, apds_frame_result* result, apds_frame_pose* pose, int wait) {
     int ready = 0;
     const int rc = guarded([&] {
         Pipeline* P = pipe_handle(pipe);
@@ -615,6 +673,13 @@ int apds_pipeline_poll(void* pipe, apds_frame_result* result, int wait) {
         if (have()) {
             *result = P->results[P->next_result];
             P->results.erase(P->next_result);
+            auto fp = P->poses.find(P->next_result);
+            if (pose) {
+                std::memset(pose, 0, sizeof(*pose));
+                pose->frame = P->next_result;
+                if (fp != P->poses.end()) *pose = fp->second;
+            }
+            if (fp != P->poses.end()) P->poses.erase(fp);
             auto why = P->result_errors.find(P->next_result);
             if (why != P->result_errors.end()) {   // (the frame's own status is in result->status; the text goes where every entry point leaves it)
                 set_last_error(why->second);
@@ -627,6 +692,44 @@ int apds_pipeline_poll(void* pipe, apds_frame_result* result, int wait) {
         if (P->failed) fail(P->fail_code, P->fail_msg);
     });
     return rc != APDS_OK ? rc : (ready ? APDS_OK : APDS_PIPELINE_NOT_READY);
+}
+
+int apds_pipeline_enable_pose(void* pipe, const apds_pipeline_pose_params* pose) {
+    return guarded([&] {
+        // the parameters first: every argument error is found before the handle is touched
+        APDS_REQUIRE(pose, APDS_ERR_BAD_ARG, "null pose parameters");
+        APDS_REQUIRE(pose->db_xyz_dev, APDS_ERR_BAD_ARG, "the DB rows' world points are required (n_db_total x 3 doubles)");
+        const double* K = pose->camera_intrinsic;
+        APDS_REQUIRE(std::isfinite(K[0]) && std::isfinite(K[4]) && K[0] > 0 && K[4] > 0, APDS_ERR_BAD_ARG, "the focal lengths must be finite and positive");
+        APDS_REQUIRE(pose->method >= APDS_SOLVEPNP_ITERATIVE && pose->method <= APDS_SOLVEPNP_SQPNP, APDS_ERR_NOT_IMPLEMENTED,
+                     "unknown cv::SolvePnPMethod (MAX_COUNT and beyond)");
+        Pipeline* P = pipe_handle(pipe);
+        std::lock_guard<std::mutex> one(P->submit_m);
+        {
+            std::lock_guard<std::mutex> g(P->m);
+            if (P->failed) fail(P->fail_code, P->fail_msg);
+            APDS_REQUIRE(P->next_submit == 0, APDS_ERR_BAD_ARG, "the pose stage is enabled before the first submit");
+            APDS_REQUIRE(!P->pose_on, APDS_ERR_BAD_ARG, "the pose stage is already enabled");
+        }
+        P->pose = *pose;
+        if (P->pose.iter_count <= 0) P->pose.iter_count = 100;
+        if (P->pose.reproj_thres <= 0) P->pose.reproj_thres = 8.0f;
+        if (!(P->pose.confidence > 0 && P->pose.confidence < 1)) P->pose.confidence = 0.99;
+        int previous = -1;
+        if (hipGetDevice(&previous) != hipSuccess) previous = -1;
+        HIP_CHECK(hipSetDevice(P->device));
+        if (!P->st_pose) HIP_CHECK(hipStreamCreateWithPriority(&P->st_pose, hipStreamNonBlocking, config().pipe_prio));
+        const size_t cap = (size_t)P->cap;
+        for (auto& s : P->slots) {
+            if (!s->pose_img) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->pose_img), cap * 2 * sizeof(float)));
+            if (!s->pose_obj) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->pose_obj), cap * 3 * sizeof(float)));
+            if (!s->ev_homography) HIP_CHECK(hipEventCreateWithFlags(&s->ev_homography, hipEventDisableTiming));
+        }
+        if (previous >= 0 && previous != P->device) (void)hipSetDevice(previous);
+        P->pose_on = true;
+        Pipeline* raw = P;
+        P->threads.emplace_back([raw] { raw->worker("pose", [&] { raw->pose_worker(); }); });
+    });
 }
 
 int apds_pipeline_stats(void* pipe, apds_pipeline_counters* out, int reset) {

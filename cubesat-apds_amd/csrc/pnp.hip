@@ -469,41 +469,96 @@ struct PoseRefiner {
 
 }  // namespace
 
+namespace {
+
+// The pose stage's correspondences, one thread per ratio-filtered match: the frame keypoint's pixel (queryIdx) and the world point of the
+// matched DB row (trainIdx, a global row) minus `origin`, subtracted in double and rounded to float once - the f32 values solvePnPRansac
+// makes of the re-centred doubles. An index outside either side raises *err and writes nothing (as points_from_matches_kernel does).
+__global__ void pnp_correspondences_kernel(const apds_keypoint* __restrict__ kps, int n_kps, const double* __restrict__ db_xyz, long long n_db, double ox,
+                                           double oy, double oz, const apds_dmatch* __restrict__ m, int nm, float2* __restrict__ img,
+                                           float* __restrict__ obj, int* __restrict__ err) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nm) return;
+    const apds_dmatch mm = m[i];
+    if (mm.query_idx < 0 || mm.query_idx >= n_kps || mm.train_idx < 0 || (long long)mm.train_idx >= n_db) {
+        atomicExch(err, 1);
+        return;
+    }
+    img[i] = make_float2(kps[mm.query_idx].x, kps[mm.query_idx].y);
+    const double* w = db_xyz + 3 * (size_t)mm.train_idx;
+    obj[3 * (size_t)i] = (float)(w[0] - ox);
+    obj[3 * (size_t)i + 1] = (float)(w[1] - oy);
+    obj[3 * (size_t)i + 2] = (float)(w[2] - oz);
+}
+
+}  // namespace
+
+void pnp_correspondences_device(const apds_keypoint* kps, int n_kps, const double* db_xyz, long long n_db, const double* origin, const apds_dmatch* m, int nm,
+                                float* img_xy, float* obj_xyz, int* err_flag, hipStream_t s) {
+    if (nm <= 0) return;
+    hipLaunchKernelGGL(pnp_correspondences_kernel, dim3(ceil_div(nm, 256)), dim3(256), 0, s, kps, n_kps, db_xyz, n_db, origin[0], origin[1], origin[2], m, nm,
+                       reinterpret_cast<float2*>(img_xy), obj_xyz, err_flag);
+    HIP_CHECK(hipGetLastError());
+}
+
+// n >= 4 and a member of cv::SolvePnPMethod; DLS / UPNP come back as EPnP (solvePnPGeneric: "broken implementations" that run EPnP)
+int pnp_checked_method(int n, int method) {
+    APDS_REQUIRE(n >= 4, APDS_ERR_ASSERT, "solvePnPRansac needs at least 4 correspondences");
+    if (method == APDS_SOLVEPNP_DLS || method == APDS_SOLVEPNP_UPNP) method = APDS_SOLVEPNP_EPNP;
+    APDS_REQUIRE(method == APDS_SOLVEPNP_EPNP || method == APDS_SOLVEPNP_P3P || method == APDS_SOLVEPNP_ITERATIVE || method == APDS_SOLVEPNP_AP3P ||
+                     method == APDS_SOLVEPNP_SQPNP || method == APDS_SOLVEPNP_IPPE_SQUARE || method == APDS_SOLVEPNP_IPPE,
+                 APDS_ERR_NOT_IMPLEMENTED, "unknown cv::SolvePnPMethod (MAX_COUNT and beyond)");
+    return method;
+}
+
+// host-array front: solvePnPRansac converts CV_64F points to CV_32F before anything else; the float copies go to the device
 int pnp_ransac_device(const double* obj_xyz, const double* img_xy, int n, const double* K, int iterations, float reproj_thr, double confidence, int method,
                       double* rvec, double* tvec, int32_t* inliers, int* n_inliers, hipStream_t s) {
     APDS_REQUIRE(n_inliers, APDS_ERR_BAD_ARG, "null argument");
     *n_inliers = 0;
     APDS_REQUIRE(obj_xyz && img_xy && K && rvec && tvec && inliers, APDS_ERR_BAD_ARG, "null argument");
-    APDS_REQUIRE(n >= 4, APDS_ERR_ASSERT, "solvePnPRansac needs at least 4 correspondences");
-    // solvePnPGeneric: SOLVEPNP_DLS and SOLVEPNP_UPNP are "broken implementations" that run EPnP
-    if (method == APDS_SOLVEPNP_DLS || method == APDS_SOLVEPNP_UPNP) method = APDS_SOLVEPNP_EPNP;
-    APDS_REQUIRE(method == APDS_SOLVEPNP_EPNP || method == APDS_SOLVEPNP_P3P || method == APDS_SOLVEPNP_ITERATIVE || method == APDS_SOLVEPNP_AP3P ||
-                     method == APDS_SOLVEPNP_SQPNP || method == APDS_SOLVEPNP_IPPE_SQUARE || method == APDS_SOLVEPNP_IPPE,
-                 APDS_ERR_NOT_IMPLEMENTED, "unknown cv::SolvePnPMethod (MAX_COUNT and beyond)");
-    // kernel choice of solvePnPRansac: P3P / AP3P on 4 points when asked for, P3P when there are only 4 points; EPnP on 5 otherwise
-    const bool ap3p = method == APDS_SOLVEPNP_AP3P;
-    const bool p3p = method == APDS_SOLVEPNP_P3P || ap3p || n == 4;
-    const int model_points = p3p ? 4 : 5;
-    const Camera cam{K[0], K[4], K[2], K[5]};
-    // solvePnPRansac converts CV_64F points to CV_32F before anything else
+    (void)pnp_checked_method(n, method);
     std::vector<float> op(3 * (size_t)n), ip(2 * (size_t)n);
     for (size_t i = 0; i < op.size(); i++) op[i] = (float)obj_xyz[i];
     for (size_t i = 0; i < ip.size(); i++) ip[i] = (float)img_xy[i];
-    if (n == model_points) {   // model_points == npoints: one direct solve, every point an inlier
-        if (p3p) {
-            if (!host_p3p<float>(op.data(), ip.data(), cam, rvec, tvec, ap3p)) return 0;
-        } else {
-            host_epnp<float>(op.data(), ip.data(), n, cam, rvec, tvec);
-        }
-        for (int i = 0; i < n; i++) inliers[i] = i;
-        *n_inliers = n;
-        return 1;
-    }
     ThreadCtx& c = ctx();
     float* obj_dev = c.alloc_n<float>(op.size());
     float* img_dev = c.alloc_n<float>(ip.size());
     HIP_CHECK(hipMemcpyAsync(obj_dev, op.data(), op.size() * sizeof(float), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(img_dev, ip.data(), ip.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    return pnp_ransac_core(obj_dev, img_dev, n, K, iterations, reproj_thr, confidence, method, rvec, tvec, inliers, n_inliers, s);
+}
+
+// The RANSAC loop on float correspondences that are already on the device (ordered on s); the host solves read the n x 5 floats it downloads.
+// inliers may be null (the pipeline's pose stage reports the count only). Scratch comes from the calling thread's workspace.
+int pnp_ransac_core(const float* obj_dev, const float* img_dev, int n, const double* K, int iterations, float reproj_thr, double confidence, int method,
+                    double* rvec, double* tvec, int32_t* inliers, int* n_inliers, hipStream_t s) {
+    APDS_REQUIRE(n_inliers, APDS_ERR_BAD_ARG, "null argument");
+    *n_inliers = 0;
+    APDS_REQUIRE(obj_dev && img_dev && K && rvec && tvec, APDS_ERR_BAD_ARG, "null argument");
+    method = pnp_checked_method(n, method);
+    // kernel choice of solvePnPRansac: P3P / AP3P on 4 points when asked for, P3P when there are only 4 points; EPnP on 5 otherwise
+    const bool ap3p = method == APDS_SOLVEPNP_AP3P;
+    const bool p3p = method == APDS_SOLVEPNP_P3P || ap3p || n == 4;
+    const int model_points = p3p ? 4 : 5;
+    const Camera cam{K[0], K[4], K[2], K[5]};
+    std::vector<float> op(3 * (size_t)n), ip(2 * (size_t)n);
+    HIP_CHECK(hipMemcpyAsync(op.data(), obj_dev, op.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(ip.data(), img_dev, ip.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (n == model_points) {   // model_points == npoints: one direct solve, every point an inlier
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (p3p) {
+            if (!host_p3p<float>(op.data(), ip.data(), cam, rvec, tvec, ap3p)) return 0;
+        } else {
+            host_epnp<float>(op.data(), ip.data(), n, cam, rvec, tvec);
+        }
+        if (inliers)
+            for (int i = 0; i < n; i++) inliers[i] = i;
+        *n_inliers = n;
+        return 1;
+    }
+    ThreadCtx& c = ctx();
 
     // a batch costs about the same wall time up to ~16 k samples (one thread each, latency-bound): speculate deep
     const int batch_env = config().pnp_batch;
@@ -569,7 +624,8 @@ int pnp_ransac_device(const double* obj_xyz, const double* img_xy, int n, const 
         if (mask[i]) {
             for (int k = 0; k < 3; k++) oi.push_back((double)op[3 * (size_t)i + k]);
             for (int k = 0; k < 2; k++) ii.push_back((double)ip[2 * (size_t)i + k]);
-            inliers[cnt++] = i;
+            if (inliers) inliers[cnt] = i;
+            cnt++;
         }
     APDS_REQUIRE(cnt == maxGood, APDS_ERR_INTERNAL, "inlier mask disagrees with the scored count");
     // SOLVEPNP_IPPE_SQUARE: the RANSAC kernel was EPnP on 5 points (or the direct P3P solve above for n == 4), and the final solvePnP over

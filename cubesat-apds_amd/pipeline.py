@@ -294,6 +294,54 @@ class ShardedMatcher:
         return dst
 
 
+SOLVEPNP_EPNP = 1
+
+
+class PoseStage:
+    """The pose stage of a pipeline (apds_pipeline_enable_pose): every frame's ratio-filtered matches -> 2D-3D pairs -> PnP RANSAC
+    (homographier::pnp_solver_ransac, mod.rs:320-369). db_xyz: [N_total, 3] world points (e.g. ECEF metres from
+    feature_database.ElevationTable.get_world_coordinates_batch, elevationdb.rs:64-104) of EVERY DB row, indexed by global row like the
+    DB keypoints. solvePnPRansac works in f32, which resolves ECEF magnitudes to 0.5 m only, so the points are re-centred on `origin` (in
+    double, then rounded once) and the pose that comes back is relative to it; origin None = the centroid of db_xyz. method: APDS_SOLVEPNP_*
+    (default EPnP, mod.rs:359); iter_count <= 0 -> 100, reproj_thres <= 0 -> 8.0, confidence outside (0, 1) -> 0.99 (solvePnPRansac's
+    defaults)."""
+
+    def __init__(self, db_xyz, camera_intrinsic, origin=None, method=SOLVEPNP_EPNP, iter_count=100, reproj_thres=8.0, confidence=0.99, device="cuda:0"):
+        xyz = db_xyz.detach().cpu().numpy() if isinstance(db_xyz, torch.Tensor) else np.asarray(db_xyz)
+        self.db_xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        self.origin = np.asarray(self.db_xyz.mean(0) if origin is None else origin, np.float64).reshape(3).copy()
+        self.K = np.ascontiguousarray(camera_intrinsic, np.float64).reshape(3, 3)
+        self.method, self.iter_count, self.reproj_thres, self.confidence = int(method), int(iter_count), float(reproj_thres), float(confidence)
+        self.db_xyz_dev = torch.from_numpy(self.db_xyz).to(device)     # borrowed by the native pipeline for its whole life
+
+    def params(self):
+        return _lib.PipelinePoseParams(db_xyz_dev=self.db_xyz_dev.data_ptr(), origin=(C.c_double * 3)(*self.origin), camera_intrinsic=(C.c_double * 9)(*self.K.ravel()),
+                                       method=self.method, iter_count=self.iter_count, reproj_thres=self.reproj_thres, confidence=self.confidence)
+
+    def solve(self, img_xy, train_idx):
+        """The established one-call path on host pairs: img_xy [M, 2] (the frame keypoints' pixels), train_idx [M] (global DB rows) ->
+        apds_pnp_solver_ransac on (db_xyz[train_idx] - origin, img_xy). Returns the pose dict the pipeline gives."""
+        M = int(len(train_idx))
+        obj = np.zeros((max(M, 1), 3), np.float64)
+        img = np.zeros((max(M, 1), 2), np.float64)
+        obj[:M] = self.db_xyz[np.asarray(train_idx, np.int64)] - self.origin
+        img[:M] = np.asarray(img_xy, np.float64)
+        rvec, tvec = np.zeros(3, np.float64), np.zeros(3, np.float64)
+        inl = np.zeros(max(M, 1), np.int32)
+        n_inl, found = C.c_int(0), C.c_int(0)
+        K = np.ascontiguousarray(self.K)
+        rc = lib().apds_pnp_solver_ransac(_lib.ptr(obj), _lib.ptr(img), M, _lib.ptr(K), self.iter_count, self.reproj_thres, self.confidence, self.method,
+                                          _lib.ptr(rvec), _lib.ptr(tvec), _lib.ptr(inl), C.byref(n_inl), C.byref(found))
+        if rc != 0:
+            return pose_dict_of(rc, 0, M, 0, np.zeros(3), np.zeros(3))
+        return pose_dict_of(0, found.value, M, n_inl.value, rvec, tvec)
+
+
+def pose_dict_of(status, found, n_correspondences, n_inliers, rvec, tvec):
+    return dict(status=int(status), found=int(found), n_correspondences=int(n_correspondences), n_inliers=int(n_inliers),
+                rvec=np.array(rvec, np.float64).reshape(3), tvec=np.array(tvec, np.float64).reshape(3))
+
+
 class FramePipeline:
     """One rank's resident state: frames, DB shard (+ the DB rows' keypoint coordinates), output buffers."""
 
@@ -310,10 +358,18 @@ class FramePipeline:
         self.p2 = torch.empty((self.cap, 2), dtype=torch.float32, device=self.dev)
         self.mask = torch.empty(self.cap, dtype=torch.uint8, device=self.dev)
 
-    def step(self, frame, filter_strength=0.8, reproj_thr=3.0, max_iters=2000, confidence=0.995):
-        """frame: [H, W, C] u8 device tensor. Returns dict(n_keypoints, n_matches, H (3x3 numpy) or None, n_inliers)."""
+    def step(self, frame, filter_strength=0.8, reproj_thr=3.0, max_iters=2000, confidence=0.995, pose=None):
+        """frame: [H, W, C] u8 device tensor. Returns dict(n_keypoints, n_matches, H (3x3 numpy) or None, n_inliers), and with a PoseStage
+        `pose` also "pose": the frame's matches downloaded, the pairs built on the host and solved by apds_pnp_solver_ransac (the
+        established path the streamed pose stage is compared against)."""
         with torch.cuda.stream(self.stream):
-            return self._step(frame, filter_strength, reproj_thr, max_iters, confidence)
+            out = self._step(frame, filter_strength, reproj_thr, max_iters, confidence)
+            if pose is not None:
+                M = out["n_matches"]
+                m = self.matches[:M].cpu().numpy()
+                kp = self.kps[:out["n_keypoints"]].cpu().numpy()
+                out["pose"] = pose.solve(kp[m[:, 0], 0:2], m[:, 1])
+            return out
 
     def _step(self, frame, filter_strength, reproj_thr, max_iters, confidence):
         L = lib()
@@ -363,7 +419,7 @@ class StreamedFramePipeline:
     pointers (train rows, their keypoints, frames), the transport choice for a sharded DB (ShardedMatcher), and results as dicts."""
 
     def __init__(self, db_rows64, db_xy, index_base=0, group=None, max_points=(1 << 18) - 1, device="cuda:0", slots=6, reserve_cus=0,
-                 n_cus=256, meta_group=None, extract_workers=None, transport="rccl"):
+                 n_cus=256, meta_group=None, extract_workers=None, transport="rccl", pose=None):
         import os
         self.dev = torch.device(device)
         self.matcher = ShardedMatcher(db_rows64, index_base, group, meta_group=meta_group, transport=transport)
@@ -381,6 +437,7 @@ class StreamedFramePipeline:
         self.gap_mean = None
         self._masked_stream_handle = None
         self._pipe, self._key = None, None
+        self.pose = pose                # PoseStage or None: every result then carries "pose"
         if reserve_cus > 0:
             # keep `reserve_cus` CUs (spread evenly over the CU index space) out of the MATCH stream only
             words = (n_cus + 31) // 32
@@ -411,6 +468,14 @@ class StreamedFramePipeline:
         check(lib().apds_set_device(self.dev.index or 0))
         check(lib().apds_pipeline_create(C.byref(h), m.rows.data_ptr(), int(m.rows.shape[0]), m.index_base, m.handle, self.db_kp.data_ptr(), self.n_db, C.byref(p)))
         self._pipe, self._key = h, key
+        if self.pose is not None:
+            pp = self.pose.params()
+            check(lib().apds_pipeline_enable_pose(h, C.byref(pp)))
+
+    def enable_pose(self, pose):
+        """Turn the pose stage on (PoseStage) or off (None) for the frames that follow: the native pipeline is made again."""
+        self.pose = pose
+        self._destroy_native()
 
     def _destroy_native(self):
         h, self._pipe = self._pipe, None
@@ -442,9 +507,12 @@ class StreamedFramePipeline:
         return C.c_void_p(f.data_ptr()), int(f.stride(0)), 1 if f.is_cuda else 0
 
     @staticmethod
-    def result_dict(r):
-        return dict(n_keypoints=r.n_keypoints, n_matches=r.n_matches, n_inliers=r.n_inliers, status=r.status,
-                    H=np.array(r.H, np.float64).reshape(3, 3) if r.homography_found else None)
+    def result_dict(r, pose=None):
+        out = dict(n_keypoints=r.n_keypoints, n_matches=r.n_matches, n_inliers=r.n_inliers, status=r.status,
+                   H=np.array(r.H, np.float64).reshape(3, 3) if r.homography_found else None)
+        if pose is not None:
+            out["pose"] = pose_dict_of(pose.status, pose.found, pose.n_correspondences, pose.n_inliers, list(pose.rvec), list(pose.tvec))
+        return out
 
     def stats(self, reset=False):
         st = _lib.PipelineCounters()
@@ -459,20 +527,22 @@ class StreamedFramePipeline:
             self.stats(reset=True)
         args = [self.frame_args(f) for f in frames]
         res = _lib.FrameResult()
+        fp = _lib.FramePose() if self.pose is not None else None
+        fpp = C.byref(fp) if fp is not None else None
         results = []
         for i in range(count):
             ptr, stride, on_dev = args[i % len(args)]
             check(L.apds_pipeline_submit(self._pipe, ptr, stride, on_dev, None))
             while True:       # take what is finished, so the result queue stays short on long runs
-                rc = L.apds_pipeline_poll(self._pipe, C.byref(res), 0)
+                rc = L.apds_pipeline_poll_pose(self._pipe, C.byref(res), fpp, 0)
                 if rc != 0:
                     if rc < 0:
                         check(rc)
                     break
-                results.append(self.result_dict(res))
+                results.append(self.result_dict(res, fp))
         while len(results) < count:
-            check(L.apds_pipeline_poll(self._pipe, C.byref(res), 1))
-            results.append(self.result_dict(res))
+            check(L.apds_pipeline_poll_pose(self._pipe, C.byref(res), fpp, 1))
+            results.append(self.result_dict(res, fp))
         for i, r in enumerate(results):
             if r["status"] != 0:
                 raise _lib.ApdsError(r["status"], f"frame {i} failed in the pipeline")

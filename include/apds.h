@@ -180,6 +180,22 @@ int apds_warp_perspective_f32(const float* src, int rows, int cols, int channels
 int apds_pnp_solver_ransac(const double* obj_xyz, const double* img_xy, int n, const double* camera_intrinsic, int iter_count, float reproj_thres,
                            double confidence, int method, double* rvec, double* tvec, int32_t* inliers, int* n_inliers, int* found);
 
+/* apds_pnp_solver_ransac (mod.rs:320-369) on correspondences that are already on the device as the float values solvePnPRansac converts
+ * its points to: obj_xyz_dev n x 3 floats, img_xy_dev n x 2 floats, ordered on `stream` (NULL: the thread's own). rvec, tvec, *n_inliers
+ * and *found go to the host; inliers: a host buffer of n ints, or NULL. For the same float values the result is apds_pnp_solver_ransac's
+ * in every respect (one RANSAC loop serves both): every method, the direct solves of n == 4 / n == 5, n < 4 -> APDS_ERR_ASSERT,
+ * IPPE_SQUARE's assertion, SQPnP / IPPE's *found = 0 with the RANSAC model in rvec / tvec. */
+int apds_dev_pnp_solver_ransac(const void* obj_xyz_dev, const void* img_xy_dev, int n, const double* camera_intrinsic, int iter_count, float reproj_thres,
+                               double confidence, int method, double* rvec, double* tvec, int32_t* inliers, int* n_inliers, int* found, void* stream);
+/* The 2D-3D pairs of a frame's matches for apds_dev_pnp_solver_ransac, on the device, one thread per match: img_xy[m] = kps[queryIdx].xy
+ * (n_matches x 2 floats), obj_xyz[m] = (float)(db_xyz[trainIdx] - origin) (n_matches x 3 floats; subtracted in double, rounded once).
+ * kps: the frame's n_kps keypoints (28 bytes each); db_xyz: n_db x 3 doubles, the world point of every GLOBAL train row (e.g. ECEF metres
+ * from apds_get_world_coordinates, elevationdb.rs:64-104); matches: apds_dev_ratio_filter's output; origin: 3 doubles (host). The origin
+ * exists because solvePnPRansac works in f32, which resolves ECEF magnitudes to 0.5 m only: the pose is then relative to it.
+ * An index outside either side -> APDS_ERR_OUT_OF_RANGE (as apds_dev_points_from_matches). Returns when the gather is done. */
+int apds_dev_pnp_correspondences(const void* kps, int n_kps, const void* db_xyz, int64_t n_db, const double* origin, const void* matches, int n_matches,
+                                 void* img_xy, void* obj_xyz, void* stream);
+
 /* feature_database/src/elevationdb.rs:64-104 get_world_coordinates, batched (the object points pnp_solver_ransac consumes): pixel
  * (x, y) of the reference mosaic -> dataset geotransform -> elevation through the inverse elevation geotransform (row id of
  * elevationdb.rs:240) -> EPSG:4326 -> EPSG:4978 (ECEF metres). xy: n x 2, xyz: n x 3 doubles; geotransforms: GDAL's 6 doubles;
@@ -356,6 +372,32 @@ int apds_pipeline_poll(void* pipe, apds_frame_result* result, int wait);
 int apds_pipeline_stats(void* pipe, apds_pipeline_counters* out, int reset);
 /* Drains the frames in flight, joins the workers, releases streams and buffers. */
 int apds_pipeline_destroy(void* pipe);
+/* The pose stage (opt-in): after the homography, each frame's ratio-filtered matches -> 2D-3D pairs (apds_dev_pnp_correspondences) ->
+ * apds_dev_pnp_solver_ransac, on a stage thread and a high-priority stream of its own, so frame i's pose overlaps frame i+1's homography.
+ * This is the satellite side of the mission - DB keypoint -> world point (elevationdb.rs:64-104) -> attitude by pnp_solver_ransac
+ * (mod.rs:320-369) - which the reference never committed. A pipeline that does not enable it behaves as before. */
+typedef struct apds_pipeline_pose_params {
+    const void* db_xyz_dev;     /* n_db_total x 3 doubles (world points of every global DB row), borrowed until destroy */
+    double origin[3];           /* subtracted (in double) before the f32 conversion; poses are relative to it */
+    double camera_intrinsic[9]; /* row major 3x3 (homographier Cmat) */
+    int method;                 /* APDS_SOLVEPNP_*; the python/Rust fronts default to EPNP as mod.rs:359 does */
+    int iter_count;             /* <= 0: 100 (solvePnPRansac's default) */
+    float reproj_thres;         /* <= 0: 8.0 */
+    double confidence;          /* outside (0, 1): 0.99 */
+} apds_pipeline_pose_params;
+typedef struct apds_frame_pose {
+    int64_t frame;
+    int status;                 /* APDS_OK, or what apds_pnp_solver_ransac returned for this frame's correspondences
+                                   (APDS_ERR_ASSERT for < 4 matches); the frame's own status if extraction/match failed */
+    int found, n_correspondences, n_inliers;
+    double rvec[3], tvec[3];
+} apds_frame_pose;
+/* Before the first submit (else APDS_ERR_BAD_ARG). Checked before any device work: a null db_xyz_dev (APDS_ERR_BAD_ARG), focal lengths that
+ * are not finite and positive (APDS_ERR_BAD_ARG), a method past cv::SolvePnPMethod (APDS_ERR_NOT_IMPLEMENTED). */
+int apds_pipeline_enable_pose(void* pipe, const apds_pipeline_pose_params* pose);
+/* apds_pipeline_poll with the frame's pose: *pose (may be NULL) is filled when pose is enabled, zeroed (status APDS_OK, found 0) otherwise.
+ * apds_pipeline_poll is this call with pose = NULL. */
+int apds_pipeline_poll_pose(void* pipe, apds_frame_result* result, apds_frame_pose* pose, int wait);
 
 /* ---- device-resident API ------------------------------------------------------------------- */
 /* All pointers below are HIP device pointers. stream: hipStream_t or NULL (the thread's own stream).

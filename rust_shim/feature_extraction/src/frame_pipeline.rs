@@ -4,7 +4,8 @@
 //! chains `akaze_keypoint_descriptor_extraction_def` -> `get_knn_matches` -> `get_points_from_matches` only inside unit tests
 //! (feature_extraction/src/lib.rs:197-249) and calls extraction from a rayon pool without a lock (preprocessor/src/main.rs:227-245); this
 //! is that chain for a stream of frames, one `submit` and one `poll` per frame. NOT compiled in the build container (no Rust toolchain).
-use apds_sys::{apds_frame_result, apds_pipeline_counters, apds_pipeline_params, APDS_PIPELINE_NOT_READY};
+use apds_sys::{apds_frame_pose, apds_frame_result, apds_pipeline_counters, apds_pipeline_params, apds_pipeline_pose_params, APDS_PIPELINE_NOT_READY,
+               APDS_SOLVEPNP_EPNP};
 use std::ffi::CStr;
 use std::os::raw::c_void;
 use std::ptr;
@@ -20,6 +21,19 @@ pub struct FrameResult {
     pub inliers: i32,
     /// row major, `h[8] == 1`; `None`: fewer than four matches survived the ratio test, or no model (`MatError::Empty`, mod.rs:258)
     pub homography: Option<[f64; 9]>,
+}
+
+/// The pose stage's answer for one frame (`apds_frame_pose`): cv::solvePnPRansac over the frame's ratio-filtered matches paired with the
+/// world points of their DB rows, re-centred on the origin given to `enable_pose` (the pose is relative to it).
+pub struct FramePose {
+    pub frame: i64,
+    /// 0, or what `pnp_solver_ransac` returned for these pairs (`APDS_ERR_ASSERT` for fewer than four), or the frame's own failure
+    pub status: i32,
+    pub found: bool,
+    pub correspondences: i32,
+    pub inliers: i32,
+    pub rvec: [f64; 3],
+    pub tvec: [f64; 3],
 }
 
 pub struct FramePipeline {
@@ -84,6 +98,49 @@ impl FramePipeline {
             inliers: r.n_inliers,
             homography: if r.homography_found != 0 { Some(r.H) } else { None },
         }))
+    }
+
+    /// Turns the pose stage on; before the first `submit`. `db_xyz_dev`: n x 3 f64 world points of the train rows on the device (e.g.
+    /// `get_world_coordinates`, elevationdb.rs:64-104), borrowed until the pipeline is dropped; `origin` is subtracted in f64 before
+    /// solvePnPRansac's f32 conversion; `camera_intrinsic` row major 3x3; `method` defaults to SOLVEPNP_EPNP as mod.rs:359 does;
+    /// `iter_count` <= 0, `reproj_thres` <= 0 and `confidence` outside (0, 1) take solvePnPRansac's defaults (100, 8.0, 0.99).
+    pub fn enable_pose(&self, db_xyz_dev: *const c_void, origin: [f64; 3], camera_intrinsic: [f64; 9], method: Option<i32>, iter_count: i32,
+                       reproj_thres: f32, confidence: f64) -> Result<(), String> {
+        let params = apds_pipeline_pose_params {
+            db_xyz_dev, origin, camera_intrinsic, method: method.unwrap_or(APDS_SOLVEPNP_EPNP), iter_count, reproj_thres, confidence,
+        };
+        let rc = unsafe { apds_sys::apds_pipeline_enable_pose(self.pipe, &params) };
+        if rc != 0 {
+            return Err(err(rc));
+        }
+        Ok(())
+    }
+
+    /// `poll` with the frame's pose (all zero, `found == false`, when the pose stage is off). A failed pose does not fail the frame: it is
+    /// in `FramePose::status`.
+    pub fn poll_pose(&self, wait: bool) -> Result<Option<(FrameResult, FramePose)>, String> {
+        let mut r = apds_frame_result { frame: 0, status: 0, n_keypoints: 0, n_matches: 0, n_inliers: 0, homography_found: 0, H: [0.0; 9] };
+        let mut p = apds_frame_pose { frame: 0, status: 0, found: 0, n_correspondences: 0, n_inliers: 0, rvec: [0.0; 3], tvec: [0.0; 3] };
+        let rc = unsafe { apds_sys::apds_pipeline_poll_pose(self.pipe, &mut r, &mut p, wait as i32) };
+        if rc == APDS_PIPELINE_NOT_READY {
+            return Ok(None);
+        }
+        if rc != 0 {
+            return Err(err(rc));
+        }
+        if r.status != 0 {
+            return Err(err(r.status));
+        }
+        Ok(Some((
+            FrameResult {
+                frame: r.frame,
+                keypoints: r.n_keypoints,
+                matches: r.n_matches,
+                inliers: r.n_inliers,
+                homography: if r.homography_found != 0 { Some(r.H) } else { None },
+            },
+            FramePose { frame: p.frame, status: p.status, found: p.found != 0, correspondences: p.n_correspondences, inliers: p.n_inliers, rvec: p.rvec, tvec: p.tvec },
+        )))
     }
 
     pub fn frames_done(&self) -> Result<i64, String> {
