@@ -1,4 +1,5 @@
-// csrc/hamming_mfma.hip — Hamming top-1 / top-2 of 512-bit rows on the FP4 matrix pipe (get_knn_matches, lib.rs:94-114, k <= 2).
+// csrc/hamming_mfma.hip — Hamming top-k of 512-bit rows on the FP4 matrix pipe (get_knn_matches, lib.rs:94-114): k <= 2 on hamming_mfma_kernel (all
+// the crate consumes; the tuned path), 3 <= k <= 8 on hamming_mfma_topk_kernel further down.
 //
 // Brute-force Hamming matching is all pairs x all bits: Q x N x 512 one-bit products. match_hamming.hip forms them on the vector ALU
 // (xor + popcount per dword: 32 lane-operations per pair, bound by the half-rate v_bcnt at 52 T lane-op/s = 1.6e12 pairs/s). CDNA4's
@@ -91,11 +92,11 @@ __global__ void hm_pad_rows_kernel(uint4* __restrict__ rows, float* __restrict__
     }
 }
 
-// thr[q]: the kernel's ranking value (hamming - popcount(query) + bias, as float bits) of the second key of a finished top-2 list
-__global__ void hm_thresholds_kernel(const uint64_t* __restrict__ top2, const float* __restrict__ qpc, int nq, uint32_t* __restrict__ thr) {
+// thr[q]: the kernel's ranking value (hamming - popcount(query) + bias, as float bits) of the last key of a finished top-K list (K = 2, 4, 8)
+__global__ void hm_thresholds_kernel(const uint64_t* __restrict__ topk, int K, const float* __restrict__ qpc, int nq, uint32_t* __restrict__ thr) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nq) return;
-    const uint64_t k2 = top2[(size_t)i * 2 + 1];
+    const uint64_t k2 = topk[(size_t)i * K + K - 1];
     thr[i] = k2 == HM_EMPTY ? 0x7F800000u : __float_as_uint((float)((int)(uint32_t)(k2 >> 32) - (int)qpc[i] + HM_BIAS));
 }
 
@@ -289,9 +290,207 @@ __global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(A
     }
 }
 
-HmPlan hm_plan(int nq, long long nt) {
+// ---- 3 <= k <= 8: the same kernel around a sorted K-entry list per query column and lane (K = 4 serves k = 3, 4; K = 8 serves k = 5 .. 8) ----
+// A kernel of its own rather than a K parameter of hamming_mfma_kernel: the top-2 kernel's registers and instruction stream stay what they
+// are. Everything in front of the ranking is the text above (operands, LDS image, LDS-DMA staging, preset accumulator, four scaled MFMAs
+// per 16 x 16 block); what follows the list length is here: the column blocks per wave (the list registers come out of the B operands'),
+// the insertion, the cross-lane fold and the K-th threshold.
+template <int K>
+struct HmTopK {
+    uint32_t d[K];   // ascending bit patterns of the (positive) ranking values
+    uint32_t i[K];
+};
+// Branch-free insertion into the sorted list (static register indices only). Rows arrive in ascending order inside a lane: strict '<' puts a
+// value behind its equals, so the lower row of a tie stays in front and a value equal to the K-th never enters.
+template <int K>
+__device__ __forceinline__ void hm_insert_k(HmTopK<K>& b, uint32_t d, uint32_t idx) {
+#pragma unroll
+    for (int j = K - 1; j > 0; j--) {   // (descending: slot j - 1 still holds its old entry when slot j takes it over)
+        const bool shift = d < b.d[j - 1], here = d < b.d[j];
+        b.i[j] = shift ? b.i[j - 1] : (here ? idx : b.i[j]);
+        b.d[j] = shift ? b.d[j - 1] : (here ? d : b.d[j]);
+    }
+    const bool first = d < b.d[0];
+    b.i[0] = first ? idx : b.i[0];
+    b.d[0] = first ? d : b.d[0];
+}
+__device__ __forceinline__ uint64_t hm_shfl_xor_u64(uint64_t v, int off) {
+    return ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, off);
+}
+
+// Column blocks per wave for a list length: at four waves per SIMD (128 registers) the top-2 kernel's three blocks leave no room for 3 x 2 x 8
+// list registers; two blocks (16 B-operand registers, 4 accumulators and one list fewer) do: 120 VGPRs for K = 8, 104 for K = 4, no scratch.
+// (K = 4 with three blocks: 128 VGPRs and two of them spilled - 12 bytes of scratch per lane.)
+#ifndef APDS_HM_NC_K4
+#define APDS_HM_NC_K4 2
+#endif
+#ifndef APDS_HM_NC_K8
+#define APDS_HM_NC_K8 2
+#endif
+template <int K>
+struct HmShape {
+    static constexpr int NC = K <= 4 ? APDS_HM_NC_K4 : APDS_HM_NC_K8;
+    static constexpr int Q = HM_WAVES * 16 * NC;   // queries per workgroup
+};
+
+// out[split][nq][K]: keys (distance << 32 | row + index_base) in ascending order, EMPTY behind the rows the split holds.
+template <int K, int NC, int PRIO, bool THR>
+__global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(APDS_HM_WPE, APDS_HM_WPE))) void hamming_mfma_topk_kernel(
+    const uint4* __restrict__ train_fp4, const float* __restrict__ tpc, int n_train, const uint4* __restrict__ query_fp4, const float* __restrict__ qpc, int nq,
+    int tiles_per_split, int q_tiles, int splits, uint32_t index_base, const uint32_t* __restrict__ thr, uint64_t* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(128))) unsigned char hm_lds[];
+    constexpr int TILE_BYTES = HM_TM * 256;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int split, qtile;   // (splits pinned to the XCDs: see hamming_mfma_kernel)
+    if ((splits & 7) == 0) {
+        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+        split = xcd + 8 * (j / q_tiles);
+        qtile = j % q_tiles;
+    } else {
+        split = blockIdx.x / q_tiles;
+        qtile = blockIdx.x % q_tiles;
+    }
+    const int q0 = qtile * (HM_WAVES * 16 * NC) + wave * 16 * NC;   // this wave's queries
+    const int n_tiles = (n_train + HM_TM - 1) / HM_TM;
+    const int tile_begin = split * tiles_per_split, tile_end = min(n_tiles, tile_begin + tiles_per_split);
+    const int col = lane & 15, kq = lane >> 4;
+
+    uint4 B[NC][4];
+    float qq[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        const int qi = min(q0 + 16 * c + col, nq - 1);
+#pragma unroll
+        for (int s = 0; s < 4; s++) B[c][s] = query_fp4[(size_t)qi * 16 + 4 * s + kq];
+        qq[c] = qpc[qi];
+    }
+    // The list starts as K copies of thr[query] (the K-th smallest ranking value over a sample of EARLIER rows: a row of this launch enters
+    // the query's final top-K only with a strictly smaller value) or of +inf, without a row. Real rows push them out from the front; what is
+    // left of them is written as empty. A padding row's value is +inf and never passes the strict test, whatever the list holds.
+    HmTopK<K> best[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        const uint32_t start = THR ? thr[min(q0 + 16 * c + col, nq - 1)] : 0x7F800000u;
+#pragma unroll
+        for (int j = 0; j < K; j++) best[c].d[j] = start, best[c].i[j] = 0xFFFFFFFFu;
+    }
+
+    if (tile_begin < tile_end) {
+        int soff[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int r = 16 * wave + 4 * i + (lane >> 4);
+            soff[i] = r * 256 + (((lane & 15) ^ (r & 15)) << 4);
+        }
+        auto stage = [&](int tile, int buf) {
+            const unsigned char* tbase = reinterpret_cast<const unsigned char*>(train_fp4) + (size_t)tile * TILE_BYTES;   // wave-uniform
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tbase + soff[i]),
+                                                 (__attribute__((address_space(3))) void*)(hm_lds + buf * TILE_BYTES + (16 * wave + 4 * i) * 256), 16, 0, 0);
+            if (wave < HM_TM / 64)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tpc + (size_t)tile * HM_TM + 64 * wave + lane),
+                                                 (__attribute__((address_space(3))) void*)(hm_lds + 2 * TILE_BYTES + buf * (HM_TM * 4) + 256 * wave), 4, 0, 0);
+        };
+        int aoff[4];
+#pragma unroll
+        for (int s = 0; s < 4; s++) aoff[s] = col * 256 + (((4 * s + kq) ^ col) << 4);
+        const int noff = 2 * TILE_BYTES + 16 * kq;
+
+        hm_f32x4 acc[NC];
+        // The common case is the top-2 kernel's: one minimum and one compare per accumulator, against the K-th value. Behind the wave-uniform
+        // branch every one of the four rows is tested again (against the K-th value as the rows before it left it): an insertion is about
+        // 6 K instructions, and most blocks with a hit have it in one row.
+        auto rank = [&](const hm_f32x4 (&a)[NC], uint32_t row0) {
+            bool hit[NC];
+#pragma unroll
+            for (int c = 0; c < NC; c++) {
+                const uint32_t mn = min(min(__float_as_uint(a[c][0]), __float_as_uint(a[c][1])), min(__float_as_uint(a[c][2]), __float_as_uint(a[c][3])));
+                hit[c] = mn < best[c].d[K - 1];
+            }
+#pragma unroll
+            for (int c = 0; c < NC; c++)
+                if (__any(hit[c])) {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const uint32_t v = __float_as_uint(a[c][j]);
+                        if (__any(v < best[c].d[K - 1])) hm_insert_k<K>(best[c], v, row0 + j);
+                    }
+                }
+        };
+
+        stage(tile_begin, 0);
+        __syncthreads();
+        for (int tile = tile_begin; tile < tile_end; tile++) {
+            const int buf = (tile - tile_begin) & 1;
+            if (tile + 1 < tile_end) stage(tile + 1, buf ^ 1);
+            const unsigned char* T = hm_lds + buf * TILE_BYTES;
+            const unsigned char* Nn = hm_lds + noff + buf * (HM_TM * 4);
+#pragma unroll
+            for (int rb = 0; rb < HM_TM / 16; rb++) {
+                const hm_f32x4 init = *reinterpret_cast<const hm_f32x4*>(Nn + rb * 64);
+                uint4 a[4];
+#pragma unroll
+                for (int s = 0; s < 4; s++) a[s] = *reinterpret_cast<const uint4*>(T + rb * 4096 + aoff[s]);
+                if (PRIO) __builtin_amdgcn_s_setprio(PRIO);
+#pragma unroll
+                for (int s = 0; s < 4; s++) {
+                    const hm_v8i A = {(int)a[s].x, (int)a[s].y, (int)a[s].z, (int)a[s].w, 0, 0, 0, 0};
+#pragma unroll
+                    for (int c = 0; c < NC; c++) {
+                        const hm_v8i Bv = {(int)B[c][s].x, (int)B[c][s].y, (int)B[c][s].z, (int)B[c][s].w, 0, 0, 0, 0};
+                        acc[c] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(A, Bv, s == 0 ? init : acc[c], 4, 4, 0, HM_UNIT_SCALE, 0, HM_UNIT_SCALE);
+                    }
+                }
+                if (PRIO) __builtin_amdgcn_s_setprio(0);
+                rank(acc, (uint32_t)(tile * HM_TM + rb * 16 + 4 * kq) + index_base);
+            }
+            __syncthreads();
+        }
+    }
+    // A query column lives in four lanes (kq = 0..3) whose rows interleave: the lists are folded as (value, row) pairs - one 64-bit key each,
+    // a list entry without a row (0xFFFFFFFF) behind every row of its value. Two sorted K-lists -> the K smallest, sorted: min(mine[j],
+    // theirs[K - 1 - j]) holds them as a bitonic sequence, log2 K rounds of compare-exchange sort it. Both partners compute the same list.
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        uint64_t key[K];
+#pragma unroll
+        for (int j = 0; j < K; j++) key[j] = ((uint64_t)best[c].d[j] << 32) | best[c].i[j];
+#pragma unroll
+        for (int off = 16; off < 64; off <<= 1) {
+            uint64_t other[K];
+#pragma unroll
+            for (int j = 0; j < K; j++) other[j] = hm_shfl_xor_u64(key[j], off);
+#pragma unroll
+            for (int j = 0; j < K; j++) key[j] = min(key[j], other[K - 1 - j]);
+#pragma unroll
+            for (int step = K / 2; step > 0; step >>= 1)
+#pragma unroll
+                for (int j = 0; j < K; j++)
+                    if ((j & step) == 0) {
+                        const uint64_t lo = min(key[j], key[j + step]), hi = max(key[j], key[j + step]);
+                        key[j] = lo;
+                        key[j + step] = hi;
+                    }
+        }
+        const int qi = q0 + 16 * c + col;
+        if (kq == 0 && qi < nq) {
+            uint64_t* o = out + ((size_t)split * nq + qi) * K;
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                const uint32_t d = (uint32_t)(key[j] >> 32), i = (uint32_t)key[j];
+                o[j] = i == 0xFFFFFFFFu ? HM_EMPTY : ((uint64_t)(uint32_t)((int)(qq[c] + __uint_as_float(d)) - HM_BIAS) << 32) | i;
+            }
+        }
+    }
+}
+
+static int hm_list_len(int k) { return k <= 2 ? 2 : (k <= 4 ? 4 : 8); }   // the list the kernels keep for a k
+static int hm_queries_per_block(int K) { return K <= 2 ? HM_Q : (K <= 4 ? HmShape<4>::Q : HmShape<8>::Q); }
+
+HmPlan hm_plan(int nq, long long nt, int K) {
     HmPlan p;
-    p.q_tiles = ceil_div(nq, HM_Q);
+    p.q_tiles = ceil_div(nq, hm_queries_per_block(K));
     const int t_tiles = (int)ceil_div(nt, (long long)HM_TM);
     constexpr int SLOTS = 256 * (16 / HM_WAVES);   // two 8-wave workgroups fit a CU (LDS, registers)
     constexpr int OVERHEAD = 4;      // a workgroup's prologue and epilogue (operand loads, pipeline fill, key output) in tile times
@@ -303,7 +502,7 @@ HmPlan hm_plan(int nq, long long nt) {
     // 1.1 GB fetched per match instead of 2.65 GB (the expanded DB is 0.25 GB). Before the threshold launch existed that cost 5 % (every
     // workgroup pays its start from +inf again: 6.5 against 6.15 ms); with it 1.7 % alone on the GPU, and in the pipeline the step is
     // 3.4 % SHORTER (138.9 against 134.3 frames/s: the extraction beside it is memory-bound) - profiles/r04/mfma_xcd_ab.txt, ab_bench_env.txt.
-    const int max_splits = (int)std::max<long long>(1, std::min<long long>(std::min(t_tiles, 128), (16ll << 20) / std::max(nq, 1)));
+    const int max_splits = (int)std::max<long long>(1, std::min<long long>(std::min(t_tiles, 128), (32ll << 20) / std::max(K, 2) / std::max(nq, 1)));   // (8 K bytes per query and split)
     long long best_cost = -1;
     p.splits = 1;
     for (int sp = 1; sp <= max_splits; sp++) {
@@ -346,11 +545,43 @@ long long hm_sample_rows(long long nt) {
     return (cap > 0 && nt >= 65536) ? std::min<long long>(cap, nt / 16 / HM_TM * HM_TM) / HM_TM * HM_TM : 0;   // whole tiles (HM_TM need not be a power of two)
 }
 
-// parts: [p.splits][nq][2] keys
+// The K = 4 / K = 8 launch of hm_scan_device. PRIO: the wave priority around a block's MFMAs is off or 2 here (levels 1, 2, 3 measured alike on
+// the top-2 kernel: one compiled level instead of three).
+template <int K>
+static void hm_scan_k_launch(const void* q_fp4, const float* qpc, int nq, const void* t_fp4, const float* tpc, long long nt, const HmPlan& p, uint32_t index_base,
+                             uint64_t* parts, hipStream_t s, const uint32_t* thr, size_t lds) {
+    constexpr int NC = HmShape<K>::NC;
+    static std::atomic<bool> opted_dev[64];
+    std::atomic<bool>& opted = opted_dev[ctx().device & 63];
+    if (!opted.load()) {
+        auto opt = [&](auto kernel) { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); };
+        opt(&hamming_mfma_topk_kernel<K, NC, 0, false>), opt(&hamming_mfma_topk_kernel<K, NC, 2, false>);
+        opt(&hamming_mfma_topk_kernel<K, NC, 0, true>), opt(&hamming_mfma_topk_kernel<K, NC, 2, true>);
+        opted.store(true);
+    }
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.q_tiles * p.splits), dim3(64 * HM_WAVES), lds, s, static_cast<const uint4*>(t_fp4), tpc, (int)nt,
+                           static_cast<const uint4*>(q_fp4), qpc, nq, p.tiles_per_split, p.q_tiles, p.splits, index_base, thr, parts);
+    };
+    const bool prio = config().match_mfma_prio > 0;
+    if (thr) prio ? go(&hamming_mfma_topk_kernel<K, NC, 2, true>) : go(&hamming_mfma_topk_kernel<K, NC, 0, true>);
+    else prio ? go(&hamming_mfma_topk_kernel<K, NC, 2, false>) : go(&hamming_mfma_topk_kernel<K, NC, 0, false>);
+}
+
+// parts: [p.splits][nq][K] keys; p = hm_plan(nq, nt, K). K = 2: hamming_mfma_kernel; K = 4, 8: hamming_mfma_topk_kernel.
 void hm_scan_device(const void* q_fp4, const float* qpc, int nq, const void* t_fp4, const float* tpc, long long nt, const HmPlan& p, uint32_t index_base,
-                    uint64_t* parts, hipStream_t s, const uint32_t* thr, bool timed) {
+                    uint64_t* parts, hipStream_t s, const uint32_t* thr, bool timed, int K) {
     // (APDS_MATCH_MFMA_LDS_PAD: unused dynamic LDS on top, an experiment knob - e.g. 30000 leaves one workgroup per CU)
     const size_t lds = (size_t)2 * HM_TM * 256 + 2 * HM_TM * sizeof(float) + (size_t)std::max(0, config().match_mfma_lds_pad);
+    if (K > 2) {
+        APDS_REQUIRE(K == 4 || K == 8, APDS_ERR_ASSERT, "the matrix-core matcher keeps lists of 2, 4 or 8");
+        // two names for one launch: "hamming_topk" is what every main match launch is counted under, the second tells which kernel it was
+        std::unique_ptr<KernelTimer> timer, timer_k;
+        if (timed) timer.reset(new KernelTimer("hamming_topk", s)), timer_k.reset(new KernelTimer("hamming_topk_mfma_k", s));
+        if (K == 4) hm_scan_k_launch<4>(q_fp4, qpc, nq, t_fp4, tpc, nt, p, index_base, parts, s, thr, lds);
+        else hm_scan_k_launch<8>(q_fp4, qpc, nq, t_fp4, tpc, nt, p, index_base, parts, s, thr, lds);
+        return;
+    }
     static std::atomic<bool> opted_dev[64];   // above the default dynamic-LDS limit: opt in once per device (idempotent, so a race is harmless)
     std::atomic<bool>& opted = opted_dev[ctx().device & 63];
     if (!opted.load()) {
@@ -413,7 +644,7 @@ void hm_train_destroy(void* h) {
     if (previous >= 0) (void)hipSetDevice(previous);
 }
 
-// Top-k (k = 1 or 2) of nq 64-byte query rows against expanded train rows (t4 / tp: hm_expand_device's output, or an HmTrain's).
+// Top-k (1 <= k <= 8) of nq 64-byte query rows against expanded train rows (t4 / tp: hm_expand_device's output, or an HmTrain's).
 static void hm_topk_expanded(const void* q, int nq, const void* t4, const float* tp, long long nt, uint32_t index_base, int k, uint64_t* out, hipStream_t s) {
     ThreadCtx& c = ctx();
     void* q4 = c.alloc((size_t)nq * 256);
@@ -427,35 +658,37 @@ static void hm_topk_expanded(const void* q, int nq, const void* t4, const float*
     // the rest starts from it - its workgroups then spend their first tiles like their last ones (a workgroup that starts from +inf runs
     // insertion code for every block of its first ~1500 rows), which is also what makes many short workgroups affordable.
     const long long sample = hm_sample_rows(nt);
-    uint64_t* top2 = k == 2 ? out : c.alloc_n<uint64_t>((size_t)nq * 2);
+    const int K = hm_list_len(k);   // the list the kernel keeps: 2, 4 or 8; the columns past k are dropped at the end
+    uint64_t* topk = k == K ? out : c.alloc_n<uint64_t>((size_t)nq * K);
     if (sample) {
-        const HmPlan pa = hm_plan(nq, sample), pb = hm_plan(nq, nt - sample);
-        uint64_t* parts_a = c.alloc_n<uint64_t>((size_t)pa.splits * nq * 2);
-        uint64_t* parts_b = c.alloc_n<uint64_t>((size_t)(pb.splits + 1) * nq * 2);   // + one list: the sample's top-2
-        uint64_t* top2_a = parts_b + (size_t)pb.splits * nq * 2;
+        const HmPlan pa = hm_plan(nq, sample, K), pb = hm_plan(nq, nt - sample, K);
+        uint64_t* parts_a = c.alloc_n<uint64_t>((size_t)pa.splits * nq * K);
+        uint64_t* parts_b = c.alloc_n<uint64_t>((size_t)(pb.splits + 1) * nq * K);   // + one list: the sample's top-K
+        uint64_t* topk_a = parts_b + (size_t)pb.splits * nq * K;
         uint32_t* thr = c.alloc_n<uint32_t>(nq);
         {
             KernelTimer timer("hamming_topk_sample", s);
-            hm_scan_device(q4, qp, nq, t4, tp, sample, pa, index_base, parts_a, s, nullptr, /*timed=*/false);
-            if (pa.splits > 1) merge_topk_device(parts_a, pa.splits, nq, 2, top2_a, s);
-            else HIP_CHECK(hipMemcpyAsync(top2_a, parts_a, (size_t)nq * 16, hipMemcpyDeviceToDevice, s));
-            hipLaunchKernelGGL(hm_thresholds_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, s, (const uint64_t*)top2_a, (const float*)qp, nq, thr);
+            hm_scan_device(q4, qp, nq, t4, tp, sample, pa, index_base, parts_a, s, nullptr, /*timed=*/false, K);
+            if (pa.splits > 1) merge_topk_device(parts_a, pa.splits, nq, K, topk_a, s);
+            else HIP_CHECK(hipMemcpyAsync(topk_a, parts_a, (size_t)nq * K * 8, hipMemcpyDeviceToDevice, s));
+            hipLaunchKernelGGL(hm_thresholds_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, s, (const uint64_t*)topk_a, K, (const float*)qp, nq, thr);
         }
-        hm_scan_device(q4, qp, nq, static_cast<const char*>(t4) + (size_t)sample * 256, tp + sample, nt - sample, pb, index_base + (uint32_t)sample, parts_b, s, thr);
-        merge_topk_device(parts_b, pb.splits + 1, nq, 2, top2, s);
+        hm_scan_device(q4, qp, nq, static_cast<const char*>(t4) + (size_t)sample * 256, tp + sample, nt - sample, pb, index_base + (uint32_t)sample, parts_b, s, thr,
+                       /*timed=*/true, K);
+        merge_topk_device(parts_b, pb.splits + 1, nq, K, topk, s);
     } else {
-        const HmPlan p = hm_plan(nq, nt);
-        uint64_t* parts = p.splits == 1 ? top2 : c.alloc_n<uint64_t>((size_t)p.splits * nq * 2);
-        hm_scan_device(q4, qp, nq, t4, tp, nt, p, index_base, parts, s);
-        if (p.splits > 1) merge_topk_device(parts, p.splits, nq, 2, top2, s);
+        const HmPlan p = hm_plan(nq, nt, K);
+        uint64_t* parts = p.splits == 1 ? topk : c.alloc_n<uint64_t>((size_t)p.splits * nq * K);
+        hm_scan_device(q4, qp, nq, t4, tp, nt, p, index_base, parts, s, nullptr, /*timed=*/true, K);
+        if (p.splits > 1) merge_topk_device(parts, p.splits, nq, K, topk, s);
     }
-    if (k == 1) take_first_columns_device(top2, nq, 2, 1, out, s);
+    if (k != K) take_first_columns_device(topk, nq, K, k, out, s);
     HIP_CHECK(hipGetLastError());
 }
 
-// Top-k (k = 1 or 2) of nq queries over nt train rows, both 64-byte rows on the device. out: nq * k keys (distance << 32 | row + index_base).
+// Top-k (1 <= k <= 8) of nq queries over nt train rows, both 64-byte rows on the device. out: nq * k keys (distance << 32 | row + index_base).
 void hamming_mfma_topk_device(const void* q, int nq, const void* t, long long nt, uint32_t index_base, int k, uint64_t* out, hipStream_t s) {
-    APDS_REQUIRE(k == 1 || k == 2, APDS_ERR_ASSERT, "the matrix-core matcher serves k = 1 and k = 2");
+    APDS_REQUIRE(k >= 1 && k <= 8, APDS_ERR_ASSERT, "the matrix-core matcher serves 1 <= k <= 8");
     APDS_REQUIRE(nq > 0 && nt > 0 && nt < (1ll << 31), APDS_ERR_ASSERT, "the matrix-core matcher needs queries and train rows");
     ThreadCtx& c = ctx();
     void* t4 = c.alloc((size_t)hm_padded_rows(nt) * 256);
@@ -470,7 +703,7 @@ void hamming_mfma_topk_device(const void* q, int nq, const void* t, long long nt
 // The same against a train set expanded once (hm_train_create).
 void hamming_mfma_topk_train_device(const void* q, int nq, const void* train, uint32_t index_base, int k, uint64_t* out, hipStream_t s) {
     const HmTrain* t = static_cast<const HmTrain*>(train);
-    APDS_REQUIRE(t && (k == 1 || k == 2) && nq > 0, APDS_ERR_ASSERT, "the matrix-core matcher needs an expanded train set, queries and k = 1 or 2");
+    APDS_REQUIRE(t && k >= 1 && k <= 8 && nq > 0, APDS_ERR_ASSERT, "the matrix-core matcher needs an expanded train set, queries and 1 <= k <= 8");
     hm_topk_expanded(q, nq, t->rows, t->pc, t->n, index_base, k, out, s);
 }
 

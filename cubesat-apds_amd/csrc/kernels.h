@@ -6,11 +6,13 @@
 namespace apds {
 
 // match_hamming.hip
-// backend: 0 = the configured one (APDS_MATCH_MFMA), 1 = vector ALU (hamming_topk_kernel), 2 = matrix cores (hamming_mfma_kernel, k <= 2)
+// backend: 0 = the configured one (APDS_MATCH_MFMA, APDS_MATCH_MFMA_KMAX), 1 = vector ALU (hamming_topk_kernel), 2 = matrix cores (hamming_mfma_kernel, k <= 2),
+// 3 = matrix cores (k <= 2 as backend 2; 3 <= k <= 8: hamming_mfma_topk_kernel)
 void hamming_topk_device(const void* q, int nq, const void* t, long long nt, uint32_t index_base, int k, uint64_t* out, hipStream_t s, int backend = 0);
 void merge_topk_device(const uint64_t* parts, int nparts, int nq, int k, uint64_t* out, hipStream_t s);
 void take_first_columns_device(const uint64_t* in, int nq, int kin, int kout, uint64_t* out, hipStream_t s);
-// hamming_mfma.hip: the same keys for k = 1, 2 from the FP4 matrix pipe (bit -> e2m1 operand, exact)
+// hamming_mfma.hip: the same keys for 1 <= k <= 8 from the FP4 matrix pipe (bit -> e2m1 operand, exact). The kernels keep a sorted list of
+// K = 2, 4 or 8 entries per query (the smallest that holds k); hm_plan / hm_scan_device take that K (default: the top-2 kernel)
 void hamming_mfma_topk_device(const void* q, int nq, const void* t, long long nt, uint32_t index_base, int k, uint64_t* out, hipStream_t s);
 struct HmPlan {
     int q_tiles, splits, tiles_per_split;
@@ -22,11 +24,11 @@ struct HmTrain {   // a train set expanded once (256 bytes of fp4 operands per r
     void* rows = nullptr;
     float* pc = nullptr;
 };
-HmPlan hm_plan(int nq, long long nt);
+HmPlan hm_plan(int nq, long long nt, int K = 2);
 long long hm_padded_rows(long long n);   // expanded train rows and their popcounts are padded to whole tiles: allocate this many rows / floats
 void hm_expand_device(const void* rows64, long long n, bool query, void* out_fp4, float* pc, hipStream_t s);
 void hm_scan_device(const void* q_fp4, const float* qpc, int nq, const void* t_fp4, const float* tpc, long long nt, const HmPlan& p, uint32_t index_base,
-                    uint64_t* parts, hipStream_t s, const uint32_t* thr = nullptr, bool timed = true);
+                    uint64_t* parts, hipStream_t s, const uint32_t* thr = nullptr, bool timed = true, int K = 2);
 long long hm_sample_rows(long long nt);
 void* hm_train_create(const void* rows64, long long n, hipStream_t s);
 void hm_train_destroy(void* train);

@@ -337,7 +337,7 @@ int apds_db_knn_match(void* db, const uint8_t* query_desc, int n_query, int desc
         KeypointTable* t = static_cast<KeypointTable*>(db);
         APDS_REQUIRE(t && idx && dist && n_query >= 0, APDS_ERR_BAD_ARG, "bad argument");
         APDS_REQUIRE(desc_bytes >= 1 && desc_bytes <= 64, APDS_ERR_ASSERT, "descriptor length must be 1..64 bytes");
-        APDS_REQUIRE(k == 1 || k == 2, APDS_ERR_ASSERT, "k in {1,2}");
+        APDS_REQUIRE(k >= 1, APDS_ERR_ASSERT, "k >= 1");   // (any k apds_dev_hamming_topk serves: the keys come from the same scan)
         if (!n_query) return;
         ThreadCtx& c = ctx();
         c.ws_reset();

@@ -1177,11 +1177,13 @@ void topk_split_merge(void* h, uint32_t index_base, uint64_t* out, hipStream_t s
 }
 
 // Full top-k of nq queries over nt train rows (device, 64-byte rows). out: nq*k keys. k in {1,2} is the tuned path (the reference only
-// ever consumes the two nearest, lib.rs:107-111); 3 <= k <= 16 run with one query per lane, larger k in pages of 16 (topk_paged_device).
+// ever consumes the two nearest, lib.rs:107-111); 3 <= k <= 16 run with one query per lane here (3 <= k <= APDS_MATCH_MFMA_KMAX on the matrix
+// cores instead: hamming_mfma_topk_kernel), larger k in pages of 16 (topk_paged_device).
 void hamming_topk_device(const void* q, int nq, const void* t, long long nt, uint32_t index_base, int k, uint64_t* out,
                          hipStream_t s, int backend) {
     APDS_REQUIRE(k >= 1, APDS_ERR_ASSERT, "top-k needs k >= 1");
     APDS_REQUIRE(nt < (1ll << 31), APDS_ERR_ASSERT, "train set too large for one call; shard it");
+    APDS_REQUIRE(!(backend == 3 && k > 8), APDS_ERR_ASSERT, "backend 3 (matrix cores) serves k <= 8");
     if (nq <= 0) return;
     if (nt <= 0) {
         HIP_CHECK(hipMemsetAsync(out, 0xFF, (size_t)nq * k * 8, s));
@@ -1191,8 +1193,10 @@ void hamming_topk_device(const void* q, int nq, const void* t, long long nt, uin
         topk_paged_device(q, nq, t, nt, index_base, k, out, s);
         return;
     }
-    APDS_REQUIRE(backend >= 0 && backend <= 2 && !(backend == 2 && k > 2), APDS_ERR_ASSERT, "backend: 0 default, 1 vector ALU, 2 matrix cores (k <= 2)");
-    if (k <= 2 && (backend == 2 || (backend == 0 && config().match_mfma))) {   // the two nearest (all the crate surface consumes) come from the matrix cores
+    APDS_REQUIRE(backend >= 0 && backend <= 3 && !(backend == 2 && k > 2) && !(backend == 3 && k > 8), APDS_ERR_ASSERT,
+                 "backend: 0 default, 1 vector ALU, 2 matrix cores (k <= 2), 3 matrix cores (k <= 8)");
+    // the two nearest (all the crate surface consumes) come from the matrix cores, and so do 3 <= k <= APDS_MATCH_MFMA_KMAX
+    if (backend == 2 || backend == 3 || (backend == 0 && config().match_mfma && k <= std::max(2, config().match_mfma_kmax))) {
         hamming_mfma_topk_device(q, nq, t, nt, index_base, k, out, s);
         return;
     }

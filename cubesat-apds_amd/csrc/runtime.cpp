@@ -40,6 +40,7 @@ const Config& config() {
         k.event_scope = env("APDS_EVENT_SCOPE", 2);
         k.flag_fork = env("APDS_FLAG_FORK", 0);
         k.match_mfma = env("APDS_MATCH_MFMA", 1);
+        k.match_mfma_kmax = std::max(2, std::min(8, env("APDS_MATCH_MFMA_KMAX", 8)));
         k.match_mfma_xcd = env("APDS_MATCH_MFMA_XCD", 1);
         k.match_mfma_splits = env("APDS_MATCH_MFMA_SPLITS", 0);
         k.match_mfma_sample = env("APDS_MATCH_MFMA_SAMPLE", 16384);

@@ -74,7 +74,7 @@ struct HipDevice final : Device {
         // the scan's scratch is the calling thread's workspace, from its start: scans issued by one thread must be ordered on the GPU
         // (one stream, or events), exactly as for apds_dev_hamming_topk
         ctx().ws_reset();
-        if (k <= 2 && config().match_mfma && nq > 0 && n_rows > 0) {
+        if (k <= std::max(2, config().match_mfma_kmax) && config().match_mfma && nq > 0 && n_rows > 0) {   // (APDS_MATCH_MFMA_KMAX: hamming_topk_device's routing)
             void* train = nullptr;
             {
                 std::lock_guard<std::mutex> g(expanded_m);

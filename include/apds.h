@@ -96,8 +96,8 @@ int apds_get_knn_matches(const uint8_t* origin_desc, int n_origin, const uint8_t
 int apds_get_bruteforce_matches(const uint8_t* origin_desc, int n_origin, const uint8_t* target_desc, int n_target,
                                 int desc_bytes, apds_dmatch** matches, int* n_matches);
 
-/* BFMatcher::knnMatch itself (lib.rs:103), any k >= 1 (k <= 2 is the tuned path; above 16 the scan runs once per 16 neighbours): idx/dist are
- * n_query*k, -1 / INT32_MAX where fewer than k exist. */
+/* BFMatcher::knnMatch itself (lib.rs:103), any k >= 1 (k <= 2 is the tuned path; k <= APDS_MATCH_MFMA_KMAX runs on the matrix cores like it,
+ * see apds_dev_hamming_topk; above 16 the scan runs once per 16 neighbours): idx/dist are n_query*k, -1 / INT32_MAX where fewer than k exist. */
 int apds_knn_match(const uint8_t* query_desc, int n_query, const uint8_t* train_desc, int n_train, int desc_bytes,
                    int k, int32_t* idx, int32_t* dist);
 
@@ -234,7 +234,7 @@ int apds_db_insert_image(void* db, const apds_keypoint* kps, const uint8_t* desc
 int apds_db_select(void* db, int mode, int value, float x_start, float y_start, float x_end, float y_end, int* n_out);
 int apds_db_view(void* db, void** rows64_dev, void** kps_dev, void** row_ids_dev, void** image_ids_dev, int* n);
 int apds_db_view_download(void* db, apds_keypoint* kps, uint8_t* desc61, int32_t* ids, int32_t* image_ids);
-/* knnMatch (k in {1,2}) of host query descriptors against the current view; idx = position in the view (= trainIdx of the Vec the reference would hold) */
+/* knnMatch (any k >= 1 that apds_dev_hamming_topk serves) of host query descriptors against the current view; idx = position in the view (= trainIdx of the Vec the reference would hold) */
 int apds_db_knn_match(void* db, const uint8_t* query_desc, int n_query, int desc_bytes, int k, int32_t* idx, int32_t* dist);
 
 /* ---- multi-GPU: the descriptor DB row-sharded over the GPUs of one node (BASELINE config 5) -------------------------------
@@ -410,7 +410,9 @@ int apds_dev_pack_descriptors(const void* src_rows, int64_t n, int desc_bytes, i
 
 /* Hamming top-k (k >= 1) of n_query rows against n_train rows, both 64-byte pitch. k in {1, 2} - all that lib.rs:94-126 consumes - runs on
  * the FP4 matrix pipe (bits as e2m1 operands, exact integer distances; the train rows are expanded to 256-byte operand rows in the calling
- * thread's workspace per call - apds_dev_match_backend); every other k on the vector ALU, above 16 one pass per 16 neighbours.
+ * thread's workspace per call - apds_dev_match_backend), and so does 3 <= k <= APDS_MATCH_MFMA_KMAX (2, 4 or 8, default 8: the same kernel
+ * around a sorted list of 4 or 8 entries per query, same expansion and workspace footprint); every other k on the vector ALU, above 16 one
+ * pass per 16 neighbours.
  * out_keys: n_query*k uint64 = (distance << 32) | (train_index + index_base), ascending; 0xFFFF... when absent.
  * Ordering equals BFMatcher's: by distance, ties to the lower train index. */
 int apds_dev_hamming_topk(const void* query_rows64, int n_query, const void* train_rows64, int64_t n_train,
@@ -437,12 +439,15 @@ int apds_dev_match_lds_cap(int bytes, int* previous);
  * every kernel variant (all tile widths, all k, persistent grid). */
 int apds_dev_match_last_launch_lds(int* bytes);
 /* apds_dev_hamming_topk on a named backend, whatever APDS_MATCH_MFMA says: 0 = the configured one, 1 = vector ALU (xor + popcount,
- * any k), 2 = matrix cores (k <= 2). The keys are the same bit for bit; bench.py times both in one run and tests compare them in one process. */
+ * any k), 2 = matrix cores (k <= 2; APDS_ERR_ASSERT above), 3 = matrix cores (k <= 8: k <= 2 as backend 2, 3 <= k <= 8 on
+ * hamming_mfma_topk_kernel; APDS_ERR_ASSERT above 8). The keys are the same bit for bit; bench.py times backends 1 and 2 in one run, the
+ * tests compare 1 with 2 and 1 with 3 in one process, tools/topk_mfma_probe.py times 1 against 3. */
 int apds_dev_hamming_topk_backend(const void* query_rows64, int n_query, const void* train_rows64, int64_t n_train, uint32_t index_base, int k,
                                   void* out_keys, int backend, void* stream);
 /* Which kernel serves k <= 2 (everything lib.rs:94-126 consumes): *matrix_cores = 1: hamming_mfma_kernel - bits as FP4 (e2m1) operands of
  * v_mfma_scale_f32_16x16x128_f8f6f4, exact integer distances (default); 0: hamming_topk_kernel, xor + popcount on the vector ALU
- * (APDS_MATCH_MFMA=0; also what serves every k > 2). The keys are the same bit for bit. */
+ * (APDS_MATCH_MFMA=0; also what serves every k > APDS_MATCH_MFMA_KMAX). With the matrix cores on, 3 <= k <= APDS_MATCH_MFMA_KMAX run on
+ * hamming_mfma_topk_kernel (timed as "hamming_topk" and "hamming_topk_mfma_k": apds_dev_last_kernel_ms). The keys are the same bit for bit. */
 int apds_dev_match_backend(int* matrix_cores);
 /* Lowe ratio filter on merged keys (k >= 2): writes compacted matches in query order, count to *n_matches (host). */
 int apds_dev_ratio_filter(const void* keys, int n_query, int k, float filter_strength, void* out_matches, int* n_matches, void* stream);
