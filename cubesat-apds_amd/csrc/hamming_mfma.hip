@@ -18,10 +18,15 @@
 //                           fp4 elements are): block = 8 waves x 48 queries held as B operands in registers for the whole kernel,
 //                           128-row train tiles double-buffered in LDS, filled by LDS-DMA (global_load_lds_dwordx4: no staging registers,
 //                           no ds_write) into an XOR-swizzled image (conflict-free ds_read_b128), each A read feeds three MFMAs, running
-//                           top-2 per query column in the lanes, insertion code only when some lane has a hit. (Ranking a block's
-//                           values under the NEXT block's MFMAs was written twice - values carried over, ranking forced between the
-//                           MFMA halves - and both times the compiler put the twelve MFMAs of a block back together and ranked
-//                           behind them; the wait states that costs, s_nop 1 + five ds_reads, are filled by the SIMD's other waves.)
+//                           top-2 per query column in the lanes, insertion code only when some lane has a hit.
+//   The tile loop (hm_scan_tiles, shared with the k = 3 .. 8 kernel) is software-pipelined twice: the DMA of tile n + 1 is in flight
+//   while tile n is computed (issued from assembly - for a DMA it knows of, the compiler waits vmcnt(0) in front of the next ds_read,
+//   because it cannot tell the two buffers of the LDS array apart; each wave waits for its own share in front of the barrier that closes
+//   the tile), and the operands of row block b + 1 are read right behind the twelve MFMAs of block b, under the ranking of block b. Against
+//   the loop that drained the DMA in front of every tile's first MFMA and read a block's operands in front of its own MFMAs: 141.2 ->
+//   148.7 frames/s in the pipeline, median of five alternating runs (profiles/hm_pipeline/ab_bench.txt). (Ranking a block's values under
+//   the NEXT block's MFMAs was written twice - values carried over, ranking forced between the MFMA halves - and both times the compiler
+//   put the twelve MFMAs of a block back together and ranked behind them; those wait states are filled by the SIMD's other waves.)
 #include <atomic>
 #include <memory>
 
@@ -32,6 +37,7 @@ namespace apds {
 
 typedef int hm_v8i __attribute__((ext_vector_type(8)));
 typedef float hm_f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t hm_u32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef APDS_HM_WAVES
 #define APDS_HM_WAVES 8
@@ -118,6 +124,147 @@ __device__ __forceinline__ void hm_insert(HmTop2& b, uint32_t d, uint32_t idx) {
     }
 }
 
+// ---- the tile loop of both kernels ----
+// One wave's share of a tile by LDS-DMA: rows [16 wave, 16 wave + 16) as four pieces of 1 KB (4 rows each). The source of piece i is the
+// wave-uniform tile base + a per-lane constant (voff[i] + 1024 i); the destination is wave-uniform (m0) + 1024 i + 16 lane - the instruction
+// offset counts on both sides. Written as assembly because the DMA has to stay in flight while the tile in the OTHER buffer is read: the
+// compiler cannot tell the two halves of one LDS array apart and, for a DMA it knows of, waits vmcnt(0) in front of the next ds_read
+// (the builtin form of this loop had that wait two instructions behind the DMA issue, in front of every tile's first MFMA). Nothing else
+// in the loop uses the vector-memory counter; the wave that issued a DMA waits for it itself (hm_dma_wait) in front of the barrier
+// behind which the tile is read - a barrier alone does not wait for a DMA. m0 is the compiler's: saved and restored.
+__device__ __forceinline__ void hm_dma_rows(const unsigned char* tile_base, const int (&voff)[4], uint32_t lds_dst) {
+    uint32_t keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %6\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dwordx4 %1, %5\n\t"
+        "global_load_lds_dwordx4 %2, %5 offset:1024\n\t"
+        "global_load_lds_dwordx4 %3, %5 offset:2048\n\t"
+        "global_load_lds_dwordx4 %4, %5 offset:3072\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(tile_base), "s"(lds_dst)
+        : "memory");
+}
+// 64 popcounts (one float per lane)
+__device__ __forceinline__ void hm_dma_popcounts(const float* src, int voff, uint32_t lds_dst) {
+    uint32_t keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %3\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dword %1, %2\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(voff), "s"(src), "s"(lds_dst)
+        : "memory");
+}
+__device__ __forceinline__ void hm_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// A loaded value is in its register from here on: the compiler's wait for it stands in front of this, not at the value's first use (which, for
+// what the kernels load in front of hm_scan_tiles, would be inside the tile loop or behind it - see there).
+template <class T>
+__device__ __forceinline__ void hm_settle(T& v) { asm volatile("" : "+v"(v)); }
+
+// Train tiles [tile_begin, tile_end) against the NC x 16 query columns a wave holds as B operands; rank(acc, row0) takes the values of a
+// 16-row block (acc[c][j]: row row0 + j of the block's row group against column block c).
+// The schedule, per wave:
+//     DMA of tile n + 1 into the other buffer      (in flight until the wait below)
+//     8 x { 4 NC MFMAs of block b | ds_reads of block b + 1 | ranking of block b }
+// The operands of a block (four ds_read_b128 + the popcount preset) are read right behind the MFMAs of the block before - an A register is
+// free once the last MFMA that reads it has issued - so the LDS latency runs under the ranking instead of in front of the first MFMA.
+// Behind the LAST block's MFMAs stand the wait for this wave's DMA and the workgroup barrier (everybody's reads of this tile have fed
+// their MFMAs; everybody's share of the next tile has landed), then block 0 of the next tile is read, then the last block is ranked: the
+// tile border costs the barrier and nothing else. (After the last tile of a split the read fetches whatever the other buffer holds; it
+// is not used.)
+template <int NC, int PRIO, class Rank>
+__device__ __forceinline__ void hm_scan_tiles(const uint4* __restrict__ train_fp4, const float* __restrict__ tpc, int tile_begin, int tile_end,
+                                              uint4 (&B)[NC][4], uint32_t index_base, Rank&& rank) {
+    extern __shared__ __attribute__((aligned(128))) unsigned char hm_lds[];
+    constexpr int TILE_BYTES = HM_TM * 256;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int col = lane & 15, kq = lane >> 4;
+    const uint32_t lds0 = (uint32_t)(__SIZE_TYPE__)(__attribute__((address_space(3))) unsigned char*)hm_lds;
+    // (the expanded rows are padded to whole tiles - zero rows with a popcount of +inf - so a piece's source is a uniform tile base plus a
+    // per-lane constant: scalar address arithmetic only)
+    int voff[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int r = 16 * wave + 4 * i + (lane >> 4);
+        voff[i] = r * 256 + (((lane & 15) ^ (r & 15)) << 4) - 1024 * i;
+    }
+    auto stage = [&](int tile, int buf) {
+        hm_dma_rows(reinterpret_cast<const unsigned char*>(train_fp4) + (size_t)tile * TILE_BYTES, voff, lds0 + buf * TILE_BYTES + 16 * wave * 256);
+        if (wave < HM_TM / 64) hm_dma_popcounts(tpc + (size_t)tile * HM_TM + 64 * wave, 4 * lane, lds0 + 2 * TILE_BYTES + buf * (HM_TM * 4) + 256 * wave);
+    };
+    // this lane's four A reads of a 16-row block: row (16 rb + col), chunk 4 s + kq at position (4 s + kq) ^ col; behind them the popcounts
+    // of rows 4 kq .. + 3 of a block. Offsets into the buffer being read: they change sides at every tile border.
+    // (LDS addresses as integers: the array's base is folded in once, a read is one ds_read_b128 with an immediate offset)
+    typedef const __attribute__((address_space(3))) hm_u32x4* lds_u4;
+    typedef const __attribute__((address_space(3))) hm_f32x4* lds_f4;
+    uint32_t ra[4], rn = lds0 + 2 * TILE_BYTES + 16 * kq;
+#pragma unroll
+    for (int s = 0; s < 4; s++) ra[s] = lds0 + col * 256 + (((4 * s + kq) ^ col) << 4);
+
+    hm_u32x4 a[4];
+    hm_f32x4 init;                                            // biased popcounts of this lane's four rows
+    auto read_block = [&](int rb) {
+#pragma unroll
+        for (int s = 0; s < 4; s++) a[s] = *(lds_u4)(__SIZE_TYPE__)(ra[s] + rb * 4096);
+        init = *(lds_f4)(__SIZE_TYPE__)(rn + rb * 64);
+    };
+
+    // Everything the compiler loaded for this wave so far (the B operands, the thresholds) is waited for HERE: it counts its own loads only,
+    // so a wait of its making behind the first DMA would both count wrongly and, inside the loop, drain the prefetch once per tile.
+#pragma unroll
+    for (int c = 0; c < NC; c++)
+#pragma unroll
+        for (int s = 0; s < 4; s++) hm_settle(B[c][s].x), hm_settle(B[c][s].y), hm_settle(B[c][s].z), hm_settle(B[c][s].w);
+    hm_dma_wait();
+    stage(tile_begin, 0);
+    hm_dma_wait();
+    __syncthreads();
+    read_block(0);
+    hm_f32x4 acc[NC];
+    for (int tile = tile_begin; tile < tile_end; tile++) {
+        const int buf = (tile - tile_begin) & 1;
+        if (tile + 1 < tile_end) stage(tile + 1, buf ^ 1);
+#pragma unroll
+        for (int rb = 0; rb < HM_TM / 16; rb++) {                  // 16-row blocks of the tile
+            // a wave about to feed the matrix pipe goes ahead of the SIMD's waves that are ranking: 5.94 -> 5.60 ms alone, 139.4 -> 147.3
+            // frames/s in the pipeline (profiles/r04/mfma_prio_ab.txt, ab_bench_env.txt); levels 1, 2, 3 alike
+            if (PRIO) __builtin_amdgcn_s_setprio(PRIO);
+#pragma unroll
+            for (int s = 0; s < 4; s++) {
+                const hm_v8i A = {(int)a[s].x, (int)a[s].y, (int)a[s].z, (int)a[s].w, 0, 0, 0, 0};
+#pragma unroll
+                for (int c = 0; c < NC; c++) {
+                    const hm_v8i Bv = {(int)B[c][s].x, (int)B[c][s].y, (int)B[c][s].z, (int)B[c][s].w, 0, 0, 0, 0};
+                    acc[c] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(A, Bv, s == 0 ? init : acc[c], 4, 4, 0, HM_UNIT_SCALE, 0, HM_UNIT_SCALE);
+                }
+            }
+            if (PRIO) __builtin_amdgcn_s_setprio(0);
+            if (rb + 1 < HM_TM / 16) {
+                read_block(rb + 1);
+            } else {
+                hm_dma_wait();
+                __syncthreads();   // the next tile has landed; everybody's MFMAs have taken the last of this one
+#pragma unroll
+                for (int s = 0; s < 4; s++) ra[s] += buf ? -TILE_BYTES : TILE_BYTES;
+                rn += buf ? -HM_TM * 4 : HM_TM * 4;
+                read_block(0);
+            }
+            // The accumulators are pinned behind the reads and the reads in front of the ranking: left alone, the compiler sinks the MFMAs of
+            // the later column blocks behind the first block's ranking, the A registers stay live across the reads, and the next block's
+            // operands take twenty registers of their own.
+#pragma unroll
+            for (int c = 0; c < NC; c++) hm_settle(acc[c]);
+            __builtin_amdgcn_sched_barrier(0);
+            rank(acc, (uint32_t)(tile * HM_TM + rb * 16 + 4 * kq) + index_base);
+        }
+    }
+}
+
 // out[split][nq][2]: keys (distance << 32 | row + index_base), EMPTY where the split holds fewer than two rows.
 // LDS image of a tile (no padding: the tile is filled by LDS-DMA, whose destination is wave-uniform base + 16 * lane): row r at 256 r, and
 // its 16-byte chunk c at position c ^ (r & 15) - the 16 rows a ds_read_b128 group reads chunk c of then sit in 16 different bank groups.
@@ -131,8 +278,6 @@ __global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(A
                                                            int q_tiles, int splits, uint32_t index_base, const uint32_t* __restrict__ thr,
                                                            uint64_t* __restrict__ out) {
     // (no APDS_RAISE_WAVE_PRIORITY here: this is the kernel the short kernels of the other stages raise their priority against)
-    extern __shared__ __attribute__((aligned(128))) unsigned char hm_lds[];
-    constexpr int TILE_BYTES = HM_TM * 256;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // Workgroup b runs on XCD b % 8 (round-robin dispatch) and every XCD has an L2 of its own. With a multiple of eight splits, split
     // x + 8 m belongs to XCD x: the workgroups resident on an XCD at any time are consecutive query tiles of one split, start together and
@@ -167,38 +312,13 @@ __global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(A
     HmTop2 best[HM_NC];
 #pragma unroll
     for (int c = 0; c < HM_NC; c++) {
-        best[c].d0 = best[c].d1 = THR ? thr[min(q0 + 16 * c + col, nq - 1)] : 0x7F800000u;
+        best[c].d0 = THR ? thr[min(q0 + 16 * c + col, nq - 1)] : 0x7F800000u;
+        hm_settle(best[c].d0), hm_settle(qq[c]);
+        best[c].d1 = best[c].d0;
         best[c].i0 = best[c].i1 = 0xFFFFFFFFu;
     }
 
     if (tile_begin < tile_end) {
-        // staging by LDS-DMA: 32 pieces of 1 KB (4 rows) per tile, four per wave: wave w fills rows [16 w, 16 w + 16); + the popcounts
-        // (two pieces of 64 floats, waves 0 and 1)
-        // (the expanded rows are padded to whole tiles - zero rows with a popcount of +inf - so a piece's source is a uniform tile base plus a
-        // per-lane constant: scalar address arithmetic only)
-        int soff[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int r = 16 * wave + 4 * i + (lane >> 4);
-            soff[i] = r * 256 + (((lane & 15) ^ (r & 15)) << 4);
-        }
-        auto stage = [&](int tile, int buf) {
-            const unsigned char* tbase = reinterpret_cast<const unsigned char*>(train_fp4) + (size_t)tile * TILE_BYTES;   // wave-uniform
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tbase + soff[i]),
-                                                 (__attribute__((address_space(3))) void*)(hm_lds + buf * TILE_BYTES + (16 * wave + 4 * i) * 256), 16, 0, 0);
-            if (wave < HM_TM / 64)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tpc + (size_t)tile * HM_TM + 64 * wave + lane),
-                                                 (__attribute__((address_space(3))) void*)(hm_lds + 2 * TILE_BYTES + buf * (HM_TM * 4) + 256 * wave), 4, 0, 0);
-        };
-        // this lane's four A reads of a 16-row block: row (16 rb + col), chunk 4 s + kq at position (4 s + kq) ^ col
-        int aoff[4];
-#pragma unroll
-        for (int s = 0; s < 4; s++) aoff[s] = col * 256 + (((4 * s + kq) ^ col) << 4);
-        const int noff = 2 * TILE_BYTES + 16 * kq;                // popcounts of rows 4 kq .. + 3 of a block
-
-        hm_f32x4 acc[HM_NC];
         // Ranking a block: one minimum and one compare per 16 x 16 accumulator in the common case. Only the query blocks in which some lane
         // has a hit run insertion code (a wave-uniform branch each): the counters put the vector instructions beside the MFMAs at 1.9 per
         // MFMA when any hit sent all three query blocks through the twelve insertions, and an MFMA leaves the SIMD's issue port free for
@@ -207,7 +327,7 @@ __global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(A
         // (profiles/r04/match_mfma_probe_single_threshold.txt): a chain of six dependent minima in front of the branch. The twelve MFMAs as
         // three chains of four with the previous chain's minimum / test placed between the next chain's MFMAs by sched_group_barrier: the
         // compiler follows the directives, keeps its wait states (it counts an MFMA as one), and nothing changes: 5.45 - 5.51 ms.)
-        auto rank = [&](const hm_f32x4 (&a)[HM_NC], uint32_t row0) {
+        hm_scan_tiles<HM_NC, PRIO>(train_fp4, tpc, tile_begin, tile_end, B, index_base, [&](const hm_f32x4 (&a)[HM_NC], uint32_t row0) {
             bool hit[HM_NC];
 #pragma unroll
             for (int c = 0; c < HM_NC; c++) {
@@ -220,41 +340,7 @@ __global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(A
 #pragma unroll
                     for (int j = 0; j < 4; j++) hm_insert(best[c], __float_as_uint(a[c][j]), row0 + j);
                 }
-        };
-
-        stage(tile_begin, 0);
-        __syncthreads();   // (drains the DMA: vmcnt(0) in front of the barrier)
-        for (int tile = tile_begin; tile < tile_end; tile++) {
-            const int buf = (tile - tile_begin) & 1;
-            if (tile + 1 < tile_end) stage(tile + 1, buf ^ 1);     // lands while this tile is computed; the closing barrier waits for it
-            const unsigned char* T = hm_lds + buf * TILE_BYTES;
-            const unsigned char* Nn = hm_lds + noff + buf * (HM_TM * 4);
-#pragma unroll
-            for (int rb = 0; rb < HM_TM / 16; rb++) {                  // 16-row blocks of the tile
-                const hm_f32x4 init = *reinterpret_cast<const hm_f32x4*>(Nn + rb * 64);   // biased popcounts of this lane's four rows
-                uint4 a[4];
-#pragma unroll
-                for (int s = 0; s < 4; s++) a[s] = *reinterpret_cast<const uint4*>(T + rb * 4096 + aoff[s]);
-                auto steps = [&](int s_lo, int s_hi) {
-#pragma unroll
-                    for (int s = s_lo; s < s_hi; s++) {
-                        const hm_v8i A = {(int)a[s].x, (int)a[s].y, (int)a[s].z, (int)a[s].w, 0, 0, 0, 0};
-#pragma unroll
-                        for (int c = 0; c < HM_NC; c++) {
-                            const hm_v8i Bv = {(int)B[c][s].x, (int)B[c][s].y, (int)B[c][s].z, (int)B[c][s].w, 0, 0, 0, 0};
-                            acc[c] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(A, Bv, s == 0 ? init : acc[c], 4, 4, 0, HM_UNIT_SCALE, 0, HM_UNIT_SCALE);
-                        }
-                    }
-                };
-                // a wave about to feed the matrix pipe goes ahead of the SIMD's waves that are ranking: 5.94 -> 5.60 ms alone, 139.4 -> 147.3
-                // frames/s in the pipeline (profiles/r04/mfma_prio_ab.txt, ab_bench_env.txt); levels 1, 2, 3 alike
-                if (PRIO) __builtin_amdgcn_s_setprio(PRIO);
-                steps(0, 4);
-                if (PRIO) __builtin_amdgcn_s_setprio(0);
-                rank(acc, (uint32_t)(tile * HM_TM + rb * 16 + 4 * kq) + index_base);
-            }
-            __syncthreads();   // the next tile has landed; everybody is done with this one
-        }
+        });
     }
     // a query column lives in four lanes (kq = 0..3, different rows): fold them with shuffles, lanes 0..15 write
 #pragma unroll
@@ -338,8 +424,6 @@ template <int K, int NC, int PRIO, bool THR>
 __global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(APDS_HM_WPE, APDS_HM_WPE))) void hamming_mfma_topk_kernel(
     const uint4* __restrict__ train_fp4, const float* __restrict__ tpc, int n_train, const uint4* __restrict__ query_fp4, const float* __restrict__ qpc, int nq,
     int tiles_per_split, int q_tiles, int splits, uint32_t index_base, const uint32_t* __restrict__ thr, uint64_t* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(128))) unsigned char hm_lds[];
-    constexpr int TILE_BYTES = HM_TM * 256;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int split, qtile;   // (splits pinned to the XCDs: see hamming_mfma_kernel)
     if ((splits & 7) == 0) {
@@ -370,38 +454,17 @@ __global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(A
     HmTopK<K> best[NC];
 #pragma unroll
     for (int c = 0; c < NC; c++) {
-        const uint32_t start = THR ? thr[min(q0 + 16 * c + col, nq - 1)] : 0x7F800000u;
+        uint32_t start = THR ? thr[min(q0 + 16 * c + col, nq - 1)] : 0x7F800000u;
+        hm_settle(start), hm_settle(qq[c]);
 #pragma unroll
         for (int j = 0; j < K; j++) best[c].d[j] = start, best[c].i[j] = 0xFFFFFFFFu;
     }
 
     if (tile_begin < tile_end) {
-        int soff[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int r = 16 * wave + 4 * i + (lane >> 4);
-            soff[i] = r * 256 + (((lane & 15) ^ (r & 15)) << 4);
-        }
-        auto stage = [&](int tile, int buf) {
-            const unsigned char* tbase = reinterpret_cast<const unsigned char*>(train_fp4) + (size_t)tile * TILE_BYTES;   // wave-uniform
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tbase + soff[i]),
-                                                 (__attribute__((address_space(3))) void*)(hm_lds + buf * TILE_BYTES + (16 * wave + 4 * i) * 256), 16, 0, 0);
-            if (wave < HM_TM / 64)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tpc + (size_t)tile * HM_TM + 64 * wave + lane),
-                                                 (__attribute__((address_space(3))) void*)(hm_lds + 2 * TILE_BYTES + buf * (HM_TM * 4) + 256 * wave), 4, 0, 0);
-        };
-        int aoff[4];
-#pragma unroll
-        for (int s = 0; s < 4; s++) aoff[s] = col * 256 + (((4 * s + kq) ^ col) << 4);
-        const int noff = 2 * TILE_BYTES + 16 * kq;
-
-        hm_f32x4 acc[NC];
         // The common case is the top-2 kernel's: one minimum and one compare per accumulator, against the K-th value. Behind the wave-uniform
         // branch every one of the four rows is tested again (against the K-th value as the rows before it left it): an insertion is about
         // 6 K instructions, and most blocks with a hit have it in one row.
-        auto rank = [&](const hm_f32x4 (&a)[NC], uint32_t row0) {
+        hm_scan_tiles<NC, PRIO>(train_fp4, tpc, tile_begin, tile_end, B, index_base, [&](const hm_f32x4 (&a)[NC], uint32_t row0) {
             bool hit[NC];
 #pragma unroll
             for (int c = 0; c < NC; c++) {
@@ -417,36 +480,7 @@ __global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(A
                         if (__any(v < best[c].d[K - 1])) hm_insert_k<K>(best[c], v, row0 + j);
                     }
                 }
-        };
-
-        stage(tile_begin, 0);
-        __syncthreads();
-        for (int tile = tile_begin; tile < tile_end; tile++) {
-            const int buf = (tile - tile_begin) & 1;
-            if (tile + 1 < tile_end) stage(tile + 1, buf ^ 1);
-            const unsigned char* T = hm_lds + buf * TILE_BYTES;
-            const unsigned char* Nn = hm_lds + noff + buf * (HM_TM * 4);
-#pragma unroll
-            for (int rb = 0; rb < HM_TM / 16; rb++) {
-                const hm_f32x4 init = *reinterpret_cast<const hm_f32x4*>(Nn + rb * 64);
-                uint4 a[4];
-#pragma unroll
-                for (int s = 0; s < 4; s++) a[s] = *reinterpret_cast<const uint4*>(T + rb * 4096 + aoff[s]);
-                if (PRIO) __builtin_amdgcn_s_setprio(PRIO);
-#pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    const hm_v8i A = {(int)a[s].x, (int)a[s].y, (int)a[s].z, (int)a[s].w, 0, 0, 0, 0};
-#pragma unroll
-                    for (int c = 0; c < NC; c++) {
-                        const hm_v8i Bv = {(int)B[c][s].x, (int)B[c][s].y, (int)B[c][s].z, (int)B[c][s].w, 0, 0, 0, 0};
-                        acc[c] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(A, Bv, s == 0 ? init : acc[c], 4, 4, 0, HM_UNIT_SCALE, 0, HM_UNIT_SCALE);
-                    }
-                }
-                if (PRIO) __builtin_amdgcn_s_setprio(0);
-                rank(acc, (uint32_t)(tile * HM_TM + rb * 16 + 4 * kq) + index_base);
-            }
-            __syncthreads();
-        }
+        });
     }
     // A query column lives in four lanes (kq = 0..3) whose rows interleave: the lists are folded as (value, row) pairs - one 64-bit key each,
     // a list entry without a row (0xFFFFFFFF) behind every row of its value. Two sorted K-lists -> the K smallest, sorted: min(mine[j],
