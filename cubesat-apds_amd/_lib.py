@@ -34,7 +34,20 @@ SYMBOLS = [
     "apds_pipeline_create", "apds_pipeline_submit", "apds_pipeline_poll", "apds_pipeline_stats", "apds_pipeline_destroy", "apds_pipeline_enable_pose",
     "apds_pipeline_poll_pose",
     "apds_dev_topk_state_create", "apds_dev_topk_state_destroy", "apds_dev_topk_prepass", "apds_dev_topk_scan", "apds_dev_topk_merge",
+    "apds_mosaic_create", "apds_mosaic_destroy", "apds_mosaic_info", "apds_mosaic_min_max", "apds_resample_weights", "apds_mosaic_window",
+    "apds_mosaic_tile_extract", "apds_mosaic_tile_extract_batch",
 ]
+
+RESAMPLE_NEAREST, RESAMPLE_LANCZOS = 0, 1
+RESAMPLE_MODES = {"nearest": RESAMPLE_NEAREST, "lanczos": RESAMPLE_LANCZOS}
+
+
+def resample_mode(name):
+    """"nearest" | "lanczos" -> APDS_RESAMPLE_*"""
+    try:
+        return RESAMPLE_MODES[name]
+    except (KeyError, TypeError):
+        raise ApdsError(ERR_BAD_ARG, f"unknown resampling mode {name!r}: 'nearest' or 'lanczos'") from None
 
 # multi-GPU sharded matcher (include/apds.h: apds_comm_id, apds_host_transport)
 TRANSPORT_RCCL, TRANSPORT_LOOPBACK, TRANSPORT_HOST, TRANSPORT_DEVICE = 0, 1, 2, 3
@@ -228,6 +241,14 @@ def lib():
             "apds_dev_topk_prepass": (i, [vp, vp, i, vp, i64, u32, i, vp]),
             "apds_dev_topk_scan": (i, [vp, vp, vp, vp]),
             "apds_dev_topk_merge": (i, [vp, u32, vp, vp]),
+            "apds_mosaic_create": (i, [pp, vp, vp, vp, i, i, sz, i]),
+            "apds_mosaic_destroy": (i, [vp]),
+            "apds_mosaic_info": (i, [vp, ip, ip]),
+            "apds_mosaic_min_max": (i, [vp, vp]),
+            "apds_resample_weights": (i, [i, d, d, i, i, i, vp, vp, vp]),
+            "apds_mosaic_window": (i, [vp, i, i, i, i, i, i, i, vp]),
+            "apds_mosaic_tile_extract": (i, [vp, i, i, i, i, i, i, i, vp, i, pp, pp, ip, ip]),
+            "apds_mosaic_tile_extract_batch": (i, [vp, vp, i, i, i, i, i, i, vp, i, pp, pp, ip, ip]),
         }
         for name, (rt, at) in sig.items():
             fn = getattr(L, name)

@@ -194,6 +194,73 @@ int apds_tile_extract_batch(const float* const* red, const float* const* green, 
     });
 }
 
+// apds_tile_extract on a window of the resident mosaic (geotiff_extractor mod.rs:332-343 read_as(.., Lanczos) in front of the chain): the
+// resampled bands, the BGRA image and the extraction all stay on the device.
+int apds_mosaic_tile_extract(void* mosaic, int x0, int y0, int win_w, int win_h, int out_w, int out_h, int resample, const double* minmax6, int max_points,
+                             apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes) {
+    APDS_RANGE("apds_mosaic_tile_extract");
+    return guarded([&] {
+        APDS_REQUIRE(kps && desc && n && desc_bytes, APDS_ERR_BAD_ARG, "null output");
+        *kps = nullptr;
+        *desc = nullptr;
+        *n = 0;
+        *desc_bytes = APDS_DESC_BYTES;
+        Mosaic* m = static_cast<Mosaic*>(mosaic);
+        const int32_t xy0[2] = {x0, y0};
+        mosaic_check_window(m, xy0, 1, win_w, win_h, out_w, out_h, resample);
+        if (max_points <= 0) max_points = APDS_MAX_POINTS;
+        double own[6];
+        if (!minmax6) {
+            mosaic_min_max(m, own);
+            minmax6 = own;
+        }
+        ThreadCtx& c = ctx();
+        c.ws_reset();
+        hipStream_t s = c.stream;
+        const size_t px = (size_t)out_w * out_h;
+        float* bands = c.alloc_n<float>(3 * px);
+        uint8_t* dimg = c.alloc_n<uint8_t>(px * 4);
+        mosaic_window_device(m, xy0, 1, win_w, win_h, out_w, out_h, resample, bands, s);
+        band_merger_device(bands, bands + px, bands + 2 * px, px, minmax6, /*bgra=*/1, dimg, s);
+        extract_to_host(c, s, dimg, out_h, out_w, 4, (size_t)out_w * 4, max_points, kps, desc, n);
+    });
+}
+
+// apds_tile_extract_batch on n_tiles windows of the resident mosaic: ONE resampling launch per pass, ONE band_merger pass and ONE batched
+// extraction serve all tiles.
+int apds_mosaic_tile_extract_batch(void* mosaic, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample, const double* minmax6,
+                                   int max_points, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes) {
+    APDS_RANGE("apds_mosaic_tile_extract_batch");
+    return guarded([&] {
+        APDS_REQUIRE(kps && desc && counts && desc_bytes, APDS_ERR_BAD_ARG, "null output");
+        *kps = nullptr;
+        *desc = nullptr;
+        *desc_bytes = APDS_DESC_BYTES;
+        Mosaic* m = static_cast<Mosaic*>(mosaic);
+        mosaic_check_window(m, xy0, n_tiles, win_w, win_h, out_w, out_h, resample);
+        if (max_points <= 0) max_points = APDS_MAX_POINTS;
+        for (int i = 0; i < n_tiles; i++) counts[i] = 0;
+        double own[6];
+        if (!minmax6) {
+            mosaic_min_max(m, own);
+            minmax6 = own;
+        }
+        ThreadCtx& c = ctx();
+        c.ws_reset();
+        hipStream_t s = c.stream;
+        const size_t px = (size_t)out_w * out_h, all = px * n_tiles;
+        float* bands = c.alloc_n<float>(3 * all);   // band-major: all tiles' red, then green, then blue
+        uint8_t* dimg = c.alloc_n<uint8_t>(all * 4);
+        const int capacity = batch_capacity(out_h, out_w, max_points);
+        apds_keypoint* dk = c.alloc_n<apds_keypoint>((size_t)capacity * n_tiles);
+        uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * 64 * n_tiles);
+        mosaic_window_device(m, xy0, n_tiles, win_w, win_h, out_w, out_h, resample, bands, s);
+        band_merger_device(bands, bands + all, bands + 2 * all, all, minmax6, /*bgra=*/1, dimg, s);
+        akaze_extract_batch_device(dimg, n_tiles, px * 4, out_h, out_w, 4, (size_t)out_w * 4, max_points, dk, dd, capacity, counts, s);
+        batch_results_to_host(c, s, dk, dd, capacity, n_tiles, counts, kps, desc);
+    });
+}
+
 // n_images equal-sized host images in one call: one upload, one batched extraction (every kernel's grid covers all images), one download.
 // Outputs: concatenated keypoints / 61-byte descriptors (image 0's rows first), counts[i] rows per image.
 int apds_akaze_extract_batch(const uint8_t* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride, int max_points,

@@ -149,6 +149,44 @@ def tiles_keypoint_descriptor_extraction(windows, min_max, max_points=None):
     return out
 
 
+def mosaic_tile_keypoint_descriptor_extraction(mosaic, window, window_size, size, resample="nearest", min_max=None, max_points=None):
+    """tile_keypoint_descriptor_extraction on a window of a geotiff_extractor.DeviceMosaic: window (x, y) and window_size (w, h) in raster
+    pixels, resampled to size (w, h) on the device ("nearest" | "lanczos"), then band_merger, raster_to_mat and the extraction, all in one
+    library call. min_max None = the mosaic's own."""
+    mm = None if min_max is None else min_max.as_array()
+    kps, desc = C.c_void_p(), C.c_void_p()
+    n, nb = C.c_int(0), C.c_int(0)
+    check(lib().apds_mosaic_tile_extract(mosaic.handle, int(window[0]), int(window[1]), int(window_size[0]), int(window_size[1]), int(size[0]), int(size[1]),
+                                         _lib.resample_mode(resample), None if mm is None else ptr(mm), MAX_POINTS if max_points is None else int(max_points),
+                                         C.byref(kps), C.byref(desc), C.byref(n), C.byref(nb)))
+    k = take(kps, n.value, KEYPOINT_DTYPE)
+    d = take(desc, n.value * nb.value, np.uint8).reshape(n.value, nb.value)
+    return ExtractedKeyPoint(k, d)
+
+
+def mosaic_tiles_keypoint_descriptor_extraction(mosaic, windows, window_size, size, resample="nearest", min_max=None, max_points=None):
+    """A batch of tiles of a DeviceMosaic in ONE library call: `windows` = list of (x, y) origins of one window_size and size. Returns a
+    list of ExtractedKeyPoint, each exactly what mosaic_tile_keypoint_descriptor_extraction returns for that tile."""
+    xy = np.ascontiguousarray(np.asarray(list(windows), np.int64).reshape(-1, 2), np.int32)
+    b = len(xy)
+    if not b:
+        return []
+    mm = None if min_max is None else min_max.as_array()
+    kps, desc = C.c_void_p(), C.c_void_p()
+    counts, nb = (C.c_int * b)(), C.c_int(0)
+    check(lib().apds_mosaic_tile_extract_batch(mosaic.handle, ptr(xy), b, int(window_size[0]), int(window_size[1]), int(size[0]), int(size[1]),
+                                               _lib.resample_mode(resample), None if mm is None else ptr(mm),
+                                               MAX_POINTS if max_points is None else int(max_points), C.byref(kps), C.byref(desc), counts, C.byref(nb)))
+    total = sum(counts)
+    k = take(kps, total, KEYPOINT_DTYPE)
+    d = take(desc, total * nb.value, np.uint8).reshape(total, nb.value)
+    out, off = [], 0
+    for c in counts:
+        out.append(ExtractedKeyPoint(k[off:off + c].copy(), d[off:off + c].copy()))
+        off += c
+    return out
+
+
 def _desc(a):
     a = np.ascontiguousarray(a, np.uint8)
     if a.ndim != 2:

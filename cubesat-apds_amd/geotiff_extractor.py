@@ -1,6 +1,7 @@
 """Host-side mirror of the pixel math of the reference crate `geotiff_extractor`
 (/root/reference/geotiff_extractor/src/image_extractor/mod.rs) — the step right before the hot path.
 GDAL I/O itself is out of scope; these functions take the f32 bands GDAL would deliver."""
+import ctypes as C
 import struct
 
 import numpy as np
@@ -138,6 +139,11 @@ class MosaicedDataset:
         if self.bands.ndim != 3 or self.bands.shape[0] < 3:
             raise ValueError("bands: [>=3, H, W] float32")
         self.min_max = None
+        self._device = None
+
+    def to_device(self):
+        """The same raster resident in HBM (DeviceMosaic): windows are resampled and extracted there."""
+        return DeviceMosaic(self.bands)
 
     @classmethod
     def import_mosaic_dataset(cls, path):
@@ -156,21 +162,26 @@ class MosaicedDataset:
             self.min_max = BandsMinMax(mm[0][0], mm[0][1], mm[1][0], mm[1][1], mm[2][0], mm[2][1])
         return self.min_max
 
-    def to_rgb(self, window, window_size, size):
+    def to_rgb(self, window, window_size, size, resample="nearest"):
         """mod.rs:241-269 — window (x, y) and window_size (w, h) in raster pixels, resampled to size (w, h), then band_merger.
-        Returns size[0]*size[1] RGBA8 pixels. The reference resamples with GDAL's Lanczos (mod.rs:339), which is not restated:
-        equal sizes are copied, anything else is decimated by nearest neighbour ((i + 0.5) * window / size, floored)."""
+        Returns size[0]*size[1] RGBA8 pixels. Equal sizes are copied; otherwise resample="nearest" (the default) decimates by nearest
+        neighbour ((i + 0.5) * window / size, floored) on the host, resample="lanczos" is the reference's read (GDAL's Lanczos, mod.rs:339,
+        as DESIGN.md section 2 restates it) on a device copy of the raster."""
         x0, y0 = int(window[0]), int(window[1])
         ww, wh = int(window_size[0]), int(window_size[1])
         ow, oh = int(size[0]), int(size[1])
         W, H = self.raster_size()
         if x0 < 0 or y0 < 0 or ww <= 0 or wh <= 0 or x0 + ww > W or y0 + wh > H or ow <= 0 or oh <= 0:
             raise _lib.ApdsError(_lib.ERR_OUT_OF_RANGE, "window outside the raster")
-        win = self.window(window, window_size, size)
+        win = self.window(window, window_size, size, resample)
         return band_merger([np.ascontiguousarray(win[i]).ravel() for i in range(3)], self.datasets_min_max())
 
-    def window(self, window, window_size, size):
+    def window(self, window, window_size, size, resample="nearest"):
         """The three f32 band windows `to_rgb` merges ([3, size_h, size_w]; a strided view of the mosaic when no resampling is needed)."""
+        if _lib.resample_mode(resample) == _lib.RESAMPLE_LANCZOS:
+            if self._device is None:
+                self._device = self.to_device()       # created on first use, lives as long as the dataset
+            return self._device.window(window, window_size, size, resample)
         x0, y0 = int(window[0]), int(window[1])
         ww, wh = int(window_size[0]), int(window_size[1])
         ow, oh = int(size[0]), int(size[1])
@@ -183,3 +194,62 @@ class MosaicedDataset:
             xs = np.minimum(((np.arange(ow) + 0.5) * (ww / ow)).astype(np.int64), ww - 1)
             win = win[:, ys][:, :, xs]
         return win
+
+
+class DeviceMosaic:
+    """The `MosaicedDataset` methods the preprocessor uses, on a [3, H, W] float32 raster resident in HBM (apds_mosaic_*): min/max is a
+    device reduction, windows are resampled on the device (resample="nearest": the host mirror's rule bit for bit; "lanczos": the
+    reference's read_as(.., Lanczos), mod.rs:332-343), and the preprocessor extracts tiles from it without the bands crossing PCIe."""
+
+    def __init__(self, bands):
+        b = np.asarray(bands)
+        if b.ndim != 3 or b.shape[0] < 3 or b.dtype != np.float32 or b.strides[2] != 4 or b.strides[1] % 4:
+            b = np.ascontiguousarray(bands, np.float32)
+            if b.ndim != 3 or b.shape[0] < 3:
+                raise ValueError("bands: [>=3, H, W] float32")
+        self._shape = (b.shape[1], b.shape[2])
+        self._handle = C.c_void_p()
+        check(lib().apds_mosaic_create(C.byref(self._handle), b[0].ctypes.data, b[1].ctypes.data, b[2].ctypes.data, b.shape[1], b.shape[2],
+                                       b.strides[1] // 4, 0))
+        self.min_max = None
+
+    @property
+    def handle(self):
+        if not self._handle:
+            raise _lib.ApdsError(_lib.ERR_BAD_ARG, "the device mosaic has been closed")
+        return self._handle
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            lib().apds_mosaic_destroy(self._handle)
+            self._handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # noqa: BLE001 (interpreter shutdown)
+            pass
+
+    def raster_size(self):
+        """(width, height)"""
+        return self._shape[1], self._shape[0]
+
+    def datasets_min_max(self):
+        """mod.rs:200-229 — per-band minimum and maximum (NaN ignored), reduced on the device and cached in the handle."""
+        if self.min_max is None:
+            mm = np.zeros(6, np.float64)
+            check(lib().apds_mosaic_min_max(self.handle, ptr(mm)))
+            self.min_max = BandsMinMax(*mm)
+        return self.min_max
+
+    def window(self, window, window_size, size, resample="nearest"):
+        """The three f32 band windows `to_rgb` merges, [3, size_h, size_w], resampled on the device."""
+        out = np.zeros((3, max(int(size[1]), 0), max(int(size[0]), 0)), np.float32)
+        check(lib().apds_mosaic_window(self.handle, int(window[0]), int(window[1]), int(window_size[0]), int(window_size[1]), int(size[0]), int(size[1]),
+                                       _lib.resample_mode(resample), ptr(out)))
+        return out
+
+    def to_rgb(self, window, window_size, size, resample="nearest"):
+        """mod.rs:241-269 — the resampled window through band_merger: size[0]*size[1] RGBA8 pixels."""
+        win = self.window(window, window_size, size, resample)
+        return band_merger([win[i].ravel() for i in range(3)], self.datasets_min_max())

@@ -141,6 +141,41 @@ int apds_tile_extract(const float* red, const float* green, const float* blue, i
 int apds_tile_extract_batch(const float* const* red, const float* const* green, const float* const* blue, int n_tiles, int rows, int cols, size_t row_stride,
                             const double* minmax6, int max_points, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes);
 
+/* The mosaic resident in HBM and the preprocessor's window read on it: geotiff_extractor/src/image_extractor/mod.rs:332-343
+ * read_as::<f32>(window, window_size, size, Some(ResampleAlg::Lanczos)), which preprocessor/src/main.rs:197-277 cuts every level of detail
+ * into tiles with. apds_tile_extract* take host windows of ONE size (no resampling); these calls keep the three bands on the device and
+ * resample there, so a level > 0 tile is filtered (its footprint reaching into the neighbouring tiles) instead of decimated.
+ * resample: APDS_RESAMPLE_NEAREST = index min((int64)((i + 0.5) * (win / out)), win - 1) per axis in double (the host mirror's rule, bit for
+ * bit); APDS_RESAMPLE_LANCZOS = GDAL's convolution resampler restated (per axis ratio = win / out, sw = min(1, 1 / ratio),
+ * radius = 3 / sw, centre c = (i + 0.5) ratio + origin, taps [floor(c - radius + 0.5), (int)(c + radius + 0.5)) clamped to the RASTER,
+ * weight L((j + 0.5 - c) sw) / sum; rows first, then columns, f32 accumulation, NaN propagates). Equal sizes copy the window under both.
+ * Limits: win / out <= 64 on either axis (385 taps), else APDS_ERR_BAD_ARG; a window outside the raster is APDS_ERR_OUT_OF_RANGE; an empty
+ * window or output APDS_ERR_ASSERT; an unknown `resample` APDS_ERR_BAD_ARG. */
+#define APDS_RESAMPLE_NEAREST 0
+#define APDS_RESAMPLE_LANCZOS 1
+/* Copies three rows x cols f32 bands (row_stride elements between rows; on_device 1: device pointers) into one device allocation
+ * [3][rows][cols] on the calling thread's device. The handle is immutable afterwards and may be shared between threads. */
+int apds_mosaic_create(void** mosaic, const void* red, const void* green, const void* blue, int rows, int cols, size_t row_stride, int on_device);
+int apds_mosaic_destroy(void* mosaic);
+int apds_mosaic_info(const void* mosaic, int* rows, int* cols);
+/* mod.rs:200-229 datasets_min_max: {red_min, red_max, green_min, ...}, NaN ignored (a band of NaN only gives NaN): a device reduction,
+ * computed by the first call and cached in the handle. */
+int apds_mosaic_min_max(void* mosaic, double* minmax6);
+/* The tables of one axis, host arithmetic only (no device needed): a window of `span` source pixels at `offset` of a raster of n_src, resampled
+ * to n_out. Output i reads source pixels [start[i], start[i] + count[i]) with weights[i * max_taps ..] (computed in double, rounded once
+ * to f32, zero past count). NEAREST: count 1, weight 1. max_taps below the widest footprint: APDS_ERR_BAD_ARG. */
+int apds_resample_weights(int n_src, double offset, double span, int n_out, int resample, int max_taps, int32_t* start, int32_t* count, float* weights);
+/* The resampled window itself: out3 = host [3][out_h][out_w] f32 (what to_rgb hands band_merger). */
+int apds_mosaic_window(void* mosaic, int x0, int y0, int win_w, int win_h, int out_w, int out_h, int resample, float* out3);
+/* apds_tile_extract / apds_tile_extract_batch on windows of the mosaic: window -> band_merger (BGRA) -> AKAZE entirely on the device.
+ * minmax6 NULL = the mosaic's own (apds_mosaic_min_max). The batch form takes n_tiles (1 .. 4096) origins xy0 = {x0, y0, x1, y1, ...} of
+ * ONE window and output shape: one resampling launch per pass covers all tiles and bands. Results are exactly those of apds_tile_extract
+ * on the window apds_mosaic_window returns. Outputs as apds_akaze_extract / apds_akaze_extract_batch. */
+int apds_mosaic_tile_extract(void* mosaic, int x0, int y0, int win_w, int win_h, int out_w, int out_h, int resample, const double* minmax6, int max_points,
+                             apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes);
+int apds_mosaic_tile_extract_batch(void* mosaic, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample, const double* minmax6,
+                                   int max_points, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes);
+
 /* homographier/src/homographier/mod.rs:271-300 warp_image_perspective: warpPerspective(src, M, size, INTER_LINEAR, BORDER_CONSTANT,
  * Scalar(1,1,1,1)). M (9 doubles) maps source to destination coordinates. The reference function is generic over the element type
  * (warp_image_perspective<T: DataType>): u8 elements with 1, 3 or 4 interleaved channels here (u8, Vec3b, Vec4b - the type the reference's

@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""Builds the level-of-detail 0..2 database of one synthetic mosaic three ways, alternating in one process:
+
+    (a) host MosaicedDataset, nearest   - the path before the device mosaic: numpy windows, three band uploads per tile
+    (b) DeviceMosaic, nearest           - apds_mosaic_tile_extract_batch, the same rows bit for bit
+    (c) DeviceMosaic, Lanczos           - the reference's read_as(.., Lanczos)
+
+with `--tile`-pixel tiles (the mosaic is cut as a 4-level pyramid, so --size 8192 gives 1024 x 1024 tiles: 64 + 16 + 4) and batch = all
+tiles of a level. Prints, per level and way: seconds (host clock around calls that end in a device synchronise), the resampling kernels'
+own time (hipEvents, apds_dev_last_kernel_ms "mosaic_resample"), the algorithmic bytes of the level (12 H W read + 12 H W / 4^lod
+written) over that time, and the keypoint count; last line: one JSON object with everything.
+
+    python tools/mosaic_probe.py --size 8192 --reps 2
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as graft  # noqa: E402
+
+
+def synthetic_mosaic(pkg, size):
+    base = pkg.synth.make_tile(2048, 2048, frame_index=11, channels=3).astype(np.float32)
+    reps = (size + 2047) // 2048
+    bands = np.empty((3, size, size), np.float32)
+    yy, xx = np.meshgrid(np.linspace(0.8, 1.2, size, dtype=np.float32), np.linspace(0.9, 1.1, size, dtype=np.float32), indexing="ij")
+    for b, (ch, gain, off) in enumerate(((2, 3.0, 10.0), (1, 2.0, -5.0), (0, 1.5, 0.0))):
+        bands[b] = np.tile(base[:, :, ch], (reps, reps))[:size, :size] * gain * yy * xx + off
+    bands[0, 5:9, 7:12] = np.nan
+    return bands
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=8192)
+    ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--levels", type=int, default=3)
+    args = ap.parse_args()
+    import torch  # noqa: F401  (its HIP runtime first, as bench.py does)
+    pkg = graft.load_package()
+    L = pkg.lib()
+    assert L.apds_device_count() > 0, "no HIP device: this probe measures on the GPU"
+    ge, pp, fd = pkg.geotiff_extractor, pkg.preprocessor, pkg.feature_database
+    t0 = time.perf_counter()
+    bands = synthetic_mosaic(pkg, args.size)
+    host = ge.MosaicedDataset(bands)
+    t1 = time.perf_counter()
+    dev = host.to_device()
+    t2 = time.perf_counter()
+    mm_host = host.datasets_min_max().as_array()
+    t3 = time.perf_counter()
+    L.apds_dev_timing_enable(1)
+    mm_dev = dev.datasets_min_max().as_array()
+    t4 = time.perf_counter()
+    minmax_ms, _ = pkg._lib.kernel_ms("mosaic_minmax")
+    assert np.array_equal(mm_host, mm_dev), (mm_host, mm_dev)
+    n_bytes = 12.0 * args.size * args.size
+    print(f"mosaic {args.size} x {args.size} x 3 f32 ({n_bytes / 1e9:.2f} GB): synthesis {t1 - t0:.2f} s, upload {t2 - t1:.3f} s")
+    print(f"min/max: host nanmin/nanmax {t3 - t2:.3f} s | device call {t4 - t3:.4f} s, kernels {minmax_ms:.3f} ms = {n_bytes / minmax_ms / 1e6:.0f} GB/s of the {n_bytes / 1e9:.2f} GB read")
+    amount = 4                                                                # tile = size / 8
+    tile, _, _ = pp.tile_grid(host.raster_size(), amount, 0)
+    ways = (("a host nearest", host, "nearest"), ("b device nearest", dev, "nearest"), ("c device lanczos", dev, "lanczos"))
+    results = {w[0]: {lod: [] for lod in range(args.levels)} for w in ways}
+    for rep in range(args.reps + 1):                                          # rep 0 warms every shape up and is not reported
+        for name, ds, mode in ways:
+            table, images = fd.KeypointTable(6_000_000), pp.ImageTable()
+            for lod in range(args.levels):
+                _, columns, rows = pp.tile_grid(ds.raster_size(), amount, lod)
+                pkg._lib.kernel_ms("mosaic_resample")                         # drop what is pending
+                s = time.perf_counter()
+                out = pp.downscale_from_lod(table, images, ds, amount, lod, batch=columns * rows, resample=mode)
+                e = time.perf_counter()
+                ms, launches = pkg._lib.kernel_ms("mosaic_resample")
+                if rep:
+                    results[name][lod].append(dict(seconds=e - s, resample_ms=ms, resample_calls=launches, tiles=len(out), keypoints=sum(n for _, n in out)))
+            table.close()
+    print(f"tiles of {tile[0]} x {tile[1]}, batch = all tiles of a level, {args.reps} timed repetitions after one warm-up (median shown)")
+    for lod in range(args.levels):
+        algo = n_bytes * (1.0 + 0.25 ** lod)
+        for name, _, _ in ways:
+            r = results[name][lod]
+            sec = float(np.median([x["seconds"] for x in r]))
+            ms = float(np.median([x["resample_ms"] for x in r]))
+            rate = f"{algo / ms / 1e6:8.0f} GB/s of {algo / 1e9:.2f} GB" if ms > 0 else "       - (no resampling kernel)"
+            print(f"lod {lod} {name:18s}: {r[0]['tiles']:3d} tiles {sec:8.3f} s  [{' '.join('%.3f' % x['seconds'] for x in r)}]  resample {ms:8.3f} ms {rate}  keypoints {r[0]['keypoints']}")
+    print(json.dumps(dict(size=args.size, tile=tile[0], reps=args.reps, minmax_ms=minmax_ms, host_minmax_s=t3 - t2, upload_s=t2 - t1,
+                          results={k: {str(l): v for l, v in d.items()} for k, d in results.items()})))
+    dev.close()
+
+
+if __name__ == "__main__":
+    main()
