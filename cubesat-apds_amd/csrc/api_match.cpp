@@ -5,6 +5,7 @@
 
 #include "config.h"
 #include "kernels.h"
+#include "topk_keys.h"
 
 using namespace apds;
 
@@ -59,7 +60,7 @@ int apds_knn_match(const uint8_t* q, int nq, const uint8_t* t, int nt, int desc_
         HIP_CHECK(hipMemcpyAsync(h.data(), keys, h.size() * 8, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         for (size_t i = 0; i < h.size(); i++) {
-            if (h[i] == ~0ull) idx[i] = -1, dist[i] = INT_MAX;
+            if (h[i] == EMPTY_KEY) idx[i] = -1, dist[i] = INT_MAX;
             else idx[i] = (int32_t)(uint32_t)h[i], dist[i] = (int32_t)(h[i] >> 32);
         }
     });

@@ -2,7 +2,7 @@
 // The defaults are the measured best; every switch keeps results bit-identical (the parity tests run the forced variants:
 // tests/test_strip_kernels_gpu.py). Round 3 folded 38 scattered getenv sites into this table (19 switches) and deleted the variants that had lost every
 // measurement: the persistent-grid match kernel, the staged keypoint pipeline, the 32- and 128-pixel Hessian tiles, and the tuning knobs
-// of the match's work-item plan (now constants in match_hamming.hip).
+// of the match's work-item plan (now constants in match_hamming.hip: plan_chunks).
 #pragma once
 
 namespace apds {

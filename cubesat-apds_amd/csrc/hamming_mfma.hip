@@ -32,6 +32,7 @@
 
 #include "config.h"
 #include "kernels.h"
+#include "topk_keys.h"
 
 namespace apds {
 
@@ -58,7 +59,6 @@ static constexpr int HM_NC = APDS_HM_NC;      // 16-query column blocks per wave
                                               // headline shape, 11.0 against 11.9 on 262143^2: profiles/r04/match_mfma_probe.txt)
 static constexpr int HM_Q = HM_WAVES * 16 * HM_NC;   // queries per block
 static constexpr int HM_UNIT_SCALE = 0x7F7F7F7F;   // E8M0 127 = 2^0 in every byte
-static constexpr uint64_t HM_EMPTY = ~0ull;
 // Train popcounts are stored with this bias: the ranking value popcount(t) + 1024 - 2 (t AND q) is then a POSITIVE float (>= 512), and
 // positive floats order like their bit patterns - the epilogue compares them as unsigned integers (v_min3_u32 / v_min_u32 / v_cmp_lt_u32:
 // no NaN canonicalisation in front of every float minimum, six v_max_f32 less per 16 x 48 block of pairs). +inf (rows past the end) is
@@ -103,7 +103,7 @@ __global__ void hm_thresholds_kernel(const uint64_t* __restrict__ topk, int K, c
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nq) return;
     const uint64_t k2 = topk[(size_t)i * K + K - 1];
-    thr[i] = k2 == HM_EMPTY ? 0x7F800000u : __float_as_uint((float)((int)(uint32_t)(k2 >> 32) - (int)qpc[i] + HM_BIAS));
+    thr[i] = k2 == EMPTY_KEY ? 0x7F800000u : __float_as_uint((float)((int)key_rank(k2) - (int)qpc[i] + HM_BIAS));
 }
 
 struct HmTop2 {
@@ -265,6 +265,56 @@ __device__ __forceinline__ void hm_scan_tiles(const uint4* __restrict__ train_fp
     }
 }
 
+// ---- what the two kernels spell alike around the tile loop ----
+// A workgroup's split of the train tiles and its query tile; a wave's first query. Workgroup b runs on XCD b % 8 (round-robin dispatch) and
+// every XCD has an L2 of its own. With a multiple of eight splits, split x + 8 m belongs to XCD x: the workgroups resident on an XCD at any
+// time are consecutive query tiles of one split, start together and walk the same train tiles at about the same pace - one fetches a tile,
+// the others find it in their L2.
+struct HmItem {
+    int split, q0, tile_begin, tile_end;
+    int col, kq;   // accumulator column / k chunk (operands) / row group (accumulators)
+};
+template <int NC>
+__device__ __forceinline__ HmItem hm_work_item(int n_train, int tiles_per_split, int q_tiles, int splits) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    HmItem w;
+    int qtile;
+    if ((splits & 7) == 0) {
+        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+        w.split = xcd + 8 * (j / q_tiles);
+        qtile = j % q_tiles;
+    } else {
+        w.split = blockIdx.x / q_tiles;
+        qtile = blockIdx.x % q_tiles;
+    }
+    w.q0 = qtile * (HM_WAVES * 16 * NC) + wave * 16 * NC;   // this wave's queries
+    const int n_tiles = (n_train + HM_TM - 1) / HM_TM;
+    w.tile_begin = w.split * tiles_per_split, w.tile_end = min(n_tiles, w.tile_begin + tiles_per_split);
+    w.col = lane & 15, w.kq = lane >> 4;
+    return w;
+}
+// B operands: query (q0 + 16 c + col), elements 128 s + 32 kq .. + 31 (dword 4 s + kq of the row), for the four k steps s; qq: its popcount
+template <int NC>
+__device__ __forceinline__ void hm_load_queries(const uint4* query_fp4, const float* qpc, int nq, int q0, int col, int kq, uint4 (&B)[NC][4], float (&qq)[NC]) {
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        const int qi = min(q0 + 16 * c + col, nq - 1);
+#pragma unroll
+        for (int s = 0; s < 4; s++) B[c][s] = query_fp4[(size_t)qi * 16 + 4 * s + kq];
+        qq[c] = qpc[qi];
+    }
+}
+// What every entry of the list of query qi starts as, without a row: thr[qi] when the caller has one - the K-th smallest ranking value over a
+// sample of EARLIER rows (lower indices, so a row of this launch enters the query's final list only with a strictly smaller value) - or +inf.
+// Real rows push the copies out; what is left of them at the end is written as empty.
+template <bool THR>
+__device__ __forceinline__ uint32_t hm_start_value(const uint32_t* thr, int qi) {
+    return THR ? thr[qi] : 0x7F800000u;
+}
+// Ranking value d (float bits) of a row against a query with popcount qq -> their Hamming distance, the rank of the final key. (The whole
+// key - empty for an entry without a row - as one function changed the kernels' register allocation; this much of it does not.)
+__device__ __forceinline__ uint32_t hm_distance(float qq, uint32_t d) { return (uint32_t)((int)(qq + __uint_as_float(d)) - HM_BIAS); }
+
 // out[split][nq][2]: keys (distance << 32 | row + index_base), EMPTY where the split holds fewer than two rows.
 // LDS image of a tile (no padding: the tile is filled by LDS-DMA, whose destination is wave-uniform base + 16 * lane): row r at 256 r, and
 // its 16-byte chunk c at position c ^ (r & 15) - the 16 rows a ds_read_b128 group reads chunk c of then sit in 16 different bank groups.
@@ -278,41 +328,16 @@ __global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(A
                                                            int q_tiles, int splits, uint32_t index_base, const uint32_t* __restrict__ thr,
                                                            uint64_t* __restrict__ out) {
     // (no APDS_RAISE_WAVE_PRIORITY here: this is the kernel the short kernels of the other stages raise their priority against)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // Workgroup b runs on XCD b % 8 (round-robin dispatch) and every XCD has an L2 of its own. With a multiple of eight splits, split
-    // x + 8 m belongs to XCD x: the workgroups resident on an XCD at any time are consecutive query tiles of one split, start together and
-    // walk the same train tiles at about the same pace - one fetches a tile, the others find it in their L2.
-    int split, qtile;
-    if ((splits & 7) == 0) {
-        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        split = xcd + 8 * (j / q_tiles);
-        qtile = j % q_tiles;
-    } else {
-        split = blockIdx.x / q_tiles;
-        qtile = blockIdx.x % q_tiles;
-    }
-    const int q0 = qtile * HM_Q + wave * 16 * HM_NC;              // this wave's queries
-    const int n_tiles = (n_train + HM_TM - 1) / HM_TM;
-    const int tile_begin = split * tiles_per_split, tile_end = min(n_tiles, tile_begin + tiles_per_split);
-    const int col = lane & 15, kq = lane >> 4;                     // accumulator column / k chunk (operands) / row group (accumulators)
-
-    // B operands: query (q0 + 16 c + col), elements 128 s + 32 kq .. + 31 (dword 4 s + kq of the row), for the four k steps s
+    const HmItem w = hm_work_item<HM_NC>(n_train, tiles_per_split, q_tiles, splits);
+    // (locals, and by value into the helpers: with the struct handed on by reference the kernels' register allocation changed)
+    const int split = w.split, q0 = w.q0, tile_begin = w.tile_begin, tile_end = w.tile_end, col = w.col, kq = w.kq;
     uint4 B[HM_NC][4];
     float qq[HM_NC];
+    hm_load_queries<HM_NC>(query_fp4, qpc, nq, q0, col, kq, B, qq);
+    HmTop2 best[HM_NC];   // both entries start as hm_start_value
 #pragma unroll
     for (int c = 0; c < HM_NC; c++) {
-        const int qi = min(q0 + 16 * c + col, nq - 1);
-#pragma unroll
-        for (int s = 0; s < 4; s++) B[c][s] = query_fp4[(size_t)qi * 16 + 4 * s + kq];
-        qq[c] = qpc[qi];
-    }
-    // The running top-2 starts from thr[query] when the caller has one (the second smallest ranking value over a sample of EARLIER rows - lower
-    // indices, so a row of this launch enters the query's final top-2 only with a strictly smaller value): both entries are that value
-    // without a row, real rows push them out, and what is left of them at the end is written as empty. Without it: +inf.
-    HmTop2 best[HM_NC];
-#pragma unroll
-    for (int c = 0; c < HM_NC; c++) {
-        best[c].d0 = THR ? thr[min(q0 + 16 * c + col, nq - 1)] : 0x7F800000u;
+        best[c].d0 = hm_start_value<THR>(thr, min(q0 + 16 * c + col, nq - 1));
         hm_settle(best[c].d0), hm_settle(qq[c]);
         best[c].d1 = best[c].d0;
         best[c].i0 = best[c].i1 = 0xFFFFFFFFu;
@@ -370,16 +395,16 @@ __global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(A
         const int qi = q0 + 16 * c + col;
         if (kq == 0 && qi < nq) {
             uint64_t* o = out + ((size_t)split * nq + qi) * 2;
-            o[0] = b.i0 == 0xFFFFFFFFu ? HM_EMPTY : ((uint64_t)(uint32_t)((int)(qq[c] + __uint_as_float(b.d0)) - HM_BIAS) << 32) | b.i0;
-            o[1] = b.i1 == 0xFFFFFFFFu ? HM_EMPTY : ((uint64_t)(uint32_t)((int)(qq[c] + __uint_as_float(b.d1)) - HM_BIAS) << 32) | b.i1;
+            o[0] = b.i0 == 0xFFFFFFFFu ? EMPTY_KEY : make_key(hm_distance(qq[c], b.d0), b.i0);
+            o[1] = b.i1 == 0xFFFFFFFFu ? EMPTY_KEY : make_key(hm_distance(qq[c], b.d1), b.i1);
         }
     }
 }
 
 // ---- 3 <= k <= 8: the same kernel around a sorted K-entry list per query column and lane (K = 4 serves k = 3, 4; K = 8 serves k = 5 .. 8) ----
 // A kernel of its own rather than a K parameter of hamming_mfma_kernel: the top-2 kernel's registers and instruction stream stay what they
-// are. Everything in front of the ranking is the text above (operands, LDS image, LDS-DMA staging, preset accumulator, four scaled MFMAs
-// per 16 x 16 block); what follows the list length is here: the column blocks per wave (the list registers come out of the B operands'),
+// are. Everything in front of the ranking is shared with it (hm_work_item, hm_load_queries, hm_start_value, hm_scan_tiles: operands, LDS
+// image, LDS-DMA staging, preset accumulator, four scaled MFMAs per 16 x 16 block), and so is hm_distance behind it; what follows the list length is here: the column blocks per wave (the list registers come out of the B operands'),
 // the insertion, the cross-lane fold and the K-th threshold.
 template <int K>
 struct HmTopK {
@@ -424,37 +449,16 @@ template <int K, int NC, int PRIO, bool THR>
 __global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(APDS_HM_WPE, APDS_HM_WPE))) void hamming_mfma_topk_kernel(
     const uint4* __restrict__ train_fp4, const float* __restrict__ tpc, int n_train, const uint4* __restrict__ query_fp4, const float* __restrict__ qpc, int nq,
     int tiles_per_split, int q_tiles, int splits, uint32_t index_base, const uint32_t* __restrict__ thr, uint64_t* __restrict__ out) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int split, qtile;   // (splits pinned to the XCDs: see hamming_mfma_kernel)
-    if ((splits & 7) == 0) {
-        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        split = xcd + 8 * (j / q_tiles);
-        qtile = j % q_tiles;
-    } else {
-        split = blockIdx.x / q_tiles;
-        qtile = blockIdx.x % q_tiles;
-    }
-    const int q0 = qtile * (HM_WAVES * 16 * NC) + wave * 16 * NC;   // this wave's queries
-    const int n_tiles = (n_train + HM_TM - 1) / HM_TM;
-    const int tile_begin = split * tiles_per_split, tile_end = min(n_tiles, tile_begin + tiles_per_split);
-    const int col = lane & 15, kq = lane >> 4;
-
+    const HmItem w = hm_work_item<NC>(n_train, tiles_per_split, q_tiles, splits);
+    const int split = w.split, q0 = w.q0, tile_begin = w.tile_begin, tile_end = w.tile_end, col = w.col, kq = w.kq;
     uint4 B[NC][4];
     float qq[NC];
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        const int qi = min(q0 + 16 * c + col, nq - 1);
-#pragma unroll
-        for (int s = 0; s < 4; s++) B[c][s] = query_fp4[(size_t)qi * 16 + 4 * s + kq];
-        qq[c] = qpc[qi];
-    }
-    // The list starts as K copies of thr[query] (the K-th smallest ranking value over a sample of EARLIER rows: a row of this launch enters
-    // the query's final top-K only with a strictly smaller value) or of +inf, without a row. Real rows push them out from the front; what is
-    // left of them is written as empty. A padding row's value is +inf and never passes the strict test, whatever the list holds.
+    hm_load_queries<NC>(query_fp4, qpc, nq, q0, col, kq, B, qq);
+    // The list starts as K copies of hm_start_value. A padding row's value is +inf and never passes the strict test, whatever the list holds.
     HmTopK<K> best[NC];
 #pragma unroll
     for (int c = 0; c < NC; c++) {
-        uint32_t start = THR ? thr[min(q0 + 16 * c + col, nq - 1)] : 0x7F800000u;
+        uint32_t start = hm_start_value<THR>(thr, min(q0 + 16 * c + col, nq - 1));
         hm_settle(start), hm_settle(qq[c]);
 #pragma unroll
         for (int j = 0; j < K; j++) best[c].d[j] = start, best[c].i[j] = 0xFFFFFFFFu;
@@ -512,8 +516,8 @@ __global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(A
             uint64_t* o = out + ((size_t)split * nq + qi) * K;
 #pragma unroll
             for (int j = 0; j < K; j++) {
-                const uint32_t d = (uint32_t)(key[j] >> 32), i = (uint32_t)key[j];
-                o[j] = i == 0xFFFFFFFFu ? HM_EMPTY : ((uint64_t)(uint32_t)((int)(qq[c] + __uint_as_float(d)) - HM_BIAS) << 32) | i;
+                const uint32_t d = key_rank(key[j]), i = key_index(key[j]);
+                o[j] = i == 0xFFFFFFFFu ? EMPTY_KEY : make_key(hm_distance(qq[c], d), i);
             }
         }
     }
@@ -579,24 +583,23 @@ long long hm_sample_rows(long long nt) {
     return (cap > 0 && nt >= 65536) ? std::min<long long>(cap, nt / 16 / HM_TM * HM_TM) / HM_TM * HM_TM : 0;   // whole tiles (HM_TM need not be a power of two)
 }
 
-// The K = 4 / K = 8 launch of hm_scan_device. PRIO: the wave priority around a block's MFMAs is off or 2 here (levels 1, 2, 3 measured alike on
-// the top-2 kernel: one compiled level instead of three).
-template <int K>
-static void hm_scan_k_launch(const void* q_fp4, const float* qpc, int nq, const void* t_fp4, const float* tpc, long long nt, const HmPlan& p, uint32_t index_base,
-                             uint64_t* parts, hipStream_t s, const uint32_t* thr, size_t lds) {
+// The kernels ask for more dynamic LDS than the default limit: opt a set of them in once per device (idempotent, so a race is harmless).
+template <class... Kernel>
+static void hm_opt_in_lds(std::atomic<bool> (&opted_dev)[64], Kernel... kernel) {
+    std::atomic<bool>& opted = opted_dev[ctx().device & 63];
+    if (opted.load()) return;
+    (HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)), ...);
+    opted.store(true);
+}
+
+// The K = 4 / K = 8 launch of hm_scan_device (go: its launch of a kernel). PRIO: the wave priority around a block's MFMAs is off or 2 here
+// (levels 1, 2, 3 measured alike on the top-2 kernel: one compiled level instead of three).
+template <int K, class Go>
+static void hm_scan_k_launch(Go&& go, bool thr) {
     constexpr int NC = HmShape<K>::NC;
     static std::atomic<bool> opted_dev[64];
-    std::atomic<bool>& opted = opted_dev[ctx().device & 63];
-    if (!opted.load()) {
-        auto opt = [&](auto kernel) { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); };
-        opt(&hamming_mfma_topk_kernel<K, NC, 0, false>), opt(&hamming_mfma_topk_kernel<K, NC, 2, false>);
-        opt(&hamming_mfma_topk_kernel<K, NC, 0, true>), opt(&hamming_mfma_topk_kernel<K, NC, 2, true>);
-        opted.store(true);
-    }
-    auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)p.q_tiles * p.splits), dim3(64 * HM_WAVES), lds, s, static_cast<const uint4*>(t_fp4), tpc, (int)nt,
-                           static_cast<const uint4*>(q_fp4), qpc, nq, p.tiles_per_split, p.q_tiles, p.splits, index_base, thr, parts);
-    };
+    hm_opt_in_lds(opted_dev, &hamming_mfma_topk_kernel<K, NC, 0, false>, &hamming_mfma_topk_kernel<K, NC, 2, false>,
+                  &hamming_mfma_topk_kernel<K, NC, 0, true>, &hamming_mfma_topk_kernel<K, NC, 2, true>);
     const bool prio = config().match_mfma_prio > 0;
     if (thr) prio ? go(&hamming_mfma_topk_kernel<K, NC, 2, true>) : go(&hamming_mfma_topk_kernel<K, NC, 0, true>);
     else prio ? go(&hamming_mfma_topk_kernel<K, NC, 2, false>) : go(&hamming_mfma_topk_kernel<K, NC, 0, false>);
@@ -605,31 +608,23 @@ static void hm_scan_k_launch(const void* q_fp4, const float* qpc, int nq, const 
 // parts: [p.splits][nq][K] keys; p = hm_plan(nq, nt, K). K = 2: hamming_mfma_kernel; K = 4, 8: hamming_mfma_topk_kernel.
 void hm_scan_device(const void* q_fp4, const float* qpc, int nq, const void* t_fp4, const float* tpc, long long nt, const HmPlan& p, uint32_t index_base,
                     uint64_t* parts, hipStream_t s, const uint32_t* thr, bool timed, int K) {
+    APDS_REQUIRE(K <= 2 || K == 4 || K == 8, APDS_ERR_ASSERT, "the matrix-core matcher keeps lists of 2, 4 or 8");
     // (APDS_MATCH_MFMA_LDS_PAD: unused dynamic LDS on top, an experiment knob - e.g. 30000 leaves one workgroup per CU)
     const size_t lds = (size_t)2 * HM_TM * 256 + 2 * HM_TM * sizeof(float) + (size_t)std::max(0, config().match_mfma_lds_pad);
-    if (K > 2) {
-        APDS_REQUIRE(K == 4 || K == 8, APDS_ERR_ASSERT, "the matrix-core matcher keeps lists of 2, 4 or 8");
-        // two names for one launch: "hamming_topk" is what every main match launch is counted under, the second tells which kernel it was
-        std::unique_ptr<KernelTimer> timer, timer_k;
-        if (timed) timer.reset(new KernelTimer("hamming_topk", s)), timer_k.reset(new KernelTimer("hamming_topk_mfma_k", s));
-        if (K == 4) hm_scan_k_launch<4>(q_fp4, qpc, nq, t_fp4, tpc, nt, p, index_base, parts, s, thr, lds);
-        else hm_scan_k_launch<8>(q_fp4, qpc, nq, t_fp4, tpc, nt, p, index_base, parts, s, thr, lds);
-        return;
-    }
-    static std::atomic<bool> opted_dev[64];   // above the default dynamic-LDS limit: opt in once per device (idempotent, so a race is harmless)
-    std::atomic<bool>& opted = opted_dev[ctx().device & 63];
-    if (!opted.load()) {
-        auto opt = [&](auto kernel) { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); };
-        opt(&hamming_mfma_kernel<0, false>), opt(&hamming_mfma_kernel<1, false>), opt(&hamming_mfma_kernel<2, false>), opt(&hamming_mfma_kernel<3, false>);
-        opt(&hamming_mfma_kernel<0, true>), opt(&hamming_mfma_kernel<1, true>), opt(&hamming_mfma_kernel<2, true>), opt(&hamming_mfma_kernel<3, true>);
-        opted.store(true);
-    }
-    std::unique_ptr<KernelTimer> timer;   // ("hamming_topk": the name the pipeline's counters and bench.py know the main match launch by)
-    if (timed) timer.reset(new KernelTimer("hamming_topk", s));
     auto go = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3((unsigned)p.q_tiles * p.splits), dim3(64 * HM_WAVES), lds, s, static_cast<const uint4*>(t_fp4), tpc, (int)nt,
                            static_cast<const uint4*>(q_fp4), qpc, nq, p.tiles_per_split, p.q_tiles, p.splits, index_base, thr, parts);
     };
+    // "hamming_topk": the name the pipeline's counters and bench.py know every main match launch by; for K > 2 a second name tells which
+    // kernel it was
+    std::unique_ptr<KernelTimer> timer, timer_k;
+    if (timed) timer.reset(new KernelTimer("hamming_topk", s));
+    if (timed && K > 2) timer_k.reset(new KernelTimer("hamming_topk_mfma_k", s));
+    if (K == 4) return hm_scan_k_launch<4>(go, thr != nullptr);
+    if (K == 8) return hm_scan_k_launch<8>(go, thr != nullptr);
+    static std::atomic<bool> opted_dev[64];
+    hm_opt_in_lds(opted_dev, &hamming_mfma_kernel<0, false>, &hamming_mfma_kernel<1, false>, &hamming_mfma_kernel<2, false>, &hamming_mfma_kernel<3, false>,
+                  &hamming_mfma_kernel<0, true>, &hamming_mfma_kernel<1, true>, &hamming_mfma_kernel<2, true>, &hamming_mfma_kernel<3, true>);
     const int prio = std::max(0, std::min(3, config().match_mfma_prio));
     if (thr) {
         switch (prio) {
@@ -694,28 +689,25 @@ static void hm_topk_expanded(const void* q, int nq, const void* t4, const float*
     const long long sample = hm_sample_rows(nt);
     const int K = hm_list_len(k);   // the list the kernel keeps: 2, 4 or 8; the columns past k are dropped at the end
     uint64_t* topk = k == K ? out : c.alloc_n<uint64_t>((size_t)nq * K);
+    // the lists the main launch's merge takes: one per split of the rest, and the sample's top-K behind them
+    const HmPlan p = hm_plan(nq, nt - sample, K);
+    const int lists = p.splits + (sample ? 1 : 0);
+    uint64_t* parts = lists == 1 ? topk : c.alloc_n<uint64_t>((size_t)lists * nq * K);
+    uint32_t* thr = nullptr;
     if (sample) {
-        const HmPlan pa = hm_plan(nq, sample, K), pb = hm_plan(nq, nt - sample, K);
+        const HmPlan pa = hm_plan(nq, sample, K);
         uint64_t* parts_a = c.alloc_n<uint64_t>((size_t)pa.splits * nq * K);
-        uint64_t* parts_b = c.alloc_n<uint64_t>((size_t)(pb.splits + 1) * nq * K);   // + one list: the sample's top-K
-        uint64_t* topk_a = parts_b + (size_t)pb.splits * nq * K;
-        uint32_t* thr = c.alloc_n<uint32_t>(nq);
-        {
-            KernelTimer timer("hamming_topk_sample", s);
-            hm_scan_device(q4, qp, nq, t4, tp, sample, pa, index_base, parts_a, s, nullptr, /*timed=*/false, K);
-            if (pa.splits > 1) merge_topk_device(parts_a, pa.splits, nq, K, topk_a, s);
-            else HIP_CHECK(hipMemcpyAsync(topk_a, parts_a, (size_t)nq * K * 8, hipMemcpyDeviceToDevice, s));
-            hipLaunchKernelGGL(hm_thresholds_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, s, (const uint64_t*)topk_a, K, (const float*)qp, nq, thr);
-        }
-        hm_scan_device(q4, qp, nq, static_cast<const char*>(t4) + (size_t)sample * 256, tp + sample, nt - sample, pb, index_base + (uint32_t)sample, parts_b, s, thr,
-                       /*timed=*/true, K);
-        merge_topk_device(parts_b, pb.splits + 1, nq, K, topk, s);
-    } else {
-        const HmPlan p = hm_plan(nq, nt, K);
-        uint64_t* parts = p.splits == 1 ? topk : c.alloc_n<uint64_t>((size_t)p.splits * nq * K);
-        hm_scan_device(q4, qp, nq, t4, tp, nt, p, index_base, parts, s, nullptr, /*timed=*/true, K);
-        if (p.splits > 1) merge_topk_device(parts, p.splits, nq, K, topk, s);
+        uint64_t* topk_a = parts + (size_t)p.splits * nq * K;
+        thr = c.alloc_n<uint32_t>(nq);
+        KernelTimer timer("hamming_topk_sample", s);
+        hm_scan_device(q4, qp, nq, t4, tp, sample, pa, index_base, parts_a, s, nullptr, /*timed=*/false, K);
+        if (pa.splits > 1) merge_topk_device(parts_a, pa.splits, nq, K, topk_a, s);
+        else HIP_CHECK(hipMemcpyAsync(topk_a, parts_a, (size_t)nq * K * 8, hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(hm_thresholds_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, s, (const uint64_t*)topk_a, K, (const float*)qp, nq, thr);
     }
+    hm_scan_device(q4, qp, nq, static_cast<const char*>(t4) + (size_t)sample * 256, tp + sample, nt - sample, p, index_base + (uint32_t)sample, parts, s, thr,
+                   /*timed=*/true, K);
+    if (lists > 1) merge_topk_device(parts, lists, nq, K, topk, s);
     if (k != K) take_first_columns_device(topk, nq, K, k, out, s);
     HIP_CHECK(hipGetLastError());
 }

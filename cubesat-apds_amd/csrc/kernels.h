@@ -5,12 +5,26 @@
 
 namespace apds {
 
-// match_hamming.hip
+// match_hamming.hip: Hamming top-k keys (topk_keys.h) on the vector ALU, and the front of both Hamming backends
 // backend: 0 = the configured one (APDS_MATCH_MFMA, APDS_MATCH_MFMA_KMAX), 1 = vector ALU (hamming_topk_kernel), 2 = matrix cores (hamming_mfma_kernel, k <= 2),
 // 3 = matrix cores (k <= 2 as backend 2; 3 <= k <= 8: hamming_mfma_topk_kernel)
 void hamming_topk_device(const void* q, int nq, const void* t, long long nt, uint32_t index_base, int k, uint64_t* out, hipStream_t s, int backend = 0);
+// the scan of hamming_topk_device in three separately launched steps on a per-frame state object (k = 1, 2)
+void* topk_split_create();
+void topk_split_destroy(void* state);
+void topk_split_prepass(void* state, const void* q, int nq, const void* t, long long nt, uint32_t index_base, int k, hipStream_t s);
+void topk_split_scan(void* state, const void* q, const void* t, hipStream_t s);
+void topk_split_merge(void* state, uint32_t index_base, uint64_t* out, hipStream_t s);
+void topk_split_use_train(void* state, const void* hm_train);   // a pre-expanded train set for the state's matrix-core scans (or null)
+void pack_rows_device(const void* src, long long n, int desc_bytes, long long src_stride, void* dst, hipStream_t s);
+std::atomic<int>& match_lds_cap();   // occupancy cap of the main Hamming scan
+std::atomic<int>& last_scan_launch_lds();
+void set_thread_scan_cap(int bytes);   // occupancy cap of the scans THIS thread launches (-1: the process-wide one)
+
+// topk_merge.hip: [parts][nq][k] sorted key lists -> the k smallest per query; the first kout of kin columns
 void merge_topk_device(const uint64_t* parts, int nparts, int nq, int k, uint64_t* out, hipStream_t s);
 void take_first_columns_device(const uint64_t* in, int nq, int kin, int kout, uint64_t* out, hipStream_t s);
+
 // hamming_mfma.hip: the same keys for 1 <= k <= 8 from the FP4 matrix pipe (bit -> e2m1 operand, exact). The kernels keep a sorted list of
 // K = 2, 4 or 8 entries per query (the smallest that holds k); hm_plan / hm_scan_device take that K (default: the top-2 kernel)
 void hamming_mfma_topk_device(const void* q, int nq, const void* t, long long nt, uint32_t index_base, int k, uint64_t* out, hipStream_t s);
@@ -33,41 +47,35 @@ long long hm_sample_rows(long long nt);
 void* hm_train_create(const void* rows64, long long n, hipStream_t s);
 void hm_train_destroy(void* train);
 void hamming_mfma_topk_train_device(const void* q, int nq, const void* train, uint32_t index_base, int k, uint64_t* out, hipStream_t s);
-void topk_split_use_train(void* state, const void* hm_train);   // a pre-expanded train set for the state's matrix-core scans (or null)
-// the scan of hamming_topk_device in three separately launched steps on a per-frame state object (k = 1, 2)
-void* topk_split_create();
-void topk_split_destroy(void* state);
-void topk_split_prepass(void* state, const void* q, int nq, const void* t, long long nt, uint32_t index_base, int k, hipStream_t s);
-void topk_split_scan(void* state, const void* q, const void* t, hipStream_t s);
-void topk_split_merge(void* state, uint32_t index_base, uint64_t* out, hipStream_t s);
-void pack_rows_device(const void* src, long long n, int desc_bytes, long long src_stride, void* dst, hipStream_t s);
+
+// match_filter.hip: ratio test, cross-check, ordered compaction
 int* scan_flags_device(const uint8_t* flags, int n, int** total_dev, hipStream_t s);
 int ratio_filter_device(const uint64_t* keys, int nq, int k, float fs, apds_dmatch* out, hipStream_t s);
 int cross_check_device(const uint64_t* train_best, long long n_train, int nq, apds_dmatch* out, hipStream_t s);
+
+// valu_peak.hip
 double valu_popcount_peak_device();
 int valu_peak_modes();
 const char* valu_peak_mode_name(int mode);
 void valu_peak_device(int mode, int waves_per_simd, double* lane_ops_per_s, double* cycles_per_inst);
 
-// akaze.hip
+// akaze_keypoints.hip
 int akaze_extract_device(const void* img, int rows, int cols, int channels, size_t stride, int max_points, apds_keypoint* kps,
                          uint8_t* desc64, int capacity, hipStream_t s);
 int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, int rows, int cols, int channels, size_t stride, int max_points,
                                apds_keypoint* kps, uint8_t* desc64, int capacity, int* counts, hipStream_t s);
+
+// misc.hip
 void points_from_matches_device(const apds_keypoint* kp1, int n1, const apds_keypoint* kp2, int n2, const apds_dmatch* m, int nm,
                                 int bug_compatible, float* pts1, float* pts2, int* err_flag, hipStream_t s);
 void rgba_to_bgra_device(const uint8_t* rgba, size_t n_pixels, uint8_t* bgra, hipStream_t s);
+int count_nonzero_device(const uint8_t* bytes, int n, int* count_dev, hipStream_t s);   // synchronises s
 
 // ingest.hip
-std::atomic<int>& match_lds_cap();   // match_hamming.hip: occupancy cap of the main Hamming scan
-std::atomic<int>& last_scan_launch_lds();
-void set_thread_scan_cap(int bytes);   // occupancy cap of the scans THIS thread launches (-1: the process-wide one)
-int count_nonzero_device(const uint8_t* bytes, int n, int* count_dev, hipStream_t s);   // misc.hip: synchronises s
 void band_merger_device(const float* r, const float* g, const float* b, size_t n, const double* mm, int bgra, uint8_t* out, hipStream_t s);
 void warp_perspective_device(const uint8_t* src, int rows, int cols, const double* M, int dst_rows, int dst_cols, uint8_t* dst, hipStream_t s);
 void warp_perspective_any_device(const void* src, int rows, int cols, int channels, int elem_bytes, const double* M, int dst_rows, int dst_cols, void* dst,
                                  hipStream_t s);
-
 int world_coordinates_device(const double* xy, int n, const double* dgt_host, const double* egt_host, const double* elev, int ew, int eh, double* xyz,
                              hipStream_t s);
 

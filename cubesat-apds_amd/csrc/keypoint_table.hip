@@ -13,6 +13,7 @@
 #include <cstdlib>
 
 #include "kernels.h"
+#include "topk_keys.h"
 
 namespace apds {
 
@@ -352,7 +353,7 @@ int apds_db_knn_match(void* db, const uint8_t* query_desc, int n_query, int desc
         HIP_CHECK(hipMemcpyAsync(h.data(), keys, h.size() * 8, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         for (size_t i = 0; i < h.size(); i++) {
-            if (h[i] == ~0ull) idx[i] = -1, dist[i] = 0x7fffffff;
+            if (h[i] == EMPTY_KEY) idx[i] = -1, dist[i] = 0x7fffffff;
             else idx[i] = (int32_t)(uint32_t)h[i], dist[i] = (int32_t)(h[i] >> 32);
         }
     });

@@ -13,13 +13,13 @@
 #include <cmath>
 
 #include "kernels.h"
+#include "topk_keys.h"
 
 namespace apds {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static constexpr int L2_TM = 128, L2_TN = 128, L2_KMAX = 128;
-static constexpr uint64_t L2_EMPTY = ~0ull;
 
 __global__ void row_norms_kernel(const float* __restrict__ x, long long n, int dim, float* __restrict__ out) {
     APDS_RAISE_WAVE_PRIORITY();
@@ -55,7 +55,7 @@ __device__ __forceinline__ void top2_insert(Top2& b, float d, uint32_t idx) {
 }
 
 __device__ __forceinline__ uint64_t l2_key(float d, uint32_t idx) {
-    return idx == 0xFFFFFFFFu ? L2_EMPTY : ((uint64_t)__float_as_uint(d) << 32) | idx;   // d >= 0: bit pattern order == value order
+    return idx == 0xFFFFFFFFu ? EMPTY_KEY : ((uint64_t)__float_as_uint(d) << 32) | idx;   // d >= 0: bit pattern order == value order
 }
 
 // grid: x = query tiles (128 queries), y = splits of the train tiles. out: [split][nq][K] keys
@@ -247,7 +247,7 @@ __global__ __launch_bounds__(512) void l2_topk_kernel(const float* __restrict__ 
     }
     __syncthreads();
     if (tid < L2_TN && q0 + tid < nq) {
-        uint64_t b0 = L2_EMPTY, b1 = L2_EMPTY;
+        uint64_t b0 = EMPTY_KEY, b1 = EMPTY_KEY;
         for (int j = 0; j < 64; j++) {
             const uint64_t key = cand[j * L2_TN + tid];
             if (key < b0) {
@@ -375,7 +375,7 @@ int apds_l2_knn_match(const float* q, int nq, const float* t, int nt, int dim, i
         HIP_CHECK(hipMemcpyAsync(h.data(), keys, h.size() * 8, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         for (size_t i = 0; i < h.size(); i++) {
-            if (h[i] == ~0ull) idx[i] = -1, dist[i] = INFINITY;
+            if (h[i] == EMPTY_KEY) idx[i] = -1, dist[i] = INFINITY;
             else {
                 union {
                     uint32_t u;

@@ -39,6 +39,7 @@
 
 #include "config.h"
 #include "kernels.h"
+#include "topk_keys.h"
 
 namespace apds {
 
@@ -53,7 +54,6 @@ static constexpr int SC_NC = APDS_SC_NC;     // 16-query column blocks per wave 
 static constexpr int SC_Q = 8 * 16 * SC_NC;  // queries per block (8 waves)
 static constexpr int SC_D = 128;             // descriptor length (the screen is built for it)
 static constexpr int SC_PITCH = 272;         // bytes per staged train row (256 + 16)
-static constexpr uint64_t SC_EMPTY = ~0ull;
 
 __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
     uint32_t x = __float_as_uint(f);
@@ -99,7 +99,7 @@ __device__ __forceinline__ void sc_insert(ScTop2& b, float d, uint32_t idx) {
         }
     }
 }
-__device__ __forceinline__ uint64_t sc_key(float d, uint32_t idx) { return idx == 0xFFFFFFFFu ? SC_EMPTY : ((uint64_t)__float_as_uint(d) << 32) | idx; }
+__device__ __forceinline__ uint64_t sc_key(float d, uint32_t idx) { return idx == 0xFFFFFFFFu ? EMPTY_KEY : ((uint64_t)__float_as_uint(d) << 32) | idx; }
 
 // PASS 0: running top-2 of the screen value per query -> out[split][nq][2] keys (d^2 = max(|q|^2 + u, 0) bits << 32 | row).
 // PASS 1: rows with u <= theta[q] are appended to the block's own region of cand (query << 32 | row; region = cand_cap entries per
@@ -276,7 +276,7 @@ __global__ void screen_theta_kernel(const uint64_t* __restrict__ top2, const flo
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nq) return;
     const uint64_t k2 = top2[(size_t)i * 2 + 1];
-    if (k2 == SC_EMPTY) {   // fewer than two rows: everything is a candidate
+    if (k2 == EMPTY_KEY) {   // fewer than two rows: everything is a candidate
         theta[i] = INFINITY;
         return;
     }

@@ -14,20 +14,22 @@
 // the rare groups that contain a hit. Train rows are split into chunks over blockIdx.y so the grid fills
 // 256 CUs; per-chunk candidates are merged by a second tiny kernel. Keys are (distance << 32 | index):
 // unsigned 64-bit min reproduces BFMatcher's order (distance, then lower train index).
+//
+// In this file: the scan kernels, their record format and its merge (merge_records_kernel), pack_rows, the occupancy-cap hooks, and the
+// host side - ONE threshold pre-pass -> main scan -> merge sequence (ScanLayout, scan_prepass / scan_main / scan_merge) under the one-call
+// scan, the paged scan and the per-frame split state. Merges of plain key lists: topk_merge.hip; ratio test and cross-check:
+// match_filter.hip; the VALU microbenchmark: valu_peak.hip.
 #include <atomic>
-#include <cstdlib>
-#include <vector>
 
-#include "common.h"
 #include "config.h"
 #include "kernels.h"
+#include "popcount_row.h"
+#include "topk_keys.h"
 
 namespace apds {
 
-typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-static constexpr uint64_t EMPTY_KEY = ~0ull;
 static constexpr int INF_THR = 1 << 20;          // > any Hamming distance of a 512-bit row
 static constexpr uint32_t NO_INDEX = 0xFFFFFFFFu;
 // Per-chunk candidate lists. A work item (one wave: 64*T queries x one row chunk) leaves one RECORD: T*K 64-bit presence masks
@@ -44,14 +46,6 @@ struct PartRecord {
     static constexpr int HEADER = 2 * SLOTS;             // u32 words of masks
     static constexpr int PITCH = HEADER + 64 * SLOTS;    // u32 words per record
 };
-
-// acc + popcount(x) in ONE VALU op. hipcc otherwise splits the accumulate into v_bcnt(x,0) + v_add3 (5 ops per
-// two dwords instead of 4), so the accumulate form is spelled out.
-__device__ __forceinline__ int bcnt_acc(uint32_t x, int acc) {
-    int r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-}
 
 // Lower bound of the distances of one train row to the lane's T queries: popcount over the first 15 dwords (480 bits)
 // on top of start[t] = -threshold. M-LDB uses 486 bits, so dword 15 holds at most 6 set bits of the XOR: if the bound
@@ -283,96 +277,12 @@ __global__ __launch_bounds__(256) void hamming_topk_page_kernel(const u32x16* __
 // (A persistent work-queue form of this kernel - resident workgroups pulling items from an atomic counter - was kept through round 2 behind
 // APDS_MATCH_PERSIST; the plain grid was as fast in every sweep (profiles/r01/match_persistent_sweep.log): deleted in round 3.)
 
-// The same for any k (the sharded matcher above 16 neighbours, and k not a power of two): every list is ascending and all keys are distinct
-// (a key carries its global row), so output j is the smallest key above output j - 1: each lane walks a cursor per list. parts <= 64.
-__global__ void merge_topk_any_kernel(const uint64_t* __restrict__ parts_keys, int parts, int nq, int k, uint64_t* __restrict__ out) {
-    APDS_RAISE_WAVE_PRIORITY();
-    const int qi = blockIdx.x * blockDim.x + threadIdx.x;
-    if (qi >= nq) return;
-    uint16_t cur[64];   // cursor of every list
-    for (int p = 0; p < parts; p++) cur[p] = 0;
-    for (int j = 0; j < k; j++) {
-        uint64_t best = EMPTY_KEY;
-        int arg = -1;
-        for (int p = 0; p < parts; p++) {
-            if (cur[p] >= k) continue;
-            const uint64_t v = parts_keys[((size_t)p * nq + qi) * k + cur[p]];
-            if (v < best) best = v, arg = p;
-        }
-        out[(size_t)qi * k + j] = best;
-        if (arg >= 0) cur[arg]++;
-    }
-}
-
-// merge `parts` sorted candidate lists per query into the k smallest keys
-template <int K>
-__global__ void merge_topk_kernel(const uint64_t* __restrict__ parts_keys, int parts, int nq, uint64_t* __restrict__ out) {
-    APDS_RAISE_WAVE_PRIORITY();
-    const int qi = blockIdx.x * blockDim.x + threadIdx.x;
-    if (qi >= nq) return;
-    uint64_t best[K];
-#pragma unroll
-    for (int k = 0; k < K; k++) best[k] = EMPTY_KEY;
-    auto push = [&](uint64_t key) {
-        if (key < best[K - 1]) {
-            bool placed = false;
-#pragma unroll
-            for (int j = K - 1; j > 0; j--) {
-                if (!placed) {
-                    if (best[j - 1] > key) best[j] = best[j - 1];
-                    else {
-                        best[j] = key;
-                        placed = true;
-                    }
-                }
-            }
-            if (!placed) best[0] = key;
-        }
-    };
-    constexpr int U = K <= 2 ? 8 : 2;   // independent loads in flight per lane
-    int p = 0;
-    for (; p + U <= parts; p += U) {
-        uint64_t v[U][K];
-#pragma unroll
-        for (int u = 0; u < U; u++)
-#pragma unroll
-            for (int k = 0; k < K; k++) v[u][k] = parts_keys[((size_t)(p + u) * nq + qi) * K + k];
-#pragma unroll
-        for (int u = 0; u < U; u++)
-#pragma unroll
-            for (int k = 0; k < K; k++) push(v[u][k]);
-    }
-    for (; p < parts; p++)
-#pragma unroll
-        for (int k = 0; k < K; k++) push(parts_keys[((size_t)p * nq + qi) * K + k]);
-#pragma unroll
-    for (int k = 0; k < K; k++) out[(size_t)qi * K + k] = best[k];
-}
-
 // Merge of the per-chunk records of hamming_topk_kernel. One BLOCK per query tile (lane = the T queries it owned in the match
 // kernel): its four waves take every fourth chunk each, four chunks per trip with all of a trip's loads issued before the first
 // insertion (a wave walking all chunks one by one was a chain of 360 dependent memory round trips: 0.23 ms for 138 waves on an
 // otherwise idle GPU), then wave 0 folds the other waves' lists into its own through LDS. A present key expands to
 // (distance << 32 | row offset + p * rows_per_chunk + row_base); keys are unique, so the K smallest do not depend on the order of
 // insertion. `extra` (nq x K 64-bit keys, may be null) is one more already-expanded sorted list (the sample pass).
-template <int K>
-__device__ __forceinline__ void topk_insert(uint64_t (&best)[K], uint64_t key) {
-    if (key < best[K - 1]) {
-        bool placed = false;
-#pragma unroll
-        for (int j = K - 1; j > 0; j--) {
-            if (!placed) {
-                if (best[j - 1] > key) best[j] = best[j - 1];
-                else {
-                    best[j] = key;
-                    placed = true;
-                }
-            }
-        }
-        if (!placed) best[0] = key;
-    }
-}
-
 template <int T, int K>
 __global__ __launch_bounds__(256) void merge_records_kernel(const uint32_t* __restrict__ recs, int parts, int rows_per_chunk, uint32_t row_base,
                                                             const uint64_t* __restrict__ extra, int nq, uint64_t* __restrict__ out) {
@@ -448,20 +358,13 @@ __global__ __launch_bounds__(256) void merge_records_kernel(const uint32_t* __re
     }
 }
 
-__global__ void take_first_columns_kernel(const uint64_t* __restrict__ in, int nq, int kin, int kout, uint64_t* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)nq * kout) return;
-    const int q = (int)(i / kout), c = (int)(i - (long long)q * kout);
-    out[i] = in[(size_t)q * kin + c];
-}
-
 // second-best distance of a sample of train rows -> initial thresholds for the full scan
 __global__ void thr_from_keys_kernel(const uint64_t* __restrict__ keys, int nq, int K, int* __restrict__ thr) {
     APDS_RAISE_WAVE_PRIORITY();
     const int qi = blockIdx.x * blockDim.x + threadIdx.x;
     if (qi >= nq) return;
     const uint64_t key = keys[(size_t)qi * K + (K - 1)];
-    thr[qi] = key == EMPTY_KEY ? INF_THR : (int)(key >> 32);
+    thr[qi] = key == EMPTY_KEY ? INF_THR : (int)key_rank(key);
 }
 
 __global__ void pack_rows_kernel(const uint8_t* __restrict__ src, long long n, int desc_bytes, long long src_stride,
@@ -479,333 +382,18 @@ __global__ void pack_rows_kernel(const uint8_t* __restrict__ src, long long n, i
     dst[i] = v;
 }
 
-__global__ void ratio_flag_kernel(const uint64_t* __restrict__ keys, int nq, int K, float fs, uint8_t* __restrict__ flags) {
-    APDS_RAISE_WAVE_PRIORITY();
-    const int qi = blockIdx.x * blockDim.x + threadIdx.x;
-    if (qi >= nq) return;
-    const uint64_t k0 = keys[(size_t)qi * K], k1 = keys[(size_t)qi * K + 1];
-    const float d0 = (float)(uint32_t)(k0 >> 32), d1 = (float)(uint32_t)(k1 >> 32);
-    flags[qi] = (k0 != EMPTY_KEY && k1 != EMPTY_KEY && d0 < d1 * fs) ? 1 : 0;
-}
-
-__global__ void crosscheck_scatter_kernel(const uint64_t* __restrict__ train_best, long long n_train, unsigned long long* __restrict__ best_per_query) {
-    APDS_RAISE_WAVE_PRIORITY();
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_train) return;
-    const uint64_t key = train_best[i];
-    if (key == EMPTY_KEY) return;
-    const uint32_t qidx = (uint32_t)key;
-    const uint64_t cand = (key & 0xFFFFFFFF00000000ull) | (uint64_t)(uint32_t)i;
-    atomicMin(&best_per_query[qidx], (unsigned long long)cand);
-}
-
-__global__ void nonempty_flag_kernel(const uint64_t* __restrict__ keys, int n, uint8_t* __restrict__ flags) {
-    APDS_RAISE_WAVE_PRIORITY();
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) flags[i] = keys[i] != EMPTY_KEY;
-}
-
-// ---- ordered compaction: flags -> exclusive positions (3 small kernels, no host round trip) -------------
-static constexpr int SCAN_BLOCK = 1024;
-
-__global__ __launch_bounds__(SCAN_BLOCK) void scan_block_counts_kernel(const uint8_t* __restrict__ flags, int n, int* __restrict__ block_counts) {
-    APDS_RAISE_WAVE_PRIORITY();
-    __shared__ int wsum[SCAN_BLOCK / 64];
-    const int i = blockIdx.x * SCAN_BLOCK + threadIdx.x;
-    const int f = i < n ? (flags[i] != 0) : 0;
-    const unsigned long long b = __ballot(f);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < SCAN_BLOCK / 64; w++) s += wsum[w];
-        block_counts[blockIdx.x] = s;
-    }
-}
-
-// single block: exclusive scan of block_counts in place, total to *total
-__global__ __launch_bounds__(1024) void scan_offsets_kernel(int* __restrict__ block_counts, int nblocks, int* __restrict__ total) {
-    APDS_RAISE_WAVE_PRIORITY();
-    __shared__ int buf[1024];
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nblocks; base += 1024) {
-        const int i = base + threadIdx.x;
-        const int v = i < nblocks ? block_counts[i] : 0;
-        buf[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            int add = threadIdx.x >= off ? buf[threadIdx.x - off] : 0;
-            __syncthreads();
-            buf[threadIdx.x] += add;
-            __syncthreads();
-        }
-        const int incl = buf[threadIdx.x];
-        if (i < nblocks) block_counts[i] = carry + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-__device__ __forceinline__ int block_exclusive_pos(int f, int block_offset) {
-    __shared__ int wsum[SCAN_BLOCK / 64];
-    const unsigned long long b = __ballot(f);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) wsum[w] = __popcll(b);
-    __syncthreads();
-    int before = 0;
-    for (int k = 0; k < w; k++) before += wsum[k];
-    return block_offset + before + __popcll(b & ((1ull << lane) - 1ull));
-}
-
-__global__ __launch_bounds__(SCAN_BLOCK) void emit_ratio_matches_kernel(const uint64_t* __restrict__ keys, int nq, int K, const uint8_t* __restrict__ flags,
-                                                                        const int* __restrict__ block_offsets, apds_dmatch* __restrict__ out) {
-    APDS_RAISE_WAVE_PRIORITY();
-    const int i = blockIdx.x * SCAN_BLOCK + threadIdx.x;
-    const int f = i < nq ? (flags[i] != 0) : 0;
-    const int pos = block_exclusive_pos(f, block_offsets[blockIdx.x]);
-    if (f) {
-        const uint64_t k0 = keys[(size_t)i * K];
-        apds_dmatch m;
-        m.query_idx = i;
-        m.train_idx = (int32_t)(uint32_t)k0;
-        m.img_idx = 0;
-        m.distance = (float)(uint32_t)(k0 >> 32);
-        out[pos] = m;
-    }
-}
-
-// ---- register-only VALU microbenchmark (denominator of the popcount roofline) ---------------------------
-// One instruction kind per MODE, eight independent chains per lane, nothing but that instruction in the loop body (the loop
-// counter is scalar). Modes 0-3 and 8-10 are 32-bit integer ops, 4-7 and 11 are FP32 ops issued by the same waves on the same
-// SIMDs, so one run shows whether the integer ops the match kernel is made of issue at the FP32 rate or at half of it.
-//   0 v_xor_b32(sgpr, vgpr) + v_bcnt_u32_b32 accumulate: the match kernel's inner pair (two lane-ops per pair)
-//   1 v_xor_b32 (sgpr operand)   2 v_bcnt_u32_b32 accumulate   3 v_add_u32 (sgpr operand)
-//   4 v_fma_f32   5 v_add_f32   6 v_pk_fma_f32 (two FMAs per lane per instruction)   7 v_pk_add_f32 (two adds)
-//   8 v_xor_b32 (vgpr, vgpr)   9 v_bfi_b32 (VOP3, three vgprs)   10 v_and_b32 (vgpr, vgpr)   11 v_mul_f32
-// Modes 12-17 replay the ISSUE PATTERN of the match kernel's inner loop (one train row in 15 SGPRs against 4 queries of 15 dwords
-// in VGPRs = 60 xor + 60 bcnt per row) in different instruction orders, to find the order the SIMD issues fastest:
-//   12 query-sequential, one dependent chain per query (xor t,s_j,q_cj ; bcnt a_c,t,a_c for j = 0..14, then the next query): the
-//      order hipcc emits for row_distances()        13 dword-major (the four queries' chains interleaved round-robin)
-//   14 = 13 with the xor of step i+1 issued before the bcnt of step i (two temporaries)      15 = 13 with the row first copied to
-//   VGPRs (15 v_mov per row, not counted) so the xor has no SGPR operand      16 = 12 skewed like 14      17 = 13 with two xors
-//   ahead (three temporaries)
-// Every wave also leaves its s_memtime span, so the host can state cycles per wave-instruction per SIMD without assuming a clock.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-static constexpr int VALU_MODES = 28;
-static constexpr int VALU_CHAINS = 8, VALU_UNROLL = 16;
-
-template <int MODE>
-__global__ __launch_bounds__(256) void valu_peak_kernel(uint32_t* __restrict__ sink, unsigned long long* __restrict__ spans, int iters,
-                                                        const u32x16* __restrict__ rowp) {
-    extern __shared__ uint32_t occupancy_pad[];   // dynamic LDS request only bounds the workgroups per CU
-    if (MODE >= 12) {
-        uint32_t q4[4][15];
-        int a[4];
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            a[c] = c;
-#pragma unroll
-            for (int j = 0; j < 15; j++) q4[c][j] = threadIdx.x * 2654435761u + (c * 16 + j) * 40503u + 1u;
-        }
-        // the row is reloaded every iteration (wave-uniform address: s_load_dwordx16, as in the match kernel), one row ahead; the
-        // xor is plain C and the accumulate is bcnt_acc(), as in row_distances(); sched_barrier(0) pins the order under test
-        // (two adjacent inline-asm VALU ops make hipcc insert an s_nop between them, which the match kernel's loop does not have)
-        u32x16 row = rowp[blockIdx.x & 7];
-        const unsigned long long t0 = __builtin_readcyclecounter();
-        for (int it = 0; it < iters; it++) {
-            const u32x16 next = rowp[(blockIdx.x + it + 1) & 7];
-#define APDS_X(tmp, j, c) { tmp = row[j] ^ q4[c][j]; __builtin_amdgcn_sched_barrier(0); }
-#define APDS_XV(tmp, j, c) { tmp = rv[j] ^ q4[c][j]; __builtin_amdgcn_sched_barrier(0); }
-#define APDS_B(tmp, c) { a[c] = bcnt_acc(tmp, a[c]); __builtin_amdgcn_sched_barrier(0); }
-            __builtin_amdgcn_sched_barrier(0);
-            if (MODE == 12) {
-#pragma unroll
-                for (int c = 0; c < 4; c++)
-#pragma unroll
-                    for (int j = 0; j < 15; j++) { uint32_t t; APDS_X(t, j, c); APDS_B(t, c); }
-            } else if (MODE == 18) {      // 12 with an s_nop between every xor and the bcnt that consumes it
-#pragma unroll
-                for (int c = 0; c < 4; c++)
-#pragma unroll
-                    for (int j = 0; j < 15; j++) { uint32_t t; APDS_X(t, j, c); asm volatile("s_nop 0"); __builtin_amdgcn_sched_barrier(0); APDS_B(t, c); }
-            } else if (MODE == 19) {      // 13 with the s_nop
-#pragma unroll
-                for (int j = 0; j < 15; j++)
-#pragma unroll
-                    for (int c = 0; c < 4; c++) { uint32_t t; APDS_X(t, j, c); asm volatile("s_nop 0"); __builtin_amdgcn_sched_barrier(0); APDS_B(t, c); }
-            } else if (MODE == 20) {      // 12 with an s_nop after EVERY instruction
-#pragma unroll
-                for (int c = 0; c < 4; c++)
-#pragma unroll
-                    for (int j = 0; j < 15; j++) {
-                        uint32_t t;
-                        APDS_X(t, j, c); asm volatile("s_nop 0"); __builtin_amdgcn_sched_barrier(0);
-                        APDS_B(t, c); asm volatile("s_nop 0"); __builtin_amdgcn_sched_barrier(0);
-                    }
-            } else if (MODE == 22) {      // bcnt only (the xor hoisted: 15 xors, then 60 bcnt with an s_nop after each) - is bcnt 4 cycles whatever the phase?
-                uint32_t t[15];
-#pragma unroll
-                for (int j = 0; j < 15; j++) APDS_X(t[j], j, 0);
-#pragma unroll
-                for (int c = 0; c < 4; c++)
-#pragma unroll
-                    for (int j = 0; j < 15; j++) { APDS_B(t[j], c); asm volatile("s_nop 0"); __builtin_amdgcn_sched_barrier(0); }
-            } else if (MODE == 23) {      // X X nop B B
-#pragma unroll
-                for (int c = 0; c < 4; c += 2)
-#pragma unroll
-                    for (int j = 0; j < 15; j++) {
-                        uint32_t t0, t1;
-                        APDS_X(t0, j, c); APDS_X(t1, j, c + 1); asm volatile("s_nop 0"); __builtin_amdgcn_sched_barrier(0);
-                        APDS_B(t0, c); APDS_B(t1, c + 1);
-                    }
-            } else if (MODE == 24) {      // X s_nop 1 B
-#pragma unroll
-                for (int c = 0; c < 4; c++)
-#pragma unroll
-                    for (int j = 0; j < 15; j++) { uint32_t t; APDS_X(t, j, c); asm volatile("s_nop 1"); __builtin_amdgcn_sched_barrier(0); APDS_B(t, c); }
-            } else if (MODE == 25) {      // B nop X (the nop after the bcnt instead of before it): X0, then [B nop X] ...
-                uint32_t t[60];
-                APDS_X(t[0], 0, 0);
-#pragma unroll
-                for (int i = 0; i < 60; i++) {
-                    APDS_B(t[i], i / 15);
-                    asm volatile("s_nop 0"); __builtin_amdgcn_sched_barrier(0);
-                    if (i + 1 < 60) APDS_X(t[i + 1], (i + 1) % 15, (i + 1) / 15);
-                }
-            } else if (MODE == 26) {      // X nop B where the nop is an s_sleep-free scalar ALU op (s_add on a dummy) instead of s_nop
-                int dummy = it;
-#pragma unroll
-                for (int c = 0; c < 4; c++)
-#pragma unroll
-                    for (int j = 0; j < 15; j++) {
-                        uint32_t t;
-                        APDS_X(t, j, c);
-                        asm volatile("s_add_u32 %0, %0, 1" : "+s"(dummy));
-                        __builtin_amdgcn_sched_barrier(0);
-                        APDS_B(t, c);
-                    }
-                if (dummy == 0x7ffffff0) a[0]++;
-            } else if (MODE == 27) {      // X nop B with a second independent pair stream interleaved: X0 X1 nop B0 B1 on two queries at a time, dword-major
-#pragma unroll
-                for (int j = 0; j < 15; j++) {
-                    uint32_t t0, t1, t2, t3;
-                    APDS_X(t0, j, 0); asm volatile("s_nop 0"); __builtin_amdgcn_sched_barrier(0); APDS_B(t0, 0);
-                    APDS_X(t1, j, 1); asm volatile("s_nop 0"); __builtin_amdgcn_sched_barrier(0); APDS_B(t1, 1);
-                    APDS_X(t2, j, 2); asm volatile("s_nop 0"); __builtin_amdgcn_sched_barrier(0); APDS_B(t2, 2);
-                    APDS_X(t3, j, 3); asm volatile("s_nop 0"); __builtin_amdgcn_sched_barrier(0); APDS_B(t3, 3);
-                }
-            } else if (MODE == 21) {      // 12 with ONE SGPR for the whole row (row[0]) instead of fifteen
-#pragma unroll
-                for (int c = 0; c < 4; c++)
-#pragma unroll
-                    for (int j = 0; j < 15; j++) { uint32_t t; t = row[0] ^ q4[c][j]; __builtin_amdgcn_sched_barrier(0); APDS_B(t, c); }
-            } else if (MODE == 13) {
-#pragma unroll
-                for (int j = 0; j < 15; j++)
-#pragma unroll
-                    for (int c = 0; c < 4; c++) { uint32_t t; APDS_X(t, j, c); APDS_B(t, c); }
-            } else if (MODE == 14 || MODE == 17) {
-                constexpr int AHEAD = MODE == 17 ? 2 : 1;
-                uint32_t t[60];
-#pragma unroll
-                for (int i = 0; i < 60 + AHEAD; i++) {
-                    if (i < 60) APDS_X(t[i], i >> 2, i & 3);
-                    if (i >= AHEAD) APDS_B(t[i - AHEAD], (i - AHEAD) & 3);
-                }
-            } else if (MODE == 15) {
-                uint32_t rv[15];
-#pragma unroll
-                for (int j = 0; j < 15; j++) { asm volatile("v_mov_b32 %0, %1" : "=v"(rv[j]) : "s"(row[j])); }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < 15; j++)
-#pragma unroll
-                    for (int c = 0; c < 4; c++) { uint32_t t; APDS_XV(t, j, c); APDS_B(t, c); }
-            } else {   // 16: query-sequential, skewed by one
-                uint32_t t[60];
-#pragma unroll
-                for (int i = 0; i < 61; i++) {
-                    if (i < 60) APDS_X(t[i], i % 15, i / 15);
-                    if (i >= 1) APDS_B(t[i - 1], (i - 1) / 15);
-                }
-            }
-#undef APDS_X
-#undef APDS_XV
-#undef APDS_B
-            row = next;
-        }
-        const unsigned long long t1 = __builtin_readcyclecounter();
-        if ((a[0] + a[1] + a[2] + a[3]) == 0x7fffffff) sink[0] = 1;
-        if ((threadIdx.x & 63) == 0) spans[(size_t)blockIdx.x * 4 + (threadIdx.x >> 6)] = t1 - t0;
-        return;
-    }
-    uint32_t q[VALU_UNROLL];
-#pragma unroll
-    for (int j = 0; j < VALU_UNROLL; j++) q[j] = threadIdx.x * 2654435761u + j * 40503u + 1u;
-    uint32_t acc[VALU_CHAINS];
-    float facc[VALU_CHAINS];
-    f32x2 pacc[VALU_CHAINS];
-#pragma unroll
-    for (int c = 0; c < VALU_CHAINS; c++) {
-        acc[c] = c + threadIdx.x;
-        facc[c] = 1.0f + 0.001f * (float)(c + (threadIdx.x & 7));
-        pacc[c] = f32x2{facc[c], facc[c] * 0.5f};
-    }
-    const float fm = 0.99999f, fa = 1e-6f;
-    const f32x2 pm = {0.99999f, 0.99998f}, pa = {1e-6f, 2e-6f};
-    uint32_t s = blockIdx.x * 97u + 1u;
-    const unsigned long long t0 = __builtin_readcyclecounter();
-    for (int it = 0; it < iters; it++) {
-#pragma unroll
-        for (int j = 0; j < VALU_UNROLL; j++) {
-#pragma unroll
-            for (int c = 0; c < VALU_CHAINS; c++) {
-                if (MODE == 0) {
-                    uint32_t x;
-                    asm volatile("v_xor_b32 %0, %1, %2" : "=v"(x) : "s"(s), "v"(q[j]));
-                    asm volatile("v_bcnt_u32_b32 %0, %1, %0" : "+v"(acc[c]) : "v"(x));
-                } else if (MODE == 1) asm volatile("v_xor_b32 %0, %1, %0" : "+v"(acc[c]) : "s"(s));
-                else if (MODE == 2) asm volatile("v_bcnt_u32_b32 %0, %1, %0" : "+v"(acc[c]) : "v"(q[j]));
-                else if (MODE == 3) asm volatile("v_add_u32 %0, %1, %0" : "+v"(acc[c]) : "s"(s));
-                else if (MODE == 4) asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(facc[c]) : "v"(fm), "v"(fa));
-                else if (MODE == 5) asm volatile("v_add_f32 %0, %1, %0" : "+v"(facc[c]) : "v"(fa));
-                else if (MODE == 6) asm volatile("v_pk_fma_f32 %0, %0, %1, %2" : "+v"(pacc[c]) : "v"(pm), "v"(pa));
-                else if (MODE == 7) asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(pacc[c]) : "v"(pa));
-                else if (MODE == 8) asm volatile("v_xor_b32 %0, %1, %0" : "+v"(acc[c]) : "v"(q[j]));
-                else if (MODE == 9) asm volatile("v_bfi_b32 %0, %0, %1, %2" : "+v"(acc[c]) : "v"(q[j]), "v"(q[(j + 1) & (VALU_UNROLL - 1)]));
-                else if (MODE == 10) asm volatile("v_and_b32 %0, %1, %0" : "+v"(acc[c]) : "v"(q[j]));
-                else asm volatile("v_mul_f32 %0, %1, %0" : "+v"(facc[c]) : "v"(fm));
-            }
-        }
-        s = s * 1664525u + 1013904223u;
-    }
-    const unsigned long long t1 = __builtin_readcyclecounter();
-    uint32_t fold = 0;
-#pragma unroll
-    for (int c = 0; c < VALU_CHAINS; c++) fold += acc[c] + __float_as_uint(facc[c]) + __float_as_uint(pacc[c].x) + __float_as_uint(pacc[c].y);
-    if (fold == 0x7fffffffu) sink[0] = 1;
-    if ((threadIdx.x & 63) == 0) spans[(size_t)blockIdx.x * 4 + (threadIdx.x >> 6)] = t1 - t0;
-}
-
 // ---- host launchers -------------------------------------------------------------------------------------
 struct ChunkPlan {
     int T, chunks, rows_per_chunk, qtiles_blocks;
 };
 
-
-// Occupancy cap of the main scan (bytes of unused dynamic LDS per workgroup; 0 = none), process-wide: APDS_MATCH_LDS_CAP at first
-// use, then apds_dev_match_lds_cap(). See launch_topk.
 // dynamic-LDS bytes the most recent scan launch of the process was made with (test hook: the cap reaches every kernel variant)
 std::atomic<int>& last_scan_launch_lds() {
     static std::atomic<int> v{-1};
     return v;
 }
-
+// Occupancy cap of the main scan (bytes of unused dynamic LDS per workgroup; 0 = none), process-wide: APDS_MATCH_LDS_CAP at first
+// use, then apds_dev_match_lds_cap(). See launch_topk.
 std::atomic<int>& match_lds_cap() {
     static std::atomic<int> cap{config().match_lds_cap};
     return cap;
@@ -901,41 +489,84 @@ static void merge_records_launch(const uint32_t* recs, const ChunkPlan& p, uint3
     }
 }
 
-template <int K>
-static void merge_launch(const uint64_t* parts, int nparts, int nq, uint64_t* out, hipStream_t s) {
-    hipLaunchKernelGGL((merge_topk_kernel<K>), dim3(ceil_div(nq, 256)), dim3(256), 0, s, parts, nparts, nq, out);
-}
 
+// One frame's scan, laid out in one buffer: an optional threshold pre-pass over the first `sample` rows, the main scan over the rest, the
+// merge of the main scan's records with the pre-pass's keys. The one-call scan, the paged scan and the split scan below all run these
+// three steps; they differ in whose memory the buffer is and in what runs between the steps.
+struct ScanLayout {
+    int nq = 0, k = 0;
+    long long nt = 0, sample = 0;
+    ChunkPlan sp{}, p{};   // pre-pass, main scan
+    size_t off_sparts = 0, off_sample_keys = 0, off_thr = 0, off_parts = 0;   // byte offsets: pre-pass records, its merged keys, thresholds, main records
+    size_t bytes = 0;
+};
+
+// `paged`: a page of a k > 16 scan. Those, and every K > 2, keep one query per lane.
 template <int K>
-static void topk_device_k(const void* q, int nq, const void* t, long long nt, uint32_t index_base, uint64_t* out, hipStream_t s) {
-    ThreadCtx& c = ctx();
-    // Phase 0 (only for large scans): exact top-k over the first `sample` rows gives per-query thresholds that
+static ScanLayout scan_layout(int nq, long long nt, bool paged) {
+    ScanLayout L;
+    L.nq = nq, L.k = K, L.nt = nt;
+    // The pre-pass (only for large scans): exact top-k over the first `sample` rows gives per-query thresholds that
     // every chunk starts from, so the rare-hit fast path is reached immediately. The sample rows have the
     // lowest indices, hence a later row at equal distance never outranks them: strict '<' stays exact.
     // (1/16 of the rows, at most APDS_MATCH_SAMPLE = 16384, from 32768 rows up: a 125k-row shard of an 8-GPU run still gets one)
     const int sample_rows = config().match_sample;
-    long long sample = 0;
-    if (sample_rows > 0 && nt >= 32768) sample = std::min<long long>(sample_rows, (nt / 16) & ~1023ll);
-    const int* thr = nullptr;
-    uint64_t* sample_keys = nullptr;
-    if (sample) {
-        ChunkPlan sp = plan_chunks(nq, sample, true, K > 2);
-        uint32_t* sparts = c.alloc_n<uint32_t>(record_words<K>(nq, sp));
-        sample_keys = c.alloc_n<uint64_t>((size_t)nq * K);
-        launch_topk<K>(q, nq, t, sample, nullptr, sparts, sp, s, "hamming_topk_sample");
-        merge_records_launch<K>(sparts, sp, index_base, nullptr, nq, sample_keys, s);
-        int* thr_buf = c.alloc_n<int>(nq);
-        hipLaunchKernelGGL(thr_from_keys_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, s, sample_keys, nq, K, thr_buf);
-        thr = thr_buf;
+    if (sample_rows > 0 && nt >= 32768) L.sample = std::min<long long>(sample_rows, (nt / 16) & ~1023ll);
+    auto take = [&](size_t bytes) {
+        const size_t o = L.bytes;
+        L.bytes += (bytes + 255) & ~(size_t)255;
+        return o;
+    };
+    if (L.sample) {
+        L.sp = plan_chunks(nq, L.sample, true, K > 2 || paged);
+        L.off_sparts = take(record_words<K>(nq, L.sp) * 4);
+        L.off_sample_keys = take((size_t)nq * K * 8);
+        L.off_thr = take((size_t)nq * 4);
     }
-    const char* rest = static_cast<const char*>(t) + (size_t)sample * 64;
-    const long long nrest = nt - sample;
-    ChunkPlan p = plan_chunks(nq, nrest, false, K > 2);
-    uint32_t* parts = c.alloc_n<uint32_t>(record_words<K>(nq, p));   // [chunks][wave tiles] records
-    launch_topk<K>(q, nq, rest, nrest, thr, parts, p, s);
-    // the sample pass's result joins the merge as one more (already expanded) list
-    merge_records_launch<K>(parts, p, index_base + (uint32_t)sample, sample_keys, nq, out, s);
+    L.p = plan_chunks(nq, nt - L.sample, false, K > 2 || paged);
+    L.off_parts = take(record_words<K>(nq, L.p) * 4);   // [chunks][wave tiles] records
+    return L;
+}
+
+// The steps. t: all nt rows; floor_keys / floor_base: the page floor of a paged scan (the kernels compare global row indices with it, so
+// floor_base is the global index of the first row the step scans).
+template <int K>
+static void scan_prepass(const ScanLayout& L, char* buf, const void* q, const void* t, uint32_t index_base, hipStream_t s,
+                         const uint64_t* floor_keys = nullptr, uint32_t floor_base = 0) {
+    if (!L.sample) return;
+    uint32_t* sparts = reinterpret_cast<uint32_t*>(buf + L.off_sparts);
+    uint64_t* sample_keys = reinterpret_cast<uint64_t*>(buf + L.off_sample_keys);
+    launch_topk<K>(q, L.nq, t, L.sample, nullptr, sparts, L.sp, s, "hamming_topk_sample", floor_keys, floor_base);
+    merge_records_launch<K>(sparts, L.sp, index_base, nullptr, L.nq, sample_keys, s);
+    hipLaunchKernelGGL(thr_from_keys_kernel, dim3(ceil_div(L.nq, 256)), dim3(256), 0, s, (const uint64_t*)sample_keys, L.nq, K,
+                       reinterpret_cast<int*>(buf + L.off_thr));
     HIP_CHECK(hipGetLastError());
+}
+
+template <int K>
+static void scan_main(const ScanLayout& L, char* buf, const void* q, const void* t, hipStream_t s, const uint64_t* floor_keys = nullptr,
+                      uint32_t floor_base = 0) {
+    const char* rest = static_cast<const char*>(t) + (size_t)L.sample * 64;
+    launch_topk<K>(q, L.nq, rest, L.nt - L.sample, L.sample ? reinterpret_cast<const int*>(buf + L.off_thr) : nullptr,
+                   reinterpret_cast<uint32_t*>(buf + L.off_parts), L.p, s, "hamming_topk", floor_keys, floor_base);
+}
+
+// the pre-pass's result joins the merge as one more (already expanded) list
+template <int K>
+static void scan_merge(const ScanLayout& L, const char* buf, uint32_t index_base, uint64_t* out, hipStream_t s) {
+    merge_records_launch<K>(reinterpret_cast<const uint32_t*>(buf + L.off_parts), L.p, index_base + (uint32_t)L.sample,
+                            L.sample ? reinterpret_cast<const uint64_t*>(buf + L.off_sample_keys) : nullptr, L.nq, out, s);
+    HIP_CHECK(hipGetLastError());
+}
+
+// The three steps back to back on one stream, on the calling thread's workspace (the sample size: scan_layout).
+template <int K>
+static void topk_device_k(const void* q, int nq, const void* t, long long nt, uint32_t index_base, uint64_t* out, hipStream_t s) {
+    const ScanLayout L = scan_layout<K>(nq, nt, false);
+    char* buf = static_cast<char*>(ctx().alloc(L.bytes));
+    scan_prepass<K>(L, buf, q, t, index_base, s);
+    scan_main<K>(L, buf, q, t, s);
+    scan_merge<K>(L, buf, index_base, out, s);
 }
 
 // k > 16 (BFMatcher::knnMatch takes any k, lib.rs:94-103): pages of 16. Page j is the plain K = 16 scan restricted to the keys above the
@@ -949,36 +580,18 @@ __global__ void gather_pages_kernel(const uint64_t* __restrict__ pages, int nq, 
     out[i] = page < n_pages ? pages[((size_t)page * nq + q) * 16 + (c & 15)] : EMPTY_KEY;
 }
 
-static long long split_sample_rows(long long nt);
-
 static void topk_paged_device(const void* q, int nq, const void* t, long long nt, uint32_t index_base, int k, uint64_t* out, hipStream_t s) {
     constexpr int K = 16;
     ThreadCtx& c = ctx();
     const int n_pages = (int)std::min<long long>(ceil_div(k, K), ceil_div(nt, K));   // pages past the last train row would be empty
-    const long long sample = split_sample_rows(nt);
-    const ChunkPlan p = plan_chunks(nq, nt - sample, false, true);
-    ChunkPlan sp{};
-    uint32_t* sparts = nullptr;
-    uint64_t* sample_keys = nullptr;
-    int* thr = nullptr;
-    if (sample) {
-        sp = plan_chunks(nq, sample, true, true);
-        sparts = c.alloc_n<uint32_t>(record_words<K>(nq, sp));
-        sample_keys = c.alloc_n<uint64_t>((size_t)nq * K);
-        thr = c.alloc_n<int>(nq);
-    }
-    uint32_t* parts = c.alloc_n<uint32_t>(record_words<K>(nq, p));
+    const ScanLayout L = scan_layout<K>(nq, nt, true);
+    char* buf = static_cast<char*>(c.alloc(L.bytes));
     uint64_t* pages = c.alloc_n<uint64_t>((size_t)n_pages * nq * K);
-    const char* rest = static_cast<const char*>(t) + (size_t)sample * 64;
     for (int j = 0; j < n_pages; j++) {
         const uint64_t* floor_keys = j ? pages + (size_t)(j - 1) * nq * K : nullptr;
-        if (sample) {
-            launch_topk<K>(q, nq, t, sample, nullptr, sparts, sp, s, "hamming_topk_sample", floor_keys, index_base);
-            merge_records_launch<K>(sparts, sp, index_base, nullptr, nq, sample_keys, s);
-            hipLaunchKernelGGL(thr_from_keys_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, s, (const uint64_t*)sample_keys, nq, K, thr);
-        }
-        launch_topk<K>(q, nq, rest, nt - sample, thr, parts, p, s, "hamming_topk", floor_keys, index_base + (uint32_t)sample);
-        merge_records_launch<K>(parts, p, index_base + (uint32_t)sample, sample_keys, nq, pages + (size_t)j * nq * K, s);
+        scan_prepass<K>(L, buf, q, t, index_base, s, floor_keys, index_base);
+        scan_main<K>(L, buf, q, t, s, floor_keys, index_base + (uint32_t)L.sample);
+        scan_merge<K>(L, buf, index_base, pages + (size_t)j * nq * K, s);
     }
     hipLaunchKernelGGL(gather_pages_kernel, dim3((unsigned)ceil_div((long long)nq * k, 256)), dim3(256), 0, s, (const uint64_t*)pages, nq, n_pages, k, out);
     HIP_CHECK(hipGetLastError());
@@ -993,18 +606,15 @@ struct TopkSplitState {
     int device = 0;
     char* buf = nullptr;
     size_t cap = 0;
-    // layout of the current frame (offsets into buf), filled by the pre-pass
-    size_t off_sparts = 0, off_sample_keys = 0, off_thr = 0, off_parts = 0;
-    int nq = 0, k = 0;
-    long long nt = 0, sample = 0;
-    ChunkPlan sp{}, p{};
+    // the current frame, filled by the pre-pass: nq, k and nt in both forms, the rest is the vector form's layout of buf
+    ScanLayout L{};
     // the matrix-core form (hamming_mfma.hip): expanded queries, the split lists, and the expanded train rows - the caller's resident copy
     // (topk_split_use_train) when it is one of exactly these rows, this state's own otherwise (expanded by every pre-pass)
     bool mfma = false;
     HmPlan hp{};
     const HmTrain* shared_train = nullptr;
     uint32_t index_base_mfma = 0;
-    size_t off_q4 = 0, off_qp = 0, off_t4 = 0, off_tp = 0, off_top2 = 0;
+    size_t off_q4 = 0, off_qp = 0, off_t4 = 0, off_tp = 0, off_lists = 0, off_top2 = 0;
     const void* t4 = nullptr;
     const float* tp = nullptr;
 };
@@ -1023,9 +633,8 @@ static void split_reserve(TopkSplitState& st, size_t need) {
 
 static void split_prepass_mfma(TopkSplitState& st, const void* q, int nq, const void* t, long long nt, int k, hipStream_t s) {
     st.mfma = true;
-    st.nq = nq;
-    st.k = k;
-    st.nt = nt;
+    st.L = ScanLayout{};
+    st.L.nq = nq, st.L.k = k, st.L.nt = nt;
     st.hp = hm_plan(nq, nt);
     const bool shared = st.shared_train && st.shared_train->src == t && st.shared_train->n == nt;
     size_t need = 0;
@@ -1036,7 +645,7 @@ static void split_prepass_mfma(TopkSplitState& st, const void* q, int nq, const 
     };
     st.off_q4 = take((size_t)nq * 256);
     st.off_qp = take((size_t)nq * 4);
-    st.off_parts = take((size_t)st.hp.splits * nq * 16);
+    st.off_lists = take((size_t)st.hp.splits * nq * 16);
     st.off_top2 = take((size_t)nq * 16);
     if (!shared) {
         st.off_t4 = take((size_t)hm_padded_rows(nt) * 256);
@@ -1056,66 +665,25 @@ static void split_prepass_mfma(TopkSplitState& st, const void* q, int nq, const 
     HIP_CHECK(hipGetLastError());
 }
 static void split_scan_mfma(TopkSplitState& st, hipStream_t s) {
-    hm_scan_device(st.buf + st.off_q4, reinterpret_cast<const float*>(st.buf + st.off_qp), st.nq, st.t4, st.tp, st.nt, st.hp, st.index_base_mfma,
-                   reinterpret_cast<uint64_t*>(st.buf + st.off_parts), s);
+    hm_scan_device(st.buf + st.off_q4, reinterpret_cast<const float*>(st.buf + st.off_qp), st.L.nq, st.t4, st.tp, st.L.nt, st.hp, st.index_base_mfma,
+                   reinterpret_cast<uint64_t*>(st.buf + st.off_lists), s);
 }
 static void split_merge_mfma(TopkSplitState& st, uint64_t* out, hipStream_t s) {
-    const uint64_t* parts = reinterpret_cast<const uint64_t*>(st.buf + st.off_parts);
-    uint64_t* top2 = st.k == 2 ? out : reinterpret_cast<uint64_t*>(st.buf + st.off_top2);
-    if (st.hp.splits > 1) merge_topk_device(parts, st.hp.splits, st.nq, 2, top2, s);
-    else if (st.k == 2) HIP_CHECK(hipMemcpyAsync(out, parts, (size_t)st.nq * 16, hipMemcpyDeviceToDevice, s));
+    const int nq = st.L.nq, k = st.L.k;
+    const uint64_t* parts = reinterpret_cast<const uint64_t*>(st.buf + st.off_lists);
+    uint64_t* top2 = k == 2 ? out : reinterpret_cast<uint64_t*>(st.buf + st.off_top2);
+    if (st.hp.splits > 1) merge_topk_device(parts, st.hp.splits, nq, 2, top2, s);
+    else if (k == 2) HIP_CHECK(hipMemcpyAsync(out, parts, (size_t)nq * 16, hipMemcpyDeviceToDevice, s));
     else top2 = const_cast<uint64_t*>(parts);
-    if (st.k == 1) take_first_columns_device(top2, st.nq, 2, 1, out, s);
+    if (k == 1) take_first_columns_device(top2, nq, 2, 1, out, s);
     HIP_CHECK(hipGetLastError());
-}
-
-static long long split_sample_rows(long long nt) {
-    const int sample_rows = config().match_sample;
-    return (sample_rows > 0 && nt >= 32768) ? std::min<long long>(sample_rows, (nt / 16) & ~1023ll) : 0;
 }
 
 template <int K>
 static void split_prepass_k(TopkSplitState& st, const void* q, int nq, const void* t, long long nt, uint32_t index_base, hipStream_t s) {
-    st.nq = nq;
-    st.k = K;
-    st.nt = nt;
-    st.sample = split_sample_rows(nt);
-    st.p = plan_chunks(nq, nt - st.sample, false, false);
-    size_t need = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = need;
-        need += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    if (st.sample) {
-        st.sp = plan_chunks(nq, st.sample, true, false);
-        st.off_sparts = take(record_words<K>(nq, st.sp) * 4);
-        st.off_sample_keys = take((size_t)nq * K * 8);
-        st.off_thr = take((size_t)nq * 4);
-    }
-    st.off_parts = take(record_words<K>(nq, st.p) * 4);
-    split_reserve(st, need);
-    if (!st.sample) return;
-    uint32_t* sparts = reinterpret_cast<uint32_t*>(st.buf + st.off_sparts);
-    uint64_t* sample_keys = reinterpret_cast<uint64_t*>(st.buf + st.off_sample_keys);
-    launch_topk<K>(q, nq, t, st.sample, nullptr, sparts, st.sp, s, "hamming_topk_sample");
-    merge_records_launch<K>(sparts, st.sp, index_base, nullptr, nq, sample_keys, s);
-    hipLaunchKernelGGL(thr_from_keys_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, s, sample_keys, nq, K, reinterpret_cast<int*>(st.buf + st.off_thr));
-    HIP_CHECK(hipGetLastError());
-}
-
-template <int K>
-static void split_scan_k(TopkSplitState& st, const void* q, const void* t, hipStream_t s) {
-    const char* rest = static_cast<const char*>(t) + (size_t)st.sample * 64;
-    launch_topk<K>(q, st.nq, rest, st.nt - st.sample, st.sample ? reinterpret_cast<const int*>(st.buf + st.off_thr) : nullptr,
-                   reinterpret_cast<uint32_t*>(st.buf + st.off_parts), st.p, s);
-}
-
-template <int K>
-static void split_merge_k(TopkSplitState& st, uint32_t index_base, uint64_t* out, hipStream_t s) {
-    merge_records_launch<K>(reinterpret_cast<const uint32_t*>(st.buf + st.off_parts), st.p, index_base + (uint32_t)st.sample,
-                            st.sample ? reinterpret_cast<const uint64_t*>(st.buf + st.off_sample_keys) : nullptr, st.nq, out, s);
-    HIP_CHECK(hipGetLastError());
+    st.L = scan_layout<K>(nq, nt, false);
+    split_reserve(st, st.L.bytes);
+    scan_prepass<K>(st.L, st.buf, q, t, index_base, s);
 }
 
 void* topk_split_create() {
@@ -1155,25 +723,25 @@ void topk_split_use_train(void* h, const void* hm_train) {
 void topk_split_scan(void* h, const void* q, const void* t, hipStream_t s) {
     APDS_REQUIRE(h, APDS_ERR_BAD_ARG, "null scan state");
     TopkSplitState& st = *static_cast<TopkSplitState*>(h);
-    APDS_REQUIRE(st.nq > 0, APDS_ERR_ASSERT, "scan before pre-pass");
+    APDS_REQUIRE(st.L.nq > 0, APDS_ERR_ASSERT, "scan before pre-pass");
     if (st.mfma) {
         split_scan_mfma(st, s);
         return;
     }
-    if (st.k == 1) split_scan_k<1>(st, q, t, s);
-    else split_scan_k<2>(st, q, t, s);
+    if (st.L.k == 1) scan_main<1>(st.L, st.buf, q, t, s);
+    else scan_main<2>(st.L, st.buf, q, t, s);
 }
 void topk_split_merge(void* h, uint32_t index_base, uint64_t* out, hipStream_t s) {
     APDS_REQUIRE(h && out, APDS_ERR_BAD_ARG, "null scan state / output");
     TopkSplitState& st = *static_cast<TopkSplitState*>(h);
-    APDS_REQUIRE(st.nq > 0, APDS_ERR_ASSERT, "merge before pre-pass");
+    APDS_REQUIRE(st.L.nq > 0, APDS_ERR_ASSERT, "merge before pre-pass");
     if (st.mfma) {
         APDS_REQUIRE(index_base == st.index_base_mfma, APDS_ERR_ASSERT, "the merge's index base differs from the pre-pass's");
         split_merge_mfma(st, out, s);
         return;
     }
-    if (st.k == 1) split_merge_k<1>(st, index_base, out, s);
-    else split_merge_k<2>(st, index_base, out, s);
+    if (st.L.k == 1) scan_merge<1>(st.L, st.buf, index_base, out, s);
+    else scan_merge<2>(st.L, st.buf, index_base, out, s);
 }
 
 // Full top-k of nq queries over nt train rows (device, 64-byte rows). out: nq*k keys. k in {1,2} is the tuned path (the reference only
@@ -1210,29 +778,9 @@ void hamming_topk_device(const void* q, int nq, const void* t, long long nt, uin
         default: topk_device_k<16>(q, nq, t, nt, index_base, dst, s); break;
     }
     if (K != k) {
-        hipLaunchKernelGGL(take_first_columns_kernel, dim3(ceil_div((long long)nq * k, 256)), dim3(256), 0, s, (const uint64_t*)dst, nq, K, k, out);
+        take_first_columns_device(dst, nq, K, k, out, s);
         HIP_CHECK(hipGetLastError());
     }
-}
-
-void take_first_columns_device(const uint64_t* in, int nq, int kin, int kout, uint64_t* out, hipStream_t s) {
-    if (nq <= 0) return;
-    hipLaunchKernelGGL(take_first_columns_kernel, dim3(ceil_div((long long)nq * kout, 256)), dim3(256), 0, s, in, nq, kin, kout, out);
-}
-
-void merge_topk_device(const uint64_t* parts, int nparts, int nq, int k, uint64_t* out, hipStream_t s) {
-    if (nq <= 0) return;
-    switch (k) {
-        case 1: merge_launch<1>(parts, nparts, nq, out, s); break;
-        case 2: merge_launch<2>(parts, nparts, nq, out, s); break;
-        case 4: merge_launch<4>(parts, nparts, nq, out, s); break;
-        case 8: merge_launch<8>(parts, nparts, nq, out, s); break;
-        case 16: merge_launch<16>(parts, nparts, nq, out, s); break;
-        default:
-            APDS_REQUIRE(k >= 1 && k <= 4096 && nparts <= 64, APDS_ERR_ASSERT, "merge supports 1 <= k <= 4096 over at most 64 lists");
-            hipLaunchKernelGGL(merge_topk_any_kernel, dim3(ceil_div(nq, 64)), dim3(64), 0, s, parts, nparts, nq, k, out);
-    }
-    HIP_CHECK(hipGetLastError());
 }
 
 void pack_rows_device(const void* src, long long n, int desc_bytes, long long src_stride, void* dst, hipStream_t s) {
@@ -1242,162 +790,5 @@ void pack_rows_device(const void* src, long long n, int desc_bytes, long long sr
     HIP_CHECK(hipGetLastError());
 }
 
-// flags (n bytes) -> block offsets; returns device pointers for the emit kernel; *total_dev holds the count
-int* scan_flags_device(const uint8_t* flags, int n, int** total_dev, hipStream_t s) {
-    ThreadCtx& c = ctx();
-    const int nblocks = std::max(1, ceil_div(n, SCAN_BLOCK));
-    int* block_counts = c.alloc_n<int>(nblocks + 1);
-    int* total = block_counts + nblocks;
-    hipLaunchKernelGGL(scan_block_counts_kernel, dim3(nblocks), dim3(SCAN_BLOCK), 0, s, flags, n, block_counts);
-    hipLaunchKernelGGL(scan_offsets_kernel, dim3(1), dim3(1024), 0, s, block_counts, nblocks, total);
-    HIP_CHECK(hipGetLastError());
-    *total_dev = total;
-    return block_counts;
-}
-
-int ratio_filter_device(const uint64_t* keys, int nq, int k, float fs, apds_dmatch* out, hipStream_t s) {
-    if (nq <= 0) return 0;
-    ThreadCtx& c = ctx();
-    uint8_t* flags = c.alloc_n<uint8_t>(nq);
-    hipLaunchKernelGGL(ratio_flag_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, s, keys, nq, k, fs, flags);
-    int* total_dev = nullptr;
-    int* offs = scan_flags_device(flags, nq, &total_dev, s);
-    hipLaunchKernelGGL(emit_ratio_matches_kernel, dim3(ceil_div(nq, SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, s, keys, nq, k, flags, offs, out);
-    HIP_CHECK(hipGetLastError());
-    int total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, total_dev, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return total;
-}
-
-int cross_check_device(const uint64_t* train_best, long long n_train, int nq, apds_dmatch* out, hipStream_t s) {
-    if (nq <= 0 || n_train <= 0) return 0;
-    ThreadCtx& c = ctx();
-    uint64_t* best = c.alloc_n<uint64_t>(nq);
-    HIP_CHECK(hipMemsetAsync(best, 0xFF, (size_t)nq * 8, s));
-    hipLaunchKernelGGL(crosscheck_scatter_kernel, dim3(ceil_div(n_train, 256)), dim3(256), 0, s, train_best, n_train,
-                       reinterpret_cast<unsigned long long*>(best));
-    uint8_t* flags = c.alloc_n<uint8_t>(nq);
-    hipLaunchKernelGGL(nonempty_flag_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, s, best, nq, flags);
-    int* total_dev = nullptr;
-    int* offs = scan_flags_device(flags, nq, &total_dev, s);
-    hipLaunchKernelGGL(emit_ratio_matches_kernel, dim3(ceil_div(nq, SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, s, best, nq, 1, flags, offs, out);
-    HIP_CHECK(hipGetLastError());
-    int total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, total_dev, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return total;
-}
-
-// One launch configuration of the microbenchmark: `waves_per_simd` workgroups of 256 threads resident per CU (one wave of each
-// on every SIMD; bounded through an unused dynamic-LDS request), a grid eight rounds deep.
-struct ValuPeak {
-    double lane_ops_per_s;      // wall clock (HIP events), lane-ops as defined per mode (a packed instruction counts two)
-    double cycles_per_inst;     // s_memtime cycles per wave-instruction per SIMD = mean wave span / (instructions per wave * waves per SIMD)
-};
-
-template <int MODE>
-static ValuPeak run_valu_peak(int waves_per_simd, hipStream_t st) {
-    ThreadCtx& c = ctx();
-    const int w = std::min(std::max(waves_per_simd, 1), 8);
-    const int iters = 2048, cus = 256, blocks = cus * w * 8;
-    uint32_t* sink = c.alloc_n<uint32_t>(64);
-    unsigned long long* spans = c.alloc_n<unsigned long long>((size_t)blocks * 4);
-    // 160 KB of LDS per CU: a request of 160 KB / w (minus the granule) admits exactly w workgroups
-    const size_t lds = w >= 8 ? 0 : (size_t)(160 * 1024 / w) - (w == 1 ? 0 : 1024);
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&valu_peak_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipEvent_t a, b;
-    HIP_CHECK(hipEventCreate(&a));
-    HIP_CHECK(hipEventCreate(&b));
-    u32x16* rowp = reinterpret_cast<u32x16*>(c.alloc_n<uint32_t>(16 * 8));
-    {
-        uint32_t h[16 * 8];
-        for (int i = 0; i < 16 * 8; i++) h[i] = 0x9E3779B9u * (uint32_t)(i + 1);
-        HIP_CHECK(hipMemcpyAsync(rowp, h, sizeof(h), hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
-    hipLaunchKernelGGL((valu_peak_kernel<MODE>), dim3(blocks), dim3(256), lds, st, sink, spans, 32, rowp);
-    ValuPeak best{0, 0};
-    std::vector<unsigned long long> host((size_t)blocks * 4);
-    const double per_inst = MODE == 0 ? 1 : ((MODE == 6 || MODE == 7) ? 2 : 1);   // lane-ops per instruction per lane
-    const double insts_per_wave = MODE >= 12 ? (double)iters * 120 : (double)iters * VALU_UNROLL * VALU_CHAINS * (MODE == 0 ? 2 : 1);
-    for (int rep = 0; rep < 3; rep++) {
-        HIP_CHECK(hipEventRecord(a, st));
-        hipLaunchKernelGGL((valu_peak_kernel<MODE>), dim3(blocks), dim3(256), lds, st, sink, spans, iters, rowp);
-        HIP_CHECK(hipEventRecord(b, st));
-        HIP_CHECK(hipEventSynchronize(b));
-        float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-        const double ops = (double)blocks * 256 * insts_per_wave * per_inst;
-        if (ops / (ms * 1e-3) > best.lane_ops_per_s) {
-            HIP_CHECK(hipMemcpy(host.data(), spans, host.size() * 8, hipMemcpyDeviceToHost));
-            double sum = 0;
-            for (unsigned long long v : host) sum += (double)v;
-            best.lane_ops_per_s = ops / (ms * 1e-3);
-            best.cycles_per_inst = sum / (double)host.size() / (insts_per_wave * w);
-        }
-    }
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    return best;
-}
-
-int valu_peak_modes() { return VALU_MODES; }
-
-const char* valu_peak_mode_name(int mode) {
-    static const char* names[VALU_MODES] = {"v_xor_b32(s,v)+v_bcnt_u32_b32", "v_xor_b32(s,v)", "v_bcnt_u32_b32", "v_add_u32(s,v)", "v_fma_f32", "v_add_f32",
-                                            "v_pk_fma_f32", "v_pk_add_f32", "v_xor_b32(v,v)", "v_bfi_b32", "v_and_b32(v,v)", "v_mul_f32",
-                                            "row x 4 queries: query-sequential", "row x 4 queries: dword-major", "dword-major, xor 1 ahead",
-                                            "dword-major, row in VGPRs", "query-sequential, xor 1 ahead", "dword-major, xor 2 ahead",
-                                            "query-sequential + s_nop before each bcnt", "dword-major + s_nop before each bcnt",
-                                            "query-sequential + s_nop after every op", "query-sequential, one SGPR",
-                                            "bcnt + s_nop only (75 ops counted as 120)", "X X nop B B", "X s_nop(1) B", "B nop X", "X s_add B", "dword-major X nop B"};
-    return mode >= 0 && mode < VALU_MODES ? names[mode] : "?";
-}
-
-void valu_peak_device(int mode, int waves_per_simd, double* lane_ops_per_s, double* cycles_per_inst) {
-    hipStream_t st = ctx().stream;
-    ValuPeak r{0, 0};
-    switch (mode) {
-        case 0: r = run_valu_peak<0>(waves_per_simd, st); break;
-        case 1: r = run_valu_peak<1>(waves_per_simd, st); break;
-        case 2: r = run_valu_peak<2>(waves_per_simd, st); break;
-        case 3: r = run_valu_peak<3>(waves_per_simd, st); break;
-        case 4: r = run_valu_peak<4>(waves_per_simd, st); break;
-        case 5: r = run_valu_peak<5>(waves_per_simd, st); break;
-        case 6: r = run_valu_peak<6>(waves_per_simd, st); break;
-        case 7: r = run_valu_peak<7>(waves_per_simd, st); break;
-        case 8: r = run_valu_peak<8>(waves_per_simd, st); break;
-        case 9: r = run_valu_peak<9>(waves_per_simd, st); break;
-        case 10: r = run_valu_peak<10>(waves_per_simd, st); break;
-        case 11: r = run_valu_peak<11>(waves_per_simd, st); break;
-        case 12: r = run_valu_peak<12>(waves_per_simd, st); break;
-        case 13: r = run_valu_peak<13>(waves_per_simd, st); break;
-        case 14: r = run_valu_peak<14>(waves_per_simd, st); break;
-        case 15: r = run_valu_peak<15>(waves_per_simd, st); break;
-        case 16: r = run_valu_peak<16>(waves_per_simd, st); break;
-        case 17: r = run_valu_peak<17>(waves_per_simd, st); break;
-        case 18: r = run_valu_peak<18>(waves_per_simd, st); break;
-        case 19: r = run_valu_peak<19>(waves_per_simd, st); break;
-        case 20: r = run_valu_peak<20>(waves_per_simd, st); break;
-        case 21: r = run_valu_peak<21>(waves_per_simd, st); break;
-        case 22: r = run_valu_peak<22>(waves_per_simd, st); break;
-        case 23: r = run_valu_peak<23>(waves_per_simd, st); break;
-        case 24: r = run_valu_peak<24>(waves_per_simd, st); break;
-        case 25: r = run_valu_peak<25>(waves_per_simd, st); break;
-        case 26: r = run_valu_peak<26>(waves_per_simd, st); break;
-        case 27: r = run_valu_peak<27>(waves_per_simd, st); break;
-        default: fail(APDS_ERR_BAD_ARG, "valu peak: mode out of range");
-    }
-    if (lane_ops_per_s) *lane_ops_per_s = r.lane_ops_per_s;
-    if (cycles_per_inst) *cycles_per_inst = r.cycles_per_inst;
-}
-
-// lane-ops/s of the xor+bcnt pair at full occupancy: the denominator bench.py divides the match kernel by
-double valu_popcount_peak_device() {
-    double v = 0;
-    valu_peak_device(0, 8, &v, nullptr);
-    return v;
-}
 
 }  // namespace apds

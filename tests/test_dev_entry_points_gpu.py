@@ -114,3 +114,29 @@ def test_measurement_and_housekeeping_entries(gpu_pkg, dev):
     check(L.apds_release_cached_memory())
     idx, dist = gpu_pkg.feature_extraction.knn_match(q[:10], db[:100], 2)
     assert idx.shape == (10, 2) and (dist[:, 0] <= dist[:, 1]).all()
+
+
+@pytest.mark.parametrize("k,parts", [(1, 9), (2, 8), (2, 1), (4, 3), (8, 2), (16, 3), (3, 5), (20, 64)])
+def test_merge_topk_equals_sorted_concatenation(dev, k, parts):
+    """apds_dev_merge_topk against numpy: per query, the lists concatenated, sorted, the first k - all ones where fewer rows exist.
+    k = 1, 2 merge eight lists per trip and k = 4, 8, 16 two ((1, 9), (2, 8), (2, 1), (4, 3), (8, 2), (16, 3): whole trips, their tails and
+    no trip at all); every other k walks a cursor per list ((3, 5), (20, 64): the most lists it takes). 300 queries: no multiple of a
+    wave or of a block. Lists are ascending with distinct keys; some are short, one query has none."""
+    torch, d, L, check = dev
+    nq, empty = 300, np.uint64(0xFFFFFFFFFFFFFFFF)
+    rng = np.random.default_rng(100 * k + parts)
+    keys = rng.permutation(parts * nq * k).astype(np.uint64).reshape(parts, nq, k) * np.uint64(977) + np.uint64(1 << 32)   # distinct, below all ones
+    keys[rng.random((parts, nq, k)) < 0.3] = empty          # sorted next: the all-ones entries become the tails of short lists
+    keys[:, 17, :] = empty                                  # a query without a row in any list
+    keys[0, 5, :] = empty                                   # an empty list beside full ones
+    keys.sort(axis=2)
+    want = np.sort(keys.transpose(1, 0, 2).reshape(nq, parts * k), axis=1)
+    want = np.concatenate([want, np.full((nq, k), empty)], axis=1)[:, :k]
+    real = keys[keys != empty]
+    assert len(np.unique(real)) == len(real) and (np.diff(keys.astype(object), axis=2) >= 0).all()   # the input rules: distinct, ascending,
+    assert (keys[:, 17] == empty).all() and (keys[:, :, k - 1] == empty).any() and len(real) > nq   # one query without rows, short lists, rows
+    tp = torch.from_numpy(keys.view(np.int64)).to(d)
+    out = torch.zeros((nq, k), dtype=torch.int64, device=d)
+    check(L.apds_dev_merge_topk(tp.data_ptr(), parts, nq, k, out.data_ptr(), None))
+    torch.cuda.synchronize()
+    assert np.array_equal(out.cpu().numpy().view(np.uint64), want)
