@@ -36,6 +36,7 @@ SYMBOLS = [
     "apds_dev_topk_state_create", "apds_dev_topk_state_destroy", "apds_dev_topk_prepass", "apds_dev_topk_scan", "apds_dev_topk_merge",
     "apds_mosaic_create", "apds_mosaic_destroy", "apds_mosaic_info", "apds_mosaic_min_max", "apds_resample_weights", "apds_mosaic_window",
     "apds_mosaic_tile_extract", "apds_mosaic_tile_extract_batch",
+    "apds_overview_weights", "apds_mosaic_build_overviews", "apds_mosaic_level_info", "apds_mosaic_best_level", "apds_mosaic_window_level",
 ]
 
 RESAMPLE_NEAREST, RESAMPLE_LANCZOS = 0, 1
@@ -249,6 +250,11 @@ def lib():
             "apds_mosaic_window": (i, [vp, i, i, i, i, i, i, i, vp]),
             "apds_mosaic_tile_extract": (i, [vp, i, i, i, i, i, i, i, vp, i, pp, pp, ip, ip]),
             "apds_mosaic_tile_extract_batch": (i, [vp, vp, i, i, i, i, i, i, vp, i, pp, pp, ip, ip]),
+            "apds_overview_weights": (i, [i, i, i, vp, vp, vp]),
+            "apds_mosaic_build_overviews": (i, [vp, i, ip]),
+            "apds_mosaic_level_info": (i, [vp, i, ip, ip]),
+            "apds_mosaic_best_level": (i, [vp, i, i, i, i, ip]),
+            "apds_mosaic_window_level": (i, [vp, i, i, i, i, i, i, i, i, vp]),
         }
         for name, (rt, at) in sig.items():
             fn = getattr(L, name)

@@ -207,7 +207,7 @@ int apds_mosaic_tile_extract(void* mosaic, int x0, int y0, int win_w, int win_h,
         *desc_bytes = APDS_DESC_BYTES;
         Mosaic* m = static_cast<Mosaic*>(mosaic);
         const int32_t xy0[2] = {x0, y0};
-        mosaic_check_window(m, xy0, 1, win_w, win_h, out_w, out_h, resample);
+        mosaic_check_window(m, 0, xy0, 1, win_w, win_h, out_w, out_h, resample);
         if (max_points <= 0) max_points = APDS_MAX_POINTS;
         double own[6];
         if (!minmax6) {
@@ -220,7 +220,7 @@ int apds_mosaic_tile_extract(void* mosaic, int x0, int y0, int win_w, int win_h,
         const size_t px = (size_t)out_w * out_h;
         float* bands = c.alloc_n<float>(3 * px);
         uint8_t* dimg = c.alloc_n<uint8_t>(px * 4);
-        mosaic_window_device(m, xy0, 1, win_w, win_h, out_w, out_h, resample, bands, s);
+        mosaic_read_device(m, xy0, 1, win_w, win_h, out_w, out_h, resample, bands, s);
         band_merger_device(bands, bands + px, bands + 2 * px, px, minmax6, /*bgra=*/1, dimg, s);
         extract_to_host(c, s, dimg, out_h, out_w, 4, (size_t)out_w * 4, max_points, kps, desc, n);
     });
@@ -237,7 +237,7 @@ int apds_mosaic_tile_extract_batch(void* mosaic, const int32_t* xy0, int n_tiles
         *desc = nullptr;
         *desc_bytes = APDS_DESC_BYTES;
         Mosaic* m = static_cast<Mosaic*>(mosaic);
-        mosaic_check_window(m, xy0, n_tiles, win_w, win_h, out_w, out_h, resample);
+        mosaic_check_window(m, 0, xy0, n_tiles, win_w, win_h, out_w, out_h, resample);
         if (max_points <= 0) max_points = APDS_MAX_POINTS;
         for (int i = 0; i < n_tiles; i++) counts[i] = 0;
         double own[6];
@@ -254,7 +254,7 @@ int apds_mosaic_tile_extract_batch(void* mosaic, const int32_t* xy0, int n_tiles
         const int capacity = batch_capacity(out_h, out_w, max_points);
         apds_keypoint* dk = c.alloc_n<apds_keypoint>((size_t)capacity * n_tiles);
         uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * 64 * n_tiles);
-        mosaic_window_device(m, xy0, n_tiles, win_w, win_h, out_w, out_h, resample, bands, s);
+        mosaic_read_device(m, xy0, n_tiles, win_w, win_h, out_w, out_h, resample, bands, s);
         band_merger_device(bands, bands + all, bands + 2 * all, all, minmax6, /*bgra=*/1, dimg, s);
         akaze_extract_batch_device(dimg, n_tiles, px * 4, out_h, out_w, 4, (size_t)out_w * 4, max_points, dk, dd, capacity, counts, s);
         batch_results_to_host(c, s, dk, dd, capacity, n_tiles, counts, kps, desc);

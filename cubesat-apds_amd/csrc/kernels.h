@@ -79,11 +79,13 @@ void warp_perspective_any_device(const void* src, int rows, int cols, int channe
 int world_coordinates_device(const double* xy, int n, const double* dgt_host, const double* egt_host, const double* elev, int ew, int eh, double* xyz,
                              hipStream_t s);
 
-// mosaic.hip: the mosaic resident in HBM (apds_mosaic_*). check_window throws what the entry points report; window_device writes
-// out[band][tile][out_h][out_w] f32 (the layout band_merger_device reads a batch in) and returns when the kernels are done.
+// mosaic.hip: the mosaic resident in HBM (apds_mosaic_*). check_window throws what the entry points report for windows of the raster of
+// `level` (0: the base raster); read_device writes out[band][tile][out_h][out_w] f32 (the layout band_merger_device reads a batch in) and
+// returns when the kernels are done: the base-raster windows themselves, or, on a handle with overviews, their image on the level GDAL
+// would serve the read from.
 struct Mosaic;
-void mosaic_check_window(const Mosaic* m, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample);
-void mosaic_window_device(const Mosaic* m, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample, float* out, hipStream_t s);
+void mosaic_check_window(const Mosaic* m, int level, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample);
+void mosaic_read_device(const Mosaic* m, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample, float* out, hipStream_t s);
 void mosaic_min_max(Mosaic* m, double* minmax6);   // cached in the handle; resets the calling thread's workspace when it computes
 
 // homography.hip

@@ -6,7 +6,9 @@
 //   * the separable Lanczos pair: a row pass that stages source rows in LDS and a column pass over the row-filtered strip. The weights
 //     are computed in double on the host (apds_resample_weights), rounded once to f32 and read as per-output (start, count, weights)
 //     tables; taps are clamped to the RASTER, so a tile's footprint reaches into its neighbours. One launch per pass covers every tile
-//     and band of a batch. The rule itself (GDAL's convolution resampler restated) is in DESIGN.md section 2.
+//     and band of a batch. The rule itself (GDAL's convolution resampler restated) is in DESIGN.md section 2;
+//   * the overview pyramid a COG carries beside the raster (levels of factor 2, 4, 8, ..., each resampled from the one below with
+//     Keys' cubic): one fused launch per level, and the window read of a handle that has them served from the level GDAL would pick.
 #include <algorithm>
 #include <cmath>
 #include <mutex>
@@ -16,13 +18,22 @@
 
 namespace apds {
 
+struct MosaicLevel {
+    int rows = 0, cols = 0;
+    float* data = nullptr;   // [3][rows][cols]
+};
+
 struct Mosaic {
     int device = 0;
     int rows = 0, cols = 0;
     float* data = nullptr;   // [3][rows][cols]
-    std::mutex m;            // the min/max cache is the only state that changes after create
+    std::mutex m;            // the min/max cache and the one build of the overviews are the only state that changes after create
     bool mm_valid = false;
     double mm[6] = {0, 0, 0, 0, 0, 0};
+    int ov_min_size = 0;                  // the argument the overviews were built with; 0: not built
+    std::vector<MosaicLevel> overviews;   // level k >= 1 at [k - 1]: ceil(rows / 2^k) x ceil(cols / 2^k)
+    int n_levels() const { return (int)overviews.size(); }
+    MosaicLevel level(int k) const { return k == 0 ? MosaicLevel{rows, cols, data} : overviews[(size_t)k - 1]; }
 };
 
 // one tile of a batch: window origin, its x / y weight table (tap starts in a table are relative to the window origin), and the source
@@ -34,6 +45,12 @@ struct MosaicTile {
 constexpr int kRowsPerBlock = 4;     // source rows a row-pass block filters with one read of the weights
 constexpr int kSegCap = 2304;        // floats of one staged source-row segment: 8 * (256 + 6) + 2 = 2098 serves ratio 8 at 256 outputs a block
 constexpr int kColsPerThread = 4;    // output rows a column-pass thread produces from one walk over the strip
+// one cascade step of the overviews: ratio = n / ceil(n / 2) <= 2, so the cubic's radius 2 * ratio <= 4 and an output has at most 9 taps
+constexpr int kOvTaps = 9;
+constexpr int kOvTx = 64, kOvTy = 16;   // outputs of one block: a wave is one output row wide
+constexpr int kOvSrcW = 144;            // source columns under 64 outputs: 63 * 2 + 9 = 135, 3 in front and 3 behind for 16-byte loads
+constexpr int kOvSrcH = 40;             // source rows under 16 outputs: 15 * 2 + 9 = 39
+constexpr int kOvRowsPerWave = kOvTy / 4;
 
 // NaN is the identity of both folds: a band without a number reduces to NaN, as numpy's nanmin / nanmax give it
 __device__ __forceinline__ float nan_min(float a, float v) { return (v < a || a != a) ? v : a; }
@@ -179,6 +196,70 @@ __global__ __launch_bounds__(256) void mosaic_lanczos_cols_kernel(const float* _
         if (oy0 + o < out_h) out[((size_t)z * out_h + oy0 + o) * out_w + ox] = acc[o];
 }
 
+// One cascade step of the overviews, level k - 1 -> level k, fused. grid (ceil(out_w / 64), ceil(out_h / 16), 3), 256 threads: a block owns
+// 64 x 16 outputs of one band. It reads the source rectangle under them once into LDS (16 bytes a lane when rows start 16-byte aligned,
+// i.e. cols is a multiple of four), filters rows (along x) into a second LDS array - lane i owns output column i with its weights in
+// registers, a wave walks the source rows - and filters columns from that: lane i reads float i of a row (no bank conflict), the weights
+// are the same for a wave (scalar loads). Per-output (start, count, weights[9]) tables, xw tap-major: odd sizes and the clamped edges are
+// in the tables. f32, fused multiply-adds in tap order; NaN propagates. Nothing goes through the workspace.
+__global__ __launch_bounds__(256) void mosaic_overview_kernel(const float* __restrict__ src, int rows, int cols, const int* __restrict__ xstart,
+                                                              const int* __restrict__ xcount, const float* __restrict__ xw, const int* __restrict__ ystart,
+                                                              const int* __restrict__ ycount, const float* __restrict__ yw, int out_w, int out_h,
+                                                              float* __restrict__ out) {
+    APDS_RAISE_WAVE_PRIORITY();
+    __shared__ __attribute__((aligned(16))) float tile[kOvSrcH][kOvSrcW];
+    __shared__ float filt[kOvSrcH][kOvTx];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int band = blockIdx.z;
+    const int ox0 = blockIdx.x * kOvTx, oy0 = blockIdx.y * kOvTy;
+    const int oxl = min(ox0 + kOvTx, out_w) - 1, oyl = min(oy0 + kOvTy, out_h) - 1;
+    const int xs0 = xstart[ox0], xs1 = xstart[oxl] + xcount[oxl];   // starts and ends grow with the output index: one contiguous rectangle
+    const int ys0 = ystart[oy0], ys1 = ystart[oyl] + ycount[oyl];
+    const bool vec = (cols & 3) == 0;
+    const int xa = vec ? xs0 & ~3 : xs0;
+    const int w = min((vec ? (xs1 + 3) & ~3 : xs1) - xa, kOvSrcW);   // the host has checked that the rectangle fits: never clamps
+    const int nr = min(ys1 - ys0, kOvSrcH);
+    const float* base = src + ((size_t)band * rows + ys0) * cols + xa;
+    if (vec) {
+        const int nch = w >> 2;
+        for (int i = tid; i < nr * nch; i += 256) {
+            const int r = i / nch, ch = i - r * nch;
+            *reinterpret_cast<float4*>(&tile[r][4 * ch]) = *reinterpret_cast<const float4*>(base + (size_t)r * cols + 4 * ch);
+        }
+    } else {
+        for (int i = tid; i < nr * w; i += 256) {
+            const int r = i / w, x = i - r * w;
+            tile[r][x] = base[(size_t)r * cols + x];
+        }
+    }
+    __syncthreads();
+    const int ox = min(ox0 + lane, out_w - 1);   // lanes past the raster repeat its last column (computed, not stored)
+    const int sx = max(xstart[ox] - xa, 0);
+    const int cx = min(xcount[ox], w - sx);
+    float wx[kOvTaps];
+#pragma unroll
+    for (int k = 0; k < kOvTaps; k++) wx[k] = xw[(size_t)k * out_w + ox];
+    for (int r = wave; r < nr; r += 4) {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < kOvTaps; k++)
+            if (k < cx) acc = __builtin_fmaf(tile[r][sx + k], wx[k], acc);
+        filt[r][lane] = acc;
+    }
+    __syncthreads();
+    if (ox0 + lane >= out_w) return;
+    for (int o = 0; o < kOvRowsPerWave; o++) {
+        const int oy = oy0 + wave * kOvRowsPerWave + o;   // the same for a wave
+        if (oy >= out_h) break;
+        const int sy = max(ystart[oy] - ys0, 0);
+        const int cy = min(ycount[oy], nr - sy);
+        const float* wy = yw + (size_t)oy * kOvTaps;
+        float acc = 0.f;
+        for (int k = 0; k < cy; k++) acc = __builtin_fmaf(filt[sy + k][lane], wy[k], acc);
+        out[((size_t)band * out_h + oy) * out_w + ox] = acc;
+    }
+}
+
 namespace {
 
 // L(0) = 1, L(x) = sin(pi x) sin(pi x / 3) / (pi^2 x^2 / 3) for 0 < |x| < 3, 0 otherwise
@@ -189,12 +270,27 @@ double lanczos3(double x) {
     return std::sin(a) * std::sin(a / 3.0) / (a * a / 3.0);
 }
 
+// Keys' cubic with a = -0.5 (the overviews' kernel): support 2
+double cubic(double x) {
+    const double a = std::fabs(x);
+    if (a <= 1.0) return 1.5 * a * a * a - 2.5 * a * a + 1.0;
+    if (a < 2.0) return -0.5 * a * a * a + 2.5 * a * a - 4.0 * a + 2.0;
+    return 0.0;
+}
+
+// a convolution kernel of the resampling rule: its function and the support it has at scale 1
+struct ConvKernel {
+    double (*f)(double);
+    double support;
+};
+constexpr ConvKernel kLanczos3{lanczos3, 3.0}, kCubic{cubic, 2.0};
+
 int nearest_index(int i, int win, int n_out) {
     return (int)std::min<int64_t>((int64_t)((i + 0.5) * ((double)win / n_out)), (int64_t)win - 1);
 }
 
 // taps [first, last) of output i, clamped to the raster (n_src <= 0: no raster, the footprint as it is)
-void lanczos_taps(int n_src, double offset, double ratio, double radius, int i, int* first, int* last, double* centre) {
+void conv_taps(int n_src, double offset, double ratio, double radius, int i, int* first, int* last, double* centre) {
     const double c = (i + 0.5) * ratio + offset;
     const double lo = std::floor(c - radius + 0.5), hi = c + radius + 0.5;
     *first = (int)(n_src > 0 ? std::max(lo, 0.0) : lo);
@@ -202,21 +298,21 @@ void lanczos_taps(int n_src, double offset, double ratio, double radius, int i, 
     *centre = c;
 }
 
-// the Lanczos table of one axis: start / count / weights[max_taps] per output, and the widest footprint (start null: only that)
-int lanczos_table(int n_src, double offset, double ratio, int n_out, int max_taps, int32_t* start, int32_t* count, float* weights) {
-    const double sw = std::min(1.0, 1.0 / ratio), radius = 3.0 / sw;
+// the table of one axis under kernel `kern`: start / count / weights[max_taps] per output, and the widest footprint (start null: only that)
+int conv_table(const ConvKernel& kern, int n_src, double offset, double ratio, int n_out, int max_taps, int32_t* start, int32_t* count, float* weights) {
+    const double sw = std::min(1.0, 1.0 / ratio), radius = kern.support / sw;
     int need = 1;
     std::vector<double> w;
     for (int i = 0; i < n_out; i++) {
         int a, b;
         double c;
-        lanczos_taps(n_src, offset, ratio, radius, i, &a, &b, &c);
+        conv_taps(n_src, offset, ratio, radius, i, &a, &b, &c);
         need = std::max(need, b - a);
         if (!start) continue;
         w.resize((size_t)std::max(b - a, 1));
         double sum = 0.0;
         for (int j = a; j < b; j++) {
-            w[j - a] = lanczos3((j + 0.5 - c) * sw);
+            w[j - a] = kern.f((j + 0.5 - c) * sw);
             sum += w[j - a];
         }
         start[i] = a;
@@ -234,7 +330,7 @@ void resample_table(int n_src, double offset, double span, int n_out, int resamp
     APDS_REQUIRE(offset >= 0 && offset + span <= (double)n_src, APDS_ERR_OUT_OF_RANGE, "window outside the raster");
     const double ratio = span / n_out;
     APDS_REQUIRE(ratio <= 64.0, APDS_ERR_BAD_ARG, "window / output above 64 (385 taps) is not served");
-    const int need = resample == APDS_RESAMPLE_LANCZOS ? lanczos_table(n_src, offset, ratio, n_out, 0, nullptr, nullptr, nullptr) : 1;
+    const int need = resample == APDS_RESAMPLE_LANCZOS ? conv_table(kLanczos3, n_src, offset, ratio, n_out, 0, nullptr, nullptr, nullptr) : 1;
     if (taps_needed) *taps_needed = need;
     if (max_taps == 0 && !start) return;
     APDS_REQUIRE(start && count && weights, APDS_ERR_BAD_ARG, "null output");
@@ -248,7 +344,7 @@ void resample_table(int n_src, double offset, double span, int n_out, int resamp
         }
         return;
     }
-    lanczos_table(n_src, offset, ratio, n_out, max_taps, start, count, weights);
+    conv_table(kLanczos3, n_src, offset, ratio, n_out, max_taps, start, count, weights);
 }
 
 // The tables of one axis of a batch. A window origin moves the taps with it and changes nothing else, unless the raster's edge cuts a
@@ -263,11 +359,11 @@ struct AxisTables {
     void prepare(int n_src_, int win_, int n_out_) {
         n_src = n_src_, win = win_, n_out = n_out_;
         const double ratio = (double)win / n_out;
-        taps = lanczos_table(0, 0.0, ratio, n_out, 0, nullptr, nullptr, nullptr);   // the clamp only shortens a footprint
+        taps = conv_table(kLanczos3, 0, 0.0, ratio, n_out, 0, nullptr, nullptr, nullptr);   // the clamp only shortens a footprint
         in_start.resize((size_t)n_out);
         in_count.resize((size_t)n_out);
         in_weights.assign((size_t)n_out * taps, 0.0f);
-        lanczos_table(0, 0.0, ratio, n_out, taps, in_start.data(), in_count.data(), in_weights.data());
+        conv_table(kLanczos3, 0, 0.0, ratio, n_out, taps, in_start.data(), in_count.data(), in_weights.data());
     }
     int index_of(int origin) {
         const bool interior = origin + in_start[0] >= 0 && origin + in_start[n_out - 1] + in_count[n_out - 1] <= n_src;
@@ -312,22 +408,27 @@ T* upload(ThreadCtx& c, const std::vector<T>& v, hipStream_t s) {
 
 }  // namespace
 
-void mosaic_check_window(const Mosaic* m, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample) {
+void mosaic_check_window(const Mosaic* m, int level, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample) {
     APDS_REQUIRE(m && xy0, APDS_ERR_BAD_ARG, "null argument");
+    APDS_REQUIRE(level >= 0 && level <= m->n_levels(), APDS_ERR_OUT_OF_RANGE, "the mosaic has no such overview level");
+    const MosaicLevel lv = m->level(level);
     APDS_REQUIRE(n_tiles >= 1 && n_tiles <= 4096, APDS_ERR_BAD_ARG, "batch must hold 1 .. 4096 tiles");
     APDS_REQUIRE(win_w > 0 && win_h > 0 && out_w > 0 && out_h > 0, APDS_ERR_ASSERT, "empty window or output");
     APDS_REQUIRE(resample == APDS_RESAMPLE_NEAREST || resample == APDS_RESAMPLE_LANCZOS, APDS_ERR_BAD_ARG, "unknown resampling mode");
     for (int i = 0; i < n_tiles; i++) {
         const int64_t x0 = xy0[2 * i], y0 = xy0[2 * i + 1];
-        APDS_REQUIRE(x0 >= 0 && y0 >= 0 && x0 + win_w <= m->cols && y0 + win_h <= m->rows, APDS_ERR_OUT_OF_RANGE, "window outside the raster");
+        APDS_REQUIRE(x0 >= 0 && y0 >= 0 && x0 + win_w <= lv.cols && y0 + win_h <= lv.rows, APDS_ERR_OUT_OF_RANGE, "window outside the raster");
     }
     APDS_REQUIRE((int64_t)win_w <= 64ll * out_w && (int64_t)win_h <= 64ll * out_h, APDS_ERR_BAD_ARG, "window / output above 64 (385 taps) is not served");
     APDS_REQUIRE(m->device == ctx().device, APDS_ERR_BAD_ARG, "the mosaic lives on another device than the calling thread's");
 }
 
-// The windows of n_tiles origins (xy0: x, y pairs) resampled to out_w x out_h, band-major on the device: out[band][tile][out_h][out_w].
-// Asynchronous on s; the tables and the row-filtered strip live in the calling thread's workspace. The arguments have been checked.
-void mosaic_window_device(const Mosaic* m, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample, float* out, hipStream_t s) {
+// The windows of n_tiles origins (xy0: x, y pairs, in the pixels of `level`) of that level's raster resampled to out_w x out_h, band-major
+// on the device: out[band][tile][out_h][out_w]. The tables and the row-filtered strip live in the calling thread's workspace; returns when
+// the kernels are done. The arguments have been checked.
+void mosaic_window_device(const Mosaic* m, int level, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample, float* out,
+                          hipStream_t s) {
+    const MosaicLevel lv = m->level(level);
     ThreadCtx& c = ctx();
     std::vector<MosaicTile> tiles((size_t)n_tiles);
     for (int i = 0; i < n_tiles; i++) tiles[i] = MosaicTile{xy0[2 * i], xy0[2 * i + 1], 0, 0, 0, 0};
@@ -342,8 +443,8 @@ void mosaic_window_device(const Mosaic* m, const int32_t* xy0, int n_tiles, int 
         {
             KernelTimer timer("mosaic_resample", s);
             for (int y = 0; y < out_h; y += 65535) {   // grid.y is a 16-bit quantity
-                hipLaunchKernelGGL(mosaic_nearest_kernel, dim3(ceil_div(out_w, 256), std::min(out_h - y, 65535), 3 * n_tiles), block, 0, s, (const float*)m->data,
-                                   m->rows, m->cols, dt, n_tiles, dxs, dys + y, out_w, out_h, out + (size_t)y * out_w);
+                hipLaunchKernelGGL(mosaic_nearest_kernel, dim3(ceil_div(out_w, 256), std::min(out_h - y, 65535), 3 * n_tiles), block, 0, s, (const float*)lv.data,
+                                   lv.rows, lv.cols, dt, n_tiles, dxs, dys + y, out_w, out_h, out + (size_t)y * out_w);
                 HIP_CHECK(hipGetLastError());
             }
         }
@@ -351,8 +452,8 @@ void mosaic_window_device(const Mosaic* m, const int32_t* xy0, int n_tiles, int 
         return;
     }
     AxisTables X, Y;
-    X.prepare(m->cols, win_w, out_w);
-    Y.prepare(m->rows, win_h, out_h);
+    X.prepare(lv.cols, win_w, out_w);
+    Y.prepare(lv.rows, win_h, out_h);
     for (int i = 0; i < n_tiles; i++) {
         tiles[i].xt = X.index_of(tiles[i].x0);
         tiles[i].yt = Y.index_of(tiles[i].y0);
@@ -392,14 +493,149 @@ void mosaic_window_device(const Mosaic* m, const int32_t* xy0, int n_tiles, int 
     APDS_REQUIRE(ceil_div(nr_max, kRowsPerBlock) <= 65535 && ceil_div(out_h, kColsPerThread) <= 65535, APDS_ERR_BAD_ARG, "window too tall for one launch");
     {
         KernelTimer timer("mosaic_resample", s);
-        hipLaunchKernelGGL(mosaic_lanczos_rows_kernel, dim3(ceil_div(out_w, oxb), ceil_div(nr_max, kRowsPerBlock), 3 * n_tiles), block, 0, s, (const float*)m->data, m->rows,
-                           m->cols, dt, n_tiles, dxs, dxc, dxw, X.taps, out_w, oxb, nr_max, tmp);
+        hipLaunchKernelGGL(mosaic_lanczos_rows_kernel, dim3(ceil_div(out_w, oxb), ceil_div(nr_max, kRowsPerBlock), 3 * n_tiles), block, 0, s, (const float*)lv.data, lv.rows,
+                           lv.cols, dt, n_tiles, dxs, dxc, dxw, X.taps, out_w, oxb, nr_max, tmp);
         HIP_CHECK(hipGetLastError());
         hipLaunchKernelGGL(mosaic_lanczos_cols_kernel, dim3(ceil_div(out_w, 256), ceil_div(out_h, kColsPerThread), 3 * n_tiles), block, 0, s, (const float*)tmp, dt, n_tiles,
                            dys, dyc, dyw, Y.taps, out_w, out_h, nr_max, out);
         HIP_CHECK(hipGetLastError());
     }
     HIP_CHECK(hipStreamSynchronize(s));   // the host tables are this call's locals
+}
+
+// GDAL's choice of overview for a read of win -> out, restated: the largest level whose factor does not exceed the
+// read's own downsampling; 0 without overviews or below a factor of 2
+int mosaic_best_level(const Mosaic* m, int win_w, int win_h, int out_w, int out_h) {
+    const double desired = std::min((double)win_w / out_w, (double)win_h / out_h);
+    if (desired < 2.0) return 0;
+    int best = 0;
+    for (int k = 1; k <= m->n_levels(); k++) {
+        const MosaicLevel lv = m->level(k);
+        if (std::min((double)m->cols / lv.cols, (double)m->rows / lv.rows) <= desired) best = k;
+    }
+    return best;
+}
+
+// a base-raster window on one axis of a level, as GDAL's overview read maps an integer window: origin and extent rounded to the nearest
+// pixel of the level, the extent at least 1 and shortened to the level's edge
+static void map_to_level(int n_base, int n_level, int x0, int win, int32_t* ox, int* ow) {
+    const double f = (double)n_base / n_level;
+    *ox = std::min(n_level - 1, (int)(x0 / f + 0.5));
+    *ow = std::min(std::max(1, (int)(win / f + 0.5)), n_level - *ox);
+}
+
+// What apds_mosaic_window and apds_mosaic_tile_extract* read: without overviews the window itself; with them the window mapped onto the
+// level mosaic_best_level picks, read there with the caller's mode (for windows a power of two times the output that is a copy of the
+// overview). The windows have been checked against the base raster. out as mosaic_window_device.
+void mosaic_read_device(const Mosaic* m, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample, float* out, hipStream_t s) {
+    const int level = mosaic_best_level(m, win_w, win_h, out_w, out_h);
+    if (level == 0) return mosaic_window_device(m, 0, xy0, n_tiles, win_w, win_h, out_w, out_h, resample, out, s);
+    const MosaicLevel lv = m->level(level);
+    std::vector<int32_t> xy((size_t)2 * n_tiles);
+    std::vector<int> wh((size_t)2 * n_tiles);
+    bool one_shape = true;
+    for (int i = 0; i < n_tiles; i++) {
+        map_to_level(m->cols, lv.cols, xy0[2 * i], win_w, &xy[2 * i], &wh[2 * i]);
+        map_to_level(m->rows, lv.rows, xy0[2 * i + 1], win_h, &xy[2 * i + 1], &wh[2 * i + 1]);
+        one_shape = one_shape && wh[2 * i] == wh[0] && wh[2 * i + 1] == wh[1];
+    }
+    if (one_shape) {
+        mosaic_check_window(m, level, xy.data(), n_tiles, wh[0], wh[1], out_w, out_h, resample);
+        return mosaic_window_device(m, level, xy.data(), n_tiles, wh[0], wh[1], out_w, out_h, resample, out, s);
+    }
+    // a window that the level's edge shortened has tables of its own: tile by tile, each moved to its place in the band-major batch
+    const size_t px = (size_t)out_w * out_h;
+    float* one = ctx().alloc_n<float>(3 * px);
+    for (int i = 0; i < n_tiles; i++) {
+        mosaic_check_window(m, level, &xy[2 * i], 1, wh[2 * i], wh[2 * i + 1], out_w, out_h, resample);
+        mosaic_window_device(m, level, &xy[2 * i], 1, wh[2 * i], wh[2 * i + 1], out_w, out_h, resample, one, s);
+        for (int b = 0; b < 3; b++)
+            HIP_CHECK(hipMemcpyAsync(out + ((size_t)b * n_tiles + i) * px, one + b * px, px * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+namespace {
+
+struct OverviewStep {
+    MosaicLevel dst;
+    std::vector<int32_t> xs, xc, ys, yc;
+    std::vector<float> xw, yw;   // xw tap-major [9][cols], yw [rows][9]
+};
+
+// the tables of one axis of one cascade step; the source pieces a block of `per_block` outputs reads must fit `cap`
+void overview_axis(int n_src, int n_out, int per_block, int cap, std::vector<int32_t>& start, std::vector<int32_t>& count, std::vector<float>& weights) {
+    start.resize((size_t)n_out);
+    count.resize((size_t)n_out);
+    weights.assign((size_t)n_out * kOvTaps, 0.0f);
+    const double ratio = (double)n_src / n_out;
+    const int need = conv_table(kCubic, n_src, 0.0, ratio, n_out, kOvTaps, start.data(), count.data(), weights.data());
+    APDS_REQUIRE(need <= kOvTaps, APDS_ERR_INTERNAL, "an overview footprint above 9 taps");
+    for (int g = 0; g < n_out; g += per_block) {
+        const int l = std::min(g + per_block, n_out) - 1;
+        APDS_REQUIRE(start[g] >= 0 && start[l] + count[l] <= n_src && start[l] + count[l] - start[g] <= cap, APDS_ERR_INTERNAL, "an overview block's source piece does not fit");
+    }
+}
+
+}  // namespace
+
+// Builds the overviews (once; under the handle's mutex): levels of factor 2, 4, ... while the level below exceeds min_size on either axis,
+// each from the one below, one fused launch per level. Returns the number of levels.
+int mosaic_build_overviews(Mosaic* m, int min_size) {
+    if (min_size <= 0) min_size = 512;   // the COG driver's block size
+    std::lock_guard<std::mutex> g(m->m);
+    if (m->ov_min_size) {
+        APDS_REQUIRE(m->ov_min_size == min_size, APDS_ERR_BAD_ARG, "the overviews have been built with another min_size");
+        return m->n_levels();
+    }
+    ThreadCtx& c = ctx();
+    APDS_REQUIRE(m->device == c.device, APDS_ERR_BAD_ARG, "the mosaic lives on another device than the calling thread's");
+    c.ws_reset();
+    hipStream_t s = c.stream;
+    std::vector<OverviewStep> steps;
+    try {
+        MosaicLevel prev = m->level(0);
+        while (prev.rows > min_size || prev.cols > min_size) {
+            steps.emplace_back();
+            OverviewStep& st = steps.back();
+            st.dst.rows = (prev.rows + 1) / 2;
+            st.dst.cols = (prev.cols + 1) / 2;
+            APDS_REQUIRE(ceil_div(st.dst.rows, kOvTy) <= 65535, APDS_ERR_BAD_ARG, "raster too tall for one launch");
+            overview_axis(prev.cols, st.dst.cols, kOvTx, kOvSrcW - 6, st.xs, st.xc, st.xw);
+            overview_axis(prev.rows, st.dst.rows, kOvTy, kOvSrcH, st.ys, st.yc, st.yw);
+            std::vector<float> t(st.xw.size());   // tap-major for the row pass
+            for (int i = 0; i < st.dst.cols; i++)
+                for (int k = 0; k < kOvTaps; k++) t[(size_t)k * st.dst.cols + i] = st.xw[(size_t)i * kOvTaps + k];
+            st.xw.swap(t);
+            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&st.dst.data), (size_t)3 * st.dst.rows * st.dst.cols * sizeof(float)));
+            prev = st.dst;
+        }
+        struct Dev {
+            const int *xs, *xc, *ys, *yc;
+            const float *xw, *yw;
+        };
+        std::vector<Dev> dev;
+        for (const OverviewStep& st : steps) dev.push_back(Dev{upload(c, st.xs, s), upload(c, st.xc, s), upload(c, st.ys, s), upload(c, st.yc, s), upload(c, st.xw, s), upload(c, st.yw, s)});
+        {
+            KernelTimer timer("mosaic_overviews", s);
+            prev = m->level(0);
+            for (size_t k = 0; k < steps.size(); k++) {
+                const MosaicLevel& d = steps[k].dst;
+                hipLaunchKernelGGL(mosaic_overview_kernel, dim3(ceil_div(d.cols, kOvTx), ceil_div(d.rows, kOvTy), 3), dim3(256), 0, s, (const float*)prev.data, prev.rows,
+                                   prev.cols, dev[k].xs, dev[k].xc, dev[k].xw, dev[k].ys, dev[k].yc, dev[k].yw, d.cols, d.rows, d.data);
+                HIP_CHECK(hipGetLastError());
+                prev = d;
+            }
+        }
+        HIP_CHECK(hipStreamSynchronize(s));   // the host tables are this call's locals
+    } catch (...) {
+        for (OverviewStep& st : steps)
+            if (st.dst.data) (void)hipFree(st.dst.data);
+        throw;
+    }
+    for (const OverviewStep& st : steps) m->overviews.push_back(st.dst);
+    m->ov_min_size = min_size;
+    return m->n_levels();
 }
 
 // per-band minimum and maximum, NaN ignored (a band of NaN only: NaN), computed once per handle
@@ -476,6 +712,7 @@ int apds_mosaic_destroy(void* mosaic) {
             (void)hipSetDevice(m->device);
             (void)hipDeviceSynchronize();   // another thread's window read may still be queued
             (void)hipFree(m->data);
+            for (const MosaicLevel& lv : m->overviews) (void)hipFree(lv.data);
             (void)hipSetDevice(ctx().device);
         }
         delete m;
@@ -507,21 +744,86 @@ int apds_resample_weights(int n_src, double offset, double span, int n_out, int 
     });
 }
 
+// host arithmetic only: no device is touched
+int apds_overview_weights(int n_src, int n_out, int max_taps, int32_t* start, int32_t* count, float* weights) {
+    int need = 0;
+    const int rc = guarded([&] {
+        APDS_REQUIRE(n_src > 0 && n_out > 0, APDS_ERR_ASSERT, "empty raster or output");
+        APDS_REQUIRE(n_out <= n_src, APDS_ERR_BAD_ARG, "an overview is not larger than its source");
+        const double ratio = (double)n_src / n_out;
+        APDS_REQUIRE(ratio <= 64.0, APDS_ERR_BAD_ARG, "n_src / n_out above 64 is not served");
+        need = conv_table(kCubic, n_src, 0.0, ratio, n_out, 0, nullptr, nullptr, nullptr);
+        if (max_taps == 0 && !start && !count && !weights) return;
+        APDS_REQUIRE(start && count && weights, APDS_ERR_BAD_ARG, "null output");
+        APDS_REQUIRE(max_taps >= need, APDS_ERR_BAD_ARG, "max_taps is smaller than the widest footprint");
+        std::fill(weights, weights + (size_t)n_out * max_taps, 0.0f);
+        conv_table(kCubic, n_src, 0.0, ratio, n_out, max_taps, start, count, weights);
+    });
+    return rc == APDS_OK ? need : rc;
+}
+
+int apds_mosaic_build_overviews(void* mosaic, int min_size, int* n_levels) {
+    APDS_RANGE("apds_mosaic_build_overviews");
+    return guarded([&] {
+        APDS_REQUIRE(mosaic, APDS_ERR_BAD_ARG, "null mosaic");
+        const int n = mosaic_build_overviews(static_cast<Mosaic*>(mosaic), min_size);
+        if (n_levels) *n_levels = n;
+    });
+}
+
+int apds_mosaic_level_info(const void* mosaic, int level, int* rows, int* cols) {
+    return guarded([&] {
+        const Mosaic* m = static_cast<const Mosaic*>(mosaic);
+        APDS_REQUIRE(m, APDS_ERR_BAD_ARG, "null mosaic");
+        APDS_REQUIRE(level >= 0 && level <= m->n_levels(), APDS_ERR_OUT_OF_RANGE, "the mosaic has no such overview level");
+        const MosaicLevel lv = m->level(level);
+        if (rows) *rows = lv.rows;
+        if (cols) *cols = lv.cols;
+    });
+}
+
+int apds_mosaic_best_level(const void* mosaic, int win_w, int win_h, int out_w, int out_h, int* level) {
+    return guarded([&] {
+        const Mosaic* m = static_cast<const Mosaic*>(mosaic);
+        APDS_REQUIRE(m && level, APDS_ERR_BAD_ARG, "null argument");
+        APDS_REQUIRE(win_w > 0 && win_h > 0 && out_w > 0 && out_h > 0, APDS_ERR_ASSERT, "empty window or output");
+        *level = mosaic_best_level(m, win_w, win_h, out_w, out_h);
+    });
+}
+
+namespace {
+
+// the window read of both entry points: `level` < 0 is the read of a base-raster window (mosaic_read_device)
+void window_to_host(const Mosaic* m, int level, int x0, int y0, int win_w, int win_h, int out_w, int out_h, int resample, float* out3) {
+    APDS_REQUIRE(out3, APDS_ERR_BAD_ARG, "null output");
+    const int32_t xy0[2] = {x0, y0};
+    mosaic_check_window(m, std::max(level, 0), xy0, 1, win_w, win_h, out_w, out_h, resample);
+    ThreadCtx& c = ctx();
+    c.ws_reset();
+    hipStream_t s = c.stream;
+    const size_t n = (size_t)3 * out_w * out_h;
+    float* d = c.alloc_n<float>(n);
+    if (level < 0)
+        mosaic_read_device(m, xy0, 1, win_w, win_h, out_w, out_h, resample, d, s);
+    else
+        mosaic_window_device(m, level, xy0, 1, win_w, win_h, out_w, out_h, resample, d, s);
+    HIP_CHECK(hipMemcpyAsync(out3, d, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+}  // namespace
+
 int apds_mosaic_window(void* mosaic, int x0, int y0, int win_w, int win_h, int out_w, int out_h, int resample, float* out3) {
     APDS_RANGE("apds_mosaic_window");
+    return guarded([&] { window_to_host(static_cast<const Mosaic*>(mosaic), -1, x0, y0, win_w, win_h, out_w, out_h, resample, out3); });
+}
+
+int apds_mosaic_window_level(void* mosaic, int level, int x0, int y0, int win_w, int win_h, int out_w, int out_h, int resample, float* out3) {
+    APDS_RANGE("apds_mosaic_window_level");
     return guarded([&] {
-        APDS_REQUIRE(out3, APDS_ERR_BAD_ARG, "null output");
-        const int32_t xy0[2] = {x0, y0};
-        const Mosaic* m = static_cast<const Mosaic*>(mosaic);
-        mosaic_check_window(m, xy0, 1, win_w, win_h, out_w, out_h, resample);
-        ThreadCtx& c = ctx();
-        c.ws_reset();
-        hipStream_t s = c.stream;
-        const size_t n = (size_t)3 * out_w * out_h;
-        float* d = c.alloc_n<float>(n);
-        mosaic_window_device(m, xy0, 1, win_w, win_h, out_w, out_h, resample, d, s);
-        HIP_CHECK(hipMemcpyAsync(out3, d, n * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
+        APDS_REQUIRE(mosaic, APDS_ERR_BAD_ARG, "null argument");
+        APDS_REQUIRE(level >= 0, APDS_ERR_OUT_OF_RANGE, "the mosaic has no such overview level");
+        window_to_host(static_cast<const Mosaic*>(mosaic), level, x0, y0, win_w, win_h, out_w, out_h, resample, out3);
     });
 }
 

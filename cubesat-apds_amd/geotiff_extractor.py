@@ -141,9 +141,14 @@ class MosaicedDataset:
         self.min_max = None
         self._device = None
 
-    def to_device(self):
-        """The same raster resident in HBM (DeviceMosaic): windows are resampled and extracted there."""
-        return DeviceMosaic(self.bands)
+    def to_device(self, overviews=False, min_size=512):
+        """The same raster resident in HBM (DeviceMosaic): windows are resampled and extracted there. overviews=True also builds the
+        pyramid a COG carries (DeviceMosaic.build_overviews), which window reads are then served from; this host class itself models the
+        read of a dataset without overviews."""
+        dm = DeviceMosaic(self.bands)
+        if overviews:
+            dm.build_overviews(min_size)
+        return dm
 
     @classmethod
     def import_mosaic_dataset(cls, path):
@@ -199,7 +204,9 @@ class MosaicedDataset:
 class DeviceMosaic:
     """The `MosaicedDataset` methods the preprocessor uses, on a [3, H, W] float32 raster resident in HBM (apds_mosaic_*): min/max is a
     device reduction, windows are resampled on the device (resample="nearest": the host mirror's rule bit for bit; "lanczos": the
-    reference's read_as(.., Lanczos), mod.rs:332-343), and the preprocessor extracts tiles from it without the bands crossing PCIe."""
+    reference's read_as(.., Lanczos), mod.rs:332-343), and the preprocessor extracts tiles from it without the bands crossing PCIe.
+    After build_overviews() the handle also holds the overview pyramid of the reference's COG (cubic, factor 2 per level), and every
+    window read is served from the level GDAL would pick."""
 
     def __init__(self, bands):
         b = np.asarray(bands)
@@ -242,8 +249,35 @@ class DeviceMosaic:
             self.min_max = BandsMinMax(*mm)
         return self.min_max
 
+    def build_overviews(self, min_size=512):
+        """Builds the overview levels (factor 2, 4, ... while the level below exceeds min_size on either axis) and returns how many there
+        are. Once per handle, before it is shared between threads; a repeat with the same min_size is a no-op."""
+        n = C.c_int(0)
+        check(lib().apds_mosaic_build_overviews(self.handle, int(min_size), C.byref(n)))
+        return n.value
+
+    def level_size(self, level):
+        """(width, height) of overview `level` (0: the raster itself)"""
+        rows, cols = C.c_int(0), C.c_int(0)
+        check(lib().apds_mosaic_level_info(self.handle, int(level), C.byref(rows), C.byref(cols)))
+        return cols.value, rows.value
+
+    def best_level(self, window_size, size):
+        """The level a read of window_size -> size is served from (0 without overviews)"""
+        level = C.c_int(0)
+        check(lib().apds_mosaic_best_level(self.handle, int(window_size[0]), int(window_size[1]), int(size[0]), int(size[1]), C.byref(level)))
+        return level.value
+
+    def window_level(self, level, window, window_size, size, resample="nearest"):
+        """`window` on the raster of overview `level`, in that level's own pixel coordinates: [3, size_h, size_w]"""
+        out = np.zeros((3, max(int(size[1]), 0), max(int(size[0]), 0)), np.float32)
+        check(lib().apds_mosaic_window_level(self.handle, int(level), int(window[0]), int(window[1]), int(window_size[0]), int(window_size[1]), int(size[0]),
+                                             int(size[1]), _lib.resample_mode(resample), ptr(out)))
+        return out
+
     def window(self, window, window_size, size, resample="nearest"):
-        """The three f32 band windows `to_rgb` merges, [3, size_h, size_w], resampled on the device."""
+        """The three f32 band windows `to_rgb` merges, [3, size_h, size_w], resampled on the device (on a handle with overviews: from the
+        level best_level gives)."""
         out = np.zeros((3, max(int(size[1]), 0), max(int(size[0]), 0)), np.float32)
         check(lib().apds_mosaic_window(self.handle, int(window[0]), int(window[1]), int(window_size[0]), int(window_size[1]), int(size[0]), int(size[1]),
                                        _lib.resample_mode(resample), ptr(out)))

@@ -176,6 +176,41 @@ int apds_mosaic_tile_extract(void* mosaic, int x0, int y0, int win_w, int win_h,
 int apds_mosaic_tile_extract_batch(void* mosaic, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample, const double* minmax6,
                                    int max_points, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes);
 
+/* The overview pyramid of the mosaic. The preprocessor opens its dataset as a COG (preprocessor/src/main.rs:142-161,
+ * geotiff_extractor/src/image_extractor/mod.rs:141-164), and a COG carries overviews: GDAL serves read_as(window, tile * 2^lod, tile, ..)
+ * from the overview of factor 2^lod, which the COG driver has built by CUBIC resampling, each level from the one below. These calls put
+ * that pyramid beside the raster (a third of its bytes) and route the window reads through it (restated from GDAL's
+ * behaviour, not pinned against it).
+ * Level k (k >= 1) has ceil(rows / 2^k) x ceil(cols / 2^k) pixels; levels are added while the level below exceeds min_size on either axis
+ * (min_size <= 0: 512, the COG block size). Level k is level k - 1 filtered by the convolution rule of apds_resample_weights with Keys'
+ * cubic (a = -0.5: W(x) = 1.5|x|^3 - 2.5|x|^2 + 1 for |x| <= 1, -0.5|x|^3 + 2.5|x|^2 - 4|x| + 2 for 1 < |x| < 2, else 0) over the whole
+ * axis: ratio = n(k-1) / n(k) in double (not 2 for an odd size), sw = 1 / ratio, radius = 2 / sw, taps clamped to the raster, weights
+ * divided by their sum and rounded once to f32; rows first, then columns, f32 fused multiply-adds in tap order; NaN propagates (no mask band).
+ *
+ * apds_overview_weights: the table of one axis of one such step, host arithmetic only. Outputs as apds_resample_weights. RETURNS the
+ * widest footprint (>= 1; at most 9 for n_out = ceil(n_src / 2)) or a negative status; max_taps = 0 with three null outputs computes only
+ * that. n_out > n_src or max_taps below the footprint: APDS_ERR_BAD_ARG. */
+int apds_overview_weights(int n_src, int n_out, int max_taps, int32_t* start, int32_t* count, float* weights);
+/* Builds the levels on the calling thread's device (the mosaic's, else APDS_ERR_BAD_ARG): one fused kernel launch per level. To be
+ * called once, before the handle is shared between threads; afterwards the handle is immutable again. A second call with the same
+ * min_size changes nothing and gives the same *n_levels (may be NULL); another min_size is APDS_ERR_BAD_ARG. apds_mosaic_destroy frees
+ * the levels; apds_mosaic_min_max stays a reduction over level 0. */
+int apds_mosaic_build_overviews(void* mosaic, int min_size, int* n_levels);
+/* Size of level 0 .. n_levels (0: the raster itself); any other level: APDS_ERR_OUT_OF_RANGE. */
+int apds_mosaic_level_info(const void* mosaic, int level, int* rows, int* cols);
+/* The level a read of win -> out is served from: the largest k with min(cols / cols_k, rows / rows_k) <= min(win_w / out_w, win_h / out_h),
+ * all in double; 0 without overviews or when the right-hand side is below 2. */
+int apds_mosaic_best_level(const void* mosaic, int win_w, int win_h, int out_w, int out_h, int* level);
+/* apds_mosaic_window on the raster of `level`, in that level's own pixel coordinates (level 0: apds_mosaic_window on a handle without
+ * overviews, exactly). A level the handle does not have, or a window outside the level: APDS_ERR_OUT_OF_RANGE.
+ *
+ * On a handle WITH overviews apds_mosaic_window, apds_mosaic_tile_extract and apds_mosaic_tile_extract_batch check the window against
+ * the base raster as before, pick k = apds_mosaic_best_level and, for k > 0, read the window's image on level k with the caller's mode:
+ * per axis fx = cols / cols_k, origin min(cols_k - 1, (int)(x0 / fx + 0.5)), extent max(1, (int)(win_w / fx + 0.5)) shortened to the
+ * level's edge. For a window of 2^k times the output size at an origin divisible by 2^k that is a copy of the overview. On a handle
+ * without overviews nothing changes. */
+int apds_mosaic_window_level(void* mosaic, int level, int x0, int y0, int win_w, int win_h, int out_w, int out_h, int resample, float* out3);
+
 /* homographier/src/homographier/mod.rs:271-300 warp_image_perspective: warpPerspective(src, M, size, INTER_LINEAR, BORDER_CONSTANT,
  * Scalar(1,1,1,1)). M (9 doubles) maps source to destination coordinates. The reference function is generic over the element type
  * (warp_image_perspective<T: DataType>): u8 elements with 1, 3 or 4 interleaved channels here (u8, Vec3b, Vec4b - the type the reference's

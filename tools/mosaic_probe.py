@@ -5,12 +5,18 @@
     (b) DeviceMosaic, nearest           - apds_mosaic_tile_extract_batch, the same rows bit for bit
     (c) DeviceMosaic, Lanczos           - the reference's read_as(.., Lanczos)
 
+and, with --overviews, a fourth:
+
+    (d) DeviceMosaic with overviews, Lanczos - the read of the reference's COG: level k of the cubic pyramid serves level of detail k
+
 with `--tile`-pixel tiles (the mosaic is cut as a 4-level pyramid, so --size 8192 gives 1024 x 1024 tiles: 64 + 16 + 4) and batch = all
 tiles of a level. Prints, per level and way: seconds (host clock around calls that end in a device synchronise), the resampling kernels'
 own time (hipEvents, apds_dev_last_kernel_ms "mosaic_resample"), the algorithmic bytes of the level (12 H W read + 12 H W / 4^lod
-written) over that time, and the keypoint count; last line: one JSON object with everything.
+written; way (d) copies an overview: 12 H W / 4^lod read and as much written) over that time, and the keypoint count; with --overviews
+also the build of the pyramid (host seconds and the kernels' own time on fresh handles, median, against 12 bytes per source pixel read
+plus 12 per destination pixel written, summed over the steps); last line: one JSON object with everything.
 
-    python tools/mosaic_probe.py --size 8192 --reps 2
+    python tools/mosaic_probe.py --size 8192 --reps 2 [--overviews]
 """
 import argparse
 import json
@@ -41,6 +47,7 @@ def main():
     ap.add_argument("--size", type=int, default=8192)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--levels", type=int, default=3)
+    ap.add_argument("--overviews", action="store_true", help="also build the overview pyramid and read the levels of detail from it (way d)")
     args = ap.parse_args()
     import torch  # noqa: F401  (its HIP runtime first, as bench.py does)
     pkg = graft.load_package()
@@ -65,7 +72,29 @@ def main():
     print(f"min/max: host nanmin/nanmax {t3 - t2:.3f} s | device call {t4 - t3:.4f} s, kernels {minmax_ms:.3f} ms = {n_bytes / minmax_ms / 1e6:.0f} GB/s of the {n_bytes / 1e9:.2f} GB read")
     amount = 4                                                                # tile = size / 8
     tile, _, _ = pp.tile_grid(host.raster_size(), amount, 0)
-    ways = (("a host nearest", host, "nearest"), ("b device nearest", dev, "nearest"), ("c device lanczos", dev, "lanczos"))
+    ways = [("a host nearest", host, "nearest"), ("b device nearest", dev, "nearest"), ("c device lanczos", dev, "lanczos")]
+    build = None
+    if args.overviews:
+        runs = []
+        for rep in range(args.reps + 1):                                      # a fresh handle each time: a handle builds once; rep 0 warms up
+            dev_ov = host.to_device()
+            pkg._lib.kernel_ms("mosaic_overviews")
+            s = time.perf_counter()
+            n_levels = dev_ov.build_overviews()
+            e = time.perf_counter()
+            ms, launches = pkg._lib.kernel_ms("mosaic_overviews")
+            if rep:
+                runs.append((e - s, ms, launches))
+            if rep < args.reps:
+                dev_ov.close()
+        sizes = [dev_ov.level_size(k) for k in range(n_levels + 1)]
+        algo = sum(12.0 * (sizes[k - 1][0] * sizes[k - 1][1] + sizes[k][0] * sizes[k][1]) for k in range(1, n_levels + 1))
+        ms = float(np.median([r[1] for r in runs]))
+        build = dict(levels=n_levels, sizes=sizes, seconds=float(np.median([r[0] for r in runs])), kernel_ms=ms, launches=runs[0][2], algorithmic_bytes=algo)
+        print(f"overviews: {n_levels} levels {' '.join('%dx%d' % s for s in sizes[1:])}, build call {build['seconds']:.4f} s, kernels ({runs[0][2]} launches) "
+              f"{ms:.3f} ms [{' '.join('%.3f' % r[1] for r in runs)}] = {algo / ms / 1e6:.0f} GB/s of the {algo / 1e9:.2f} GB read + written")
+        assert np.array_equal(dev_ov.datasets_min_max().as_array(), mm_dev)
+        ways.append(("d device overviews", dev_ov, "lanczos"))
     results = {w[0]: {lod: [] for lod in range(args.levels)} for w in ways}
     for rep in range(args.reps + 1):                                          # rep 0 warms every shape up and is not reported
         for name, ds, mode in ways:
@@ -82,16 +111,18 @@ def main():
             table.close()
     print(f"tiles of {tile[0]} x {tile[1]}, batch = all tiles of a level, {args.reps} timed repetitions after one warm-up (median shown)")
     for lod in range(args.levels):
-        algo = n_bytes * (1.0 + 0.25 ** lod)
         for name, _, _ in ways:
+            algo = n_bytes * (2.0 * 0.25 ** lod if name.startswith("d") else 1.0 + 0.25 ** lod)
             r = results[name][lod]
             sec = float(np.median([x["seconds"] for x in r]))
             ms = float(np.median([x["resample_ms"] for x in r]))
             rate = f"{algo / ms / 1e6:8.0f} GB/s of {algo / 1e9:.2f} GB" if ms > 0 else "       - (no resampling kernel)"
             print(f"lod {lod} {name:18s}: {r[0]['tiles']:3d} tiles {sec:8.3f} s  [{' '.join('%.3f' % x['seconds'] for x in r)}]  resample {ms:8.3f} ms {rate}  keypoints {r[0]['keypoints']}")
-    print(json.dumps(dict(size=args.size, tile=tile[0], reps=args.reps, minmax_ms=minmax_ms, host_minmax_s=t3 - t2, upload_s=t2 - t1,
+    print(json.dumps(dict(size=args.size, tile=tile[0], reps=args.reps, minmax_ms=minmax_ms, host_minmax_s=t3 - t2, upload_s=t2 - t1, overviews=build,
                           results={k: {str(l): v for l, v in d.items()} for k, d in results.items()})))
     dev.close()
+    if args.overviews:
+        dev_ov.close()
 
 
 if __name__ == "__main__":
