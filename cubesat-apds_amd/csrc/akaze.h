@@ -1,31 +1,13 @@
-// csrc/akaze.h — shared declarations of the AKAZE pipeline (filters, keypoint kernels, host driver).
+// csrc/akaze.h — shared declarations of the AKAZE pipeline: the launchers of the filter, suppression, compaction and descriptor files and the
+// extraction driver's hooks, grouped by the file that implements them. The host arithmetic (levels, launch plan, slab layout): akaze_plan.h.
 #pragma once
+#include "akaze_plan.h"
 #include "common.h"
 
 namespace apds {
 
-struct GaussTaps {
-    float k[5];   // k[0] centre, k[j] the two taps at distance j
-};
-
-static constexpr int AKAZE_MAX_LEVELS = 16;
-
-// One evolution level (mirrors OpenCV's MEvolution / the oracle's Level)
-struct LevelDesc {
-    int w, h, octave, sublevel, sigma_size, border;
-    float esigma, etime, ratio;
-    int nsteps;
-    float tau[64];
-    // device planes
-    float *Lt, *Ldet;
-    float2* Lxy;   // (Lx, Ly) interleaved
-    uint8_t* mask;      // extrema / suppression state
-    uint8_t* mask_aux;  // scratch copy for the suppression rounds
-    long long pix_offset;   // offset of this level in the level-major concatenated pixel index space
-};
-
 // Batched launches (gridDim.z = images): every image of a batch owns an identical workspace slab `bstride` bytes after the previous
-// one, so a plane of image blockIdx.z is the plane of image 0 shifted by blockIdx.z * bstride (akaze_keypoints.hip lays the slab
+// one, so a plane of image blockIdx.z is the plane of image 0 shifted by blockIdx.z * bstride (akaze_plan.h lays the slab
 // out). A single image is a batch of one (blockIdx.z = 0).
 #ifdef __HIPCC__
 template <class T>
@@ -101,6 +83,24 @@ inline int stream_band_rows(K kernel, int strips, int h, int batch, int want_row
     return std::max(rb, min_rows);
 }
 
+// akaze_suppress.hip: cross-level suppression. Makes the keypoint masks of ALL levels final (every level's Hessian kernel is done).
+void suppress_all_levels(const std::vector<LevelDesc>& ev, const SlabLayout& sl, hipStream_t s, const Batch& b);
+
+// akaze_compact.hip: sub-pixel refinement and ordered compaction (level-major, row-major).
+// All levels of every image of the batch: keypoints to kps + image * capacity (at most `capacity` each), the image's count to kp_base[1] of
+// its slab. APDS_KP_RANKED: the candidates place themselves; 0: two passes over the masks.
+void compact_all_levels(const LevelTable& T, const SlabLayout& sl, apds_keypoint* kps, int capacity, hipStream_t s, const Batch& b);
+// The keypoints of image `bi` (Tb: its level table, bstride 0), all n_all of them, then the `keep` strongest (response descending, ties by
+// detection order) to `out`. The masks are final and filtered: compact_all_levels has run.
+void compact_strongest(const LevelTable& Tb, const SlabLayout& sl, size_t slab_bytes, int bi, int n_all, int keep, apds_keypoint* out, hipStream_t s);
+
+// akaze_describe.hip: main orientation + M-LDB descriptor of keypoints [range[0], min(range[1], n_cap)) of every image (range: two ints of
+// image 0's slab) or, range == nullptr, of keypoints [0, n_cap). `blocks`: grid width (the kernels stride over the keypoints).
+void describe_keypoints(const LevelTable& T, apds_keypoint* kps, const int* range, int n_cap, size_t kp_bstride, uint8_t* desc64, size_t desc_bstride,
+                        int blocks, int batch, int xcd_ranges, hipStream_t s);
+void pack_desc61_device(const uint8_t* d64, int n, uint8_t* d61, hipStream_t s);
+
+// akaze_extract.hip (host driver: kernels.h declares akaze_extract_device)
 // Test hook: when armed (per thread) the next akaze_extract_device copies one intermediate plane to the host.
 // which: 0 Lt, 2 Lx, 3 Ly, 4 Ldet (f32), 7 keypoint mask after cross-level suppression (u8), 8 kcontrast (1 float)
 struct AkazeDebugRequest {
@@ -109,8 +109,5 @@ struct AkazeDebugRequest {
     void* host_out = nullptr;
 };
 AkazeDebugRequest& akaze_debug_request();
-
-// akaze_keypoints.hip (host driver: kernels.h declares akaze_extract_device)
-void pack_desc61_device(const uint8_t* d64, int n, uint8_t* d61, hipStream_t s);
 
 }  // namespace apds
