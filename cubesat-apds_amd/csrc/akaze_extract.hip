@@ -96,19 +96,19 @@ void zero_slab_heads(const Frame& f) {
 // difference. profiles/r03/doh_ab.txt)
 // (a stream of their own for the small levels' Hessian kernels, which queue up behind the large levels' on this one: measured, no gain)
 //
-// Two mechanisms. Events: hipEventRecord on the main stream where a level's Lsmooth exists, hipStreamWaitEvent on the Hessian stream. In a
+// The fork is an event: hipEventRecord on the main stream where a level's Lsmooth exists, hipStreamWaitEvent on the Hessian stream. In a
 // chain of short kernels an event recorded on the main stream costs 3.4 us each time (the marker packet sits between two dependent
 // kernels: tools/probes/fork_probe.hip, profiles/r04/fork_probe.txt - 16 forks: 236 us against 174 for the same kernels without any
-// dependency), and under rocprofv3 the timeline shows 5 us gaps behind every fork. APDS_FLAG_FORK=1 (round 4): the NEXT kernel of the chain
-// stores a sequence number as its first act (APDS_FORK_SIGNAL; it starts when its predecessor is done), and the Hessian stream waits for
-// that value (hipStreamWaitValue32 on 8 bytes of signal memory - a one-thread polling kernel of the runtime): nothing sits between the
-// chain's kernels (189 us in the probe). The wait is queued only AFTER the kernel that carries the value - every wait depends on something
-// submitted earlier, as with events, so no cycle of blocked hardware queues can form - which is why a level whose fork comes after its last
-// kernel hands its Hessian launch to the next level (deferred). A launcher that cannot carry a signal leaves it armed: a one-thread kernel
-// stores it then. MEASURED on the real frame: 1.635 against 1.641 ms over nine same-box rounds (profiles/r04/ab_env_flag_fork.txt) - the
-// chain's kernels are long and the marker is processed under the tail of the one before it; the 42 us the profiled timeline promises
-// (profiles/r04/timeline_flag_fork.txt) are the profiler's. Bit-identical, covered by tests/test_strip_kernels_gpu.py; off by default: 6 us
-// do not pay for a polling kernel per fork.
+// dependency), and under rocprofv3 the timeline shows 5 us gaps behind every fork.
+// (Round 4, measured and removed: the value fork - the next kernel of the chain stores a sequence number as its first act and the Hessian
+// stream waits for that value in signal memory, so that nothing sits between the chain's kernels: 189 us in the probe, but 1.635 against
+// 1.641 ms on the real frame over nine same-box rounds, profiles/r04/ab_env_flag_fork.txt - the chain's kernels are long and the marker is
+// processed under the tail of the one before it; the 42 us the profiled timeline promises, profiles/r04/timeline_flag_fork.txt, are the
+// profiler's. 6 us do not pay for a polling kernel per fork. DESIGN_HISTORY.md)
+// (Round 4, measured and removed: the early fork - level 0's Hessian kernel needs Lt[0] only and started after the fused base pass, beside
+// the contrast-factor pass: 1.649 / 1.656 / 1.642 against 1.649 / 1.636 / 1.636 ms, profiles/r04/ab_env_half_fuse.txt - the histogram
+// kernel the level chain waits for shares the machine with a kernel nothing waits for, and what the Hessian stream gains at the front it has
+// no use for at the back: its kernels follow the level chain from the second octave on.)
 class HessianFork {
   public:
     const bool on;   // the Hessian kernels go to a side stream
@@ -121,54 +121,33 @@ class HessianFork {
             c.fork_open = false;
         }
     }
-    // APDS_EARLY_FORK=1: level 0's Hessian kernel needs Lt[0] only and may start after the fused base pass, beside the contrast-factor pass.
-    // Measured three times in round 4 (profiles/r04/ab_env_half_fuse.txt: 1.649 / 1.656 / 1.642 against 1.649 / 1.636 / 1.636 ms): the
-    // histogram kernel the level chain waits for shares the machine with a kernel nothing waits for, and what the Hessian stream gains at the
-    // front it has no use for at the back (its kernels follow the level chain from the second octave on). Off by default.
-    void level0_ready_early() {
-        if (!on || !config().early_fork) return;
-        HIP_CHECK(hipEventRecord(c.fork_event(0), s));
-        early_forked = true;
-    }
-    // after the base stage: pick the side stream and the mechanism
+    // after the base stage: pick the side stream
     void open(const Frame& frame) {
         f = &frame;
         if (on) s_doh = side_stream_beside(s);
-        flag = on && config().flag_fork && c.fork_flag_ready();
-        c.fork_pending = ForkSignal{};
-        if (flag && c.fork_seq > 0x7FFF0000u) {   // (every earlier wait was joined: start the sequence again)
-            launch_fork_signal(ForkSignal{c.fork_flag, 0}, s);
-            c.fork_seq = 0;
-        }
     }
     // Lsmooth of level i exists from here on (level 0: Lt[0], ready after the base stage)
     void smooth_ready(int i) {
         if (!on) return;
         if (i == 0) c.fork_open = true;
-        if (flag) {
-            flush_deferred();   // the kernel just launched carried the previous level's signal
-            fork_value = c.arm_fork_signal().value;
-            return;
-        }
-        if (!(i == 0 && early_forked)) HIP_CHECK(hipEventRecord(c.fork_event(i), s));
+        HIP_CHECK(hipEventRecord(c.fork_event(i), s));
         HIP_CHECK(hipStreamWaitEvent(s_doh, c.fork_event(i), 0));
     }
     // a1.5 + a1.6 of level i: first / second derivatives, determinant, and the level's 3x3 extrema (mask + candidate list)
     void hessian(int i, const float* smooth) {
-        Deferred mine{i, smooth, 0, 0, fork_value};
-        deriv_weights(f->ev[i].sigma_size, mine.kside, mine.kmid);
-        if (!flag) {
-            launch(mine);
-        } else if (!c.fork_pending.flag) {   // a later kernel of this level has taken the signal: the Hessian kernel can be queued now
-            HIP_CHECK(hipStreamWaitValue32(s_doh, c.fork_flag, mine.value, hipStreamWaitValueGte, 0xFFFFFFFFu));
-            launch(mine);
-        } else {
-            deferred = mine;                 // the next level's first kernel will carry it
-        }
+        const LevelDesc& le = f->ev[i];
+        const SlabLayout& sl = f->sl;
+        float kside, kmid;
+        deriv_weights(le.sigma_size, kside, kmid);
+        uint8_t* mask = sl.mask_all + le.pix_offset;
+        if (!(i < f->n_strip_levels &&
+              launch_doh_strips(smooth, sl.Lxy[i], sl.Ldet[i], le.w, le.h, le.sigma_size, kside, kmid, le.border, AKAZE_DTHRESHOLD, mask, sl.status_all + le.pix_offset,
+                                sl.list[i], sl.list_count + i, s_doh, f->bt, f->dense_det)))
+            launch_doh_fused(smooth, sl.Lxy[i], sl.Ldet[i], le.w, le.h, le.sigma_size, kside, kmid, le.border, AKAZE_DTHRESHOLD, mask, sl.list[i], sl.list_count + i,
+                             s_doh, f->bt);
     }
     // everything after this point reads what the Hessian kernels wrote
     void join() {
-        if (flag) flush_deferred();
         if (!on) return;
         if (!c.join_event) HIP_CHECK(hipEventCreateWithFlags(&c.join_event, stream_event_flags()));
         HIP_CHECK(hipEventRecord(c.join_event, s_doh));
@@ -177,50 +156,23 @@ class HessianFork {
     }
 
   private:
-    struct Deferred {
-        int level;
-        const float* smooth;
-        float kside, kmid;
-        unsigned value;
-    };
     static bool decide() {
         const int fork_env = config().akaze_fork;
         return fork_env == 2 || (fork_env == 1 && live_contexts().load() <= 1);
-    }
-    void launch(const Deferred& d) {
-        const LevelDesc& le = f->ev[d.level];
-        const SlabLayout& sl = f->sl;
-        uint8_t* mask = sl.mask_all + le.pix_offset;
-        if (!(d.level < f->n_strip_levels &&
-              launch_doh_strips(d.smooth, sl.Lxy[d.level], sl.Ldet[d.level], le.w, le.h, le.sigma_size, d.kside, d.kmid, le.border, AKAZE_DTHRESHOLD, mask,
-                                sl.status_all + le.pix_offset, sl.list[d.level], sl.list_count + d.level, s_doh, f->bt, f->dense_det)))
-            launch_doh_fused(d.smooth, sl.Lxy[d.level], sl.Ldet[d.level], le.w, le.h, le.sigma_size, d.kside, d.kmid, le.border, AKAZE_DTHRESHOLD, mask,
-                             sl.list[d.level], sl.list_count + d.level, s_doh, f->bt);
-    }
-    void flush_deferred() {
-        if (deferred.level < 0) return;
-        launch_fork_signal(c.take_fork_signal(), s);   // (nothing if a chain kernel has taken it)
-        HIP_CHECK(hipStreamWaitValue32(s_doh, c.fork_flag, deferred.value, hipStreamWaitValueGte, 0xFFFFFFFFu));
-        launch(deferred);
-        deferred.level = -1;
     }
 
     ThreadCtx& c;
     const hipStream_t s;
     hipStream_t s_doh;
     const Frame* f = nullptr;
-    bool flag = false, early_forked = false;
-    Deferred deferred{-1, nullptr, 0, 0, 0};
-    unsigned fork_value = 0;
 };
 
 // ---- a1.1 / a1.2 / a1.3: gray, Lt[0] (= Lsmooth[0]) and the contrast factor of every octave
-void base_stage(const Frame& f, HessianFork& fork, const void* img, int channels, size_t stride) {
+void base_stage(const Frame& f, const void* img, int channels, size_t stride) {
     const SlabLayout& sl = f.sl;
     const int W = f.ev[0].w, H = f.ev[0].h, L = f.levels(), n_oct = f.ev.back().octave + 1;
     const GaussTaps g16 = gauss_taps(9, (double)AKAZE_SOFFSET), g10 = gauss_taps(5, 1.0);
     if (launch_base_strips(img, H, W, channels, stride, g16, g10, sl.Lt[0], sl.tmpF, sl.hmax_bits, L > 1, f.s, f.bt)) {   // large images: one fused pass
-        if (L > 1) fork.level0_ready_early();
         if (L > 1) launch_kcontrast(nullptr, sl.tmpF, W, H, sl.hmax_bits, sl.hist, sl.k_oct, n_oct, f.s, f.bt, /*gradient_done=*/true);
     } else {
         launch_gray(img, H, W, channels, stride, sl.gray, f.s, f.bt);
@@ -480,7 +432,7 @@ int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, i
     int* counts_dev = B > 1 ? c.alloc_n<int>(B) : nullptr;
 
     // ---- scale space: base stage, then the level chain with every level's Hessian kernel forked off it, joined at the end
-    base_stage(f, fork, img, channels, stride);
+    base_stage(f, img, channels, stride);
     fork.open(f);
     LevelChain chain{f, fork};
     for (int i = 0; i < L; i++) chain.step(i);

@@ -2,7 +2,9 @@
 // The defaults are the measured best; every switch keeps results bit-identical (the parity tests run the forced variants:
 // tests/test_strip_kernels_gpu.py). Round 3 folded 38 scattered getenv sites into this table (19 switches) and deleted the variants that had lost every
 // measurement: the persistent-grid match kernel, the staged keypoint pipeline, the 32- and 128-pixel Hessian tiles, and the tuning knobs
-// of the match's work-item plan (now constants in match_hamming.hip: plan_chunks).
+// of the match's work-item plan (now constants in match_hamming.hip: plan_chunks). Round 4 and the matrix-core matcher grew the table to 38;
+// round 4's two variants of the fork to the Hessian stream lost their measurements and are deleted as well (the value fork and the early
+// fork: HessianFork in akaze_extract.hip, DESIGN_HISTORY.md): 36 switches.
 #pragma once
 
 namespace apds {
@@ -20,7 +22,6 @@ struct Config {
     int doh_strip_rows;   // APDS_DOH_STRIP_ROWS  band height of that kernel (0 = chosen by level size); test hook
     int kp_ranked;        // APDS_KP_RANKED    1: candidates place themselves (default); 0: two passes over the masks
     int kp_xcd;           // APDS_KP_XCD       1: every XCD takes one contiguous eighth of the keypoints in the orientation / descriptor kernels (default); 0: blocks stride over all of them
-    int early_fork;       // APDS_EARLY_FORK   1: level 0's Hessian kernel may start as soon as the base pass is done, beside the contrast-factor pass; 0 (default): after it
     int half_fuse;        // APDS_HALF_FUSE    1: the launch that finishes an octave's last level also writes the next octave's start image (default); 0: half_sample_kernel
     int fed_shrink;       // APDS_FED_SHRINK   1: level_fused_kernel's FED steps skip the patches outside the zone the tile still depends on (default); 0: every step sweeps the whole region
     // ---- AKAZE extraction: scheduling
@@ -36,7 +37,6 @@ struct Config {
     int match_mfma_sample; // APDS_MATCH_MFMA_SAMPLE rows of the matrix-core matcher's threshold launch (at most a sixteenth of the set; 0: none)
     int match_mfma_splits; // APDS_MATCH_MFMA_SPLITS n > 0: that many train-row splits instead of the fill model's count (experiments)
     int match_mfma_xcd;   // APDS_MATCH_MFMA_XCD 1 (default): a multiple of eight train-row splits pinned to the XCDs when the fill model puts it within 5 % of its best count; 0: fill model alone
-    int flag_fork;        // APDS_FLAG_FORK    1: the Hessian stream waits for a value the main chain's next kernel stores; 0 (default): fork events
     int event_scope;      // APDS_EVENT_SCOPE  2: fork / join events without the system-scope fence (default); 1: the runtime's default event
     int debug_host_time;  // APDS_DEBUG_HOST_TIME  N > 0: print the host's enqueue time per extraction call every N calls (stderr)
     // ---- Hamming match

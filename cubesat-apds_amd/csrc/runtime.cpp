@@ -34,11 +34,9 @@ const Config& config() {
         k.kp_xcd = env("APDS_KP_XCD", 1);
         k.fed_shrink = env("APDS_FED_SHRINK", 1);
         k.half_fuse = env("APDS_HALF_FUSE", 1);
-        k.early_fork = env("APDS_EARLY_FORK", 0);
         k.akaze_fork = env("APDS_AKAZE_FORK", 1);
         k.side_probe = env("APDS_SIDE_PROBE", 1);
         k.event_scope = env("APDS_EVENT_SCOPE", 2);
-        k.flag_fork = env("APDS_FLAG_FORK", 0);
         k.match_mfma = env("APDS_MATCH_MFMA", 1);
         k.match_mfma_kmax = std::max(2, std::min(8, env("APDS_MATCH_MFMA_KMAX", 8)));
         k.match_mfma_xcd = env("APDS_MATCH_MFMA_XCD", 1);
@@ -193,26 +191,6 @@ void ThreadCtx::drop_side() {
     if (count_event) (void)hipEventDestroy(count_event);
     tail_event = count_event = nullptr;
     tail_pending = false;
-    if (fork_flag) (void)hipFree(fork_flag);
-    fork_flag = nullptr;
-    fork_flag_tried = false;
-    fork_seq = 0;
-    fork_pending = ForkSignal{};
-}
-
-bool ThreadCtx::fork_flag_ready() {
-    if (!fork_flag_tried) {
-        fork_flag_tried = true;
-        void* p = nullptr;
-        if (hipExtMallocWithFlags(&p, 8, hipMallocSignalMemory) == hipSuccess && p) {
-            fork_flag = static_cast<unsigned*>(p);
-            *reinterpret_cast<volatile unsigned long long*>(p) = 0;   // signal memory is host-visible
-            fork_seq = 0;
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    return fork_flag != nullptr;
 }
 
 // Events that order one GPU stream after another of the same device: no timing and no system-scope fence when the event completes.

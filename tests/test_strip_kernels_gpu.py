@@ -65,13 +65,25 @@ def test_akaze_parity_with_the_streaming_kernels_on_every_level(gpu_pkg):
     _rerun({"APDS_DOH_STRIP": "2", "APDS_DOH_STRIP_ROWS": "112", "APDS_LEVEL_STREAM": "2", "APDS_LEVEL_STREAM_ROWS": "100", "APDS_LEVEL_STRIP": "2", "APDS_LEVEL_FUSE": "0"})
 
 
-def test_akaze_parity_with_the_value_fork(gpu_pkg):
-    """APDS_FLAG_FORK=1: the Hessian stream waits for a sequence number that the next kernel of the level chain stores as its first act
-    (hipStreamWaitValue32) instead of for an event recorded between the chain's kernels; levels whose fork follows their last kernel defer
-    their Hessian launch to the next level. Every kernel family's launcher carries the signal here (streaming, strips, LDS-fused; the small
-    separate kernels take the one-thread fallback)."""
-    _rerun({"APDS_FLAG_FORK": "1"})
-    _rerun({"APDS_FLAG_FORK": "1", "APDS_LEVEL_FUSE": "0", "APDS_LEVEL_STRIP": "0", "APDS_LEVEL_STREAM": "0"})
+def test_akaze_parity_with_separate_launches_and_the_current_keypoint_kernels(gpu_pkg):
+    """separate smoothing / FED launches per level (no fused, strip or streaming level kernel) in front of the current keypoint and Hessian
+    kernels: the round-2 test above also turns off the ranked placement, the streaming Hessian kernel, the XCD split and the fused
+    half-sample."""
+    _rerun({"APDS_LEVEL_FUSE": "0", "APDS_LEVEL_STRIP": "0", "APDS_LEVEL_STREAM": "0"})
+
+
+def test_akaze_parity_with_the_hessian_fork_forced_off_and_on(gpu_pkg):
+    """APDS_AKAZE_FORK=0 (the Hessian kernels stay on the caller's stream) and 2 (always on the side stream), a child process each: by
+    default a thread forks only while it holds the process's one library context, so nothing else pins either path. The images of 96x640
+    up to 1024^2 and the batches up to 7 are the smallest with several octaves (one fork per level), a level >= 1 Mpx (the strip family), a
+    last level whose smoothing pass is separated only when forking, and a batch."""
+    for fork in ("0", "2"):
+        env = dict(os.environ, APDS_AKAZE_FORK=fork)
+        r = subprocess.run([sys.executable, "-m", "pytest", os.path.join("tests", "test_akaze_gpu.py"), "-k",
+                            "extraction_equals_oracle or batched_extraction_equals_oracle_per_image or odd_sizes_use_general_area_resize", "-q", "-m", "gpu",
+                            "-x", "-p", "no:cacheprovider"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, (fork, r.stdout[-3000:], r.stderr[-1000:])
+        assert " passed" in r.stdout and "failed" not in r.stdout
 
 
 def test_match_parity_on_the_vector_alu_matcher(gpu_pkg):
