@@ -76,9 +76,15 @@ __global__ void table_flags_kernel(const int* __restrict__ img, const int* __res
     flags[i] = f;
 }
 
-// ascending u64 key order == response descending, then row ascending (responses are positive floats)
+// ascending u64 key order == response descending, then row ascending, for every finite response and both infinities: the usual monotone
+// map of float bits (all bits flipped under a set sign, the sign bit set otherwise) ascends with the value, its complement descends.
+// -0.0 is made +0.0 first, so the two tie and fall to row order. A positive response gives ~bits with bit 31 cleared: the order among
+// positive responses is the one ~bits alone gave. The row is below 2^31, so the all-ones padding key stays strictly above every real key.
 __device__ __forceinline__ uint64_t order_key(float response, uint32_t row) {
-    return ((uint64_t)(~__float_as_uint(response)) << 32) | row;
+    uint32_t b = __float_as_uint(response);
+    if (b == 0x80000000u) b = 0;
+    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ((uint64_t)(~b) << 32) | row;
 }
 
 static constexpr int TB = 1024;
