@@ -1,5 +1,7 @@
 // csrc/akaze.h — shared declarations of the AKAZE pipeline: the launchers of the filter, suppression, compaction and descriptor files and the
-// extraction driver's hooks, grouped by the file that implements them. The host arithmetic (levels, launch plan, slab layout): akaze_plan.h.
+// extraction driver's hooks, grouped by the file that implements them. The host arithmetic (levels, slab layout, and which kernel family
+// serves the base stage and every level): akaze_plan.h. The filter launchers decide nothing: each launches the kernel the plan named and
+// APDS_REQUIREs what that kernel cannot do; band heights, grids, LDS sizes and template dispatch are theirs.
 #pragma once
 #include "akaze_plan.h"
 #include "common.h"
@@ -14,6 +16,18 @@ template <class T>
 __device__ __forceinline__ T* bofs(T* p, size_t bstride) {
     return p ? reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + (size_t)blockIdx.z * bstride) : p;
 }
+#endif
+
+// step sizes of one FED pass, by value to nld_multi_kernel, nld_strip_kernel and level_strip_kernel
+struct NldSteps {
+    float v[8];
+};
+// the register-strip FED kernels (nld_strip_kernel, level_strip_kernel): waves per SIMD the compiler is asked for, rows a wave finishes
+#ifndef APDS_STRIP_WAVES
+#define APDS_STRIP_WAVES 4
+#endif
+#ifndef APDS_STRIP_RB
+#define APDS_STRIP_RB 16
 #endif
 
 // level table handed to keypoint kernels by value (pointers: image 0 of the batch)
@@ -41,18 +55,22 @@ struct Batch {
 // akaze_filters.hip
 void launch_gray(const void* img, int rows, int cols, int channels, size_t stride, float* out, hipStream_t s, const Batch& b);
 void launch_gauss(const float* src, float* dst, int w, int h, const GaussTaps& taps, int radius, hipStream_t s, const Batch& b);
-void launch_smooth_flow(const float* src, float* smooth, float* flow, int w, int h, const GaussTaps& taps, const float* kptr, hipStream_t s, const Batch& b);
+// strips: the interior on register strips and the frame around it on LDS tiles (two launches), else LDS tiles throughout
+void launch_smooth_flow(const float* src, float* smooth, float* flow, int w, int h, const GaussTaps& taps, const float* kptr, hipStream_t s, const Batch& b,
+                        bool strips);
 void launch_kcontrast(const float* smooth, float* modg_tmp, int w, int h, unsigned int* hmax_bits, int* hist, float* k_oct, int n_oct, hipStream_t s,
                       const Batch& b, bool gradient_done = false);
-bool launch_base_strips(const void* img, int rows, int cols, int channels, size_t stride, const GaussTaps& g16, const GaussTaps& g10, float* Lt0, float* modg,
+void launch_base_strips(const void* img, int rows, int cols, int channels, size_t stride, const GaussTaps& g16, const GaussTaps& g10, float* Lt0, float* modg,
                         unsigned int* hmax_bits, bool want_modg, hipStream_t s, const Batch& b);
-bool launch_nld_multi(const float* Lt, const float* Lf, float* Lnew, int w, int h, const float* step_sizes, int nsteps, hipStream_t s, const Batch& b,
-                      float* half_out = nullptr);
-bool launch_level_strips(const float* src, float* smooth, float* flow_out, float* Lnew, int w, int h, const GaussTaps& taps, const float* kptr,
+// `nsteps` FED steps in one pass: register strips (1 .. 4 steps; half_out, optional: the 2 x 2 area means of Lnew as well, the next
+// octave's start image) or LDS tiles (1 .. 8 steps)
+void launch_nld_strips(const float* Lt, const float* Lf, float* Lnew, int w, int h, const float* step_sizes, int nsteps, hipStream_t s, const Batch& b,
+                       float* half_out = nullptr);
+void launch_nld_tiles(const float* Lt, const float* Lf, float* Lnew, int w, int h, const float* step_sizes, int nsteps, hipStream_t s, const Batch& b);
+void launch_level_strips(const float* src, float* smooth, float* flow_out, float* Lnew, int w, int h, const GaussTaps& taps, const float* kptr,
                          const float* step_sizes, int nsteps, hipStream_t s, const Batch& b);
-bool launch_level_stream(const float* src, float* smooth, float* flow_out, float* Lnew, int w, int h, const GaussTaps& taps, const float* kptr,
+void launch_level_stream(const float* src, float* smooth, float* flow_out, float* Lnew, int w, int h, const GaussTaps& taps, const float* kptr,
                          const float* step_sizes, int nsteps, hipStream_t s, const Batch& b, float* half_out = nullptr);
-int level_fused_max_steps();
 void launch_level_fused(const float* src, float* smooth, float* flow_out, const float* flow_in, float* Lnew, int w, int h, const GaussTaps& taps,
                         const float* kptr, const float* step_sizes, int nsteps, hipStream_t s, const Batch& b, float* half_out = nullptr);
 void launch_half_sample(const float* src, int sw, float* dst, int dw, int dh, hipStream_t s, const Batch& b);
@@ -62,9 +80,8 @@ void launch_doh_fused(const float* Lsmooth, float2* Lxy, float* Ldet, int w, int
                       uint32_t* list, int* list_count, hipStream_t s, const Batch& b);
 
 // akaze_doh_strips.hip: the streaming form of the same stage for the large levels; it also writes the mask and the suppression status of
-// every pixel of the level (so neither needs clearing). false = not a level for it (the caller launches doh_fused instead).
-bool doh_strips_eligible(int w, int h, int sc, int batch);
-bool launch_doh_strips(const float* Lsmooth, float2* Lxy, float* Ldet, int w, int h, int sc, float kside, float kmid, int border, float thr, uint8_t* mask,
+// every pixel of the level (so neither needs clearing).
+void launch_doh_strips(const float* Lsmooth, float2* Lxy, float* Ldet, int w, int h, int sc, float kside, float kmid, int border, float thr, uint8_t* mask,
                        uint8_t* status, uint32_t* list, int* list_count, hipStream_t s, const Batch& b, bool dense_det);
 
 // Band height of a streaming kernel (a wave walks a band of rows of one 64-column strip; 256-thread blocks = four waves): the waves of a

@@ -297,19 +297,10 @@ long long stream_wave_slots(const void* kernel, int dynamic_lds) {
     return slots;
 }
 
-// true: the level's (Lx, Ly), det, keypoint mask, suppression status (every pixel of the level: no zero fill needed) and candidate list are
-// on their way on `s`. false: not a level for this kernel (the caller takes doh_fused_kernel and clears mask / status itself).
-bool doh_strips_eligible(int w, int h, int sc, int batch) {
-    const int mode = config().doh_strip;
-    if (mode == 0 || sc < 2 || sc > 4 || w < 64 || h < 64) return false;
-    // 8 Mpx and more (the first octave of a 4096^2 frame): below that a level has too few 64-column strips to fill the chip with bands of
-    // a useful height (2048^2: 41 strips; bands of 16 rows spend half their walk on the 4 s + 2 warm-up rows) and the LDS tiles are quicker
-    return mode == 2 || (long long)w * h * batch >= (1ll << 23);
-}
-
-bool launch_doh_strips(const float* Lsmooth, float2* Lxy, float* Ldet, int w, int h, int sc, float kside, float kmid, int border, float thr, uint8_t* mask,
+// The level's (Lx, Ly), det, keypoint mask, suppression status (every pixel of the level: no zero fill needed) and candidate list.
+void launch_doh_strips(const float* Lsmooth, float2* Lxy, float* Ldet, int w, int h, int sc, float kside, float kmid, int border, float thr, uint8_t* mask,
                        uint8_t* status, uint32_t* list, int* list_count, hipStream_t s, const Batch& b, bool dense_det) {
-    if (!doh_strips_eligible(w, h, sc, b.n)) return false;
+    APDS_REQUIRE(sc >= 2 && sc <= 4 && w >= 64 && h >= 64, APDS_ERR_INTERNAL, "doh_strips: sigma_size 2..4, at least 64 x 64");
     const int vw = 64 - 4 * sc - 2;
     const int strips = ceil_div(w, vw);
     // band height (APDS_DOH_STRIP_ROWS: test hook): about 64 rows - a walk of 64 + 4 s + 2 rows - stretched so that the launch's waves fill the
@@ -329,7 +320,6 @@ bool launch_doh_strips(const float* Lsmooth, float2* Lxy, float* Ldet, int w, in
         case 3: hipLaunchKernelGGL(doh_strip_kernel<3>, grid, dim3(256), lds_pad, s, a, list, list_count, b.stride); break;
         default: hipLaunchKernelGGL(doh_strip_kernel<4>, grid, dim3(256), lds_pad, s, a, list, list_count, b.stride); break;
     }
-    return true;
 }
 
 }  // namespace apds

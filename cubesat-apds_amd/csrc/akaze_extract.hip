@@ -52,7 +52,7 @@ struct Frame {
     Batch bt;
     std::vector<LevelDesc> ev;
     SlabLayout sl;
-    int n_strip_levels = 0;   // the levels (a prefix of the list) whose Hessian kernel is the streaming one
+    ExtractionPlan plan;      // which kernels serve every level (akaze_plan.h)
     bool dense_det = false;   // the determinant plane of a level is stored whole only when somebody asked to see it (apds_akaze_debug_plane)
     int levels() const { return (int)ev.size(); }
 };
@@ -63,7 +63,8 @@ struct Frame {
 void zero_slab_heads(const Frame& f) {
     const SlabLayout& sl = f.sl;
     const int B = f.bt.n;
-    const size_t first = f.n_strip_levels < f.levels() ? (size_t)f.ev[f.n_strip_levels].pix_offset : (size_t)sl.total_pix;
+    const int n_strip = f.plan.n_strip_levels;
+    const size_t first = n_strip < f.levels() ? (size_t)f.ev[n_strip].pix_offset : (size_t)sl.total_pix;
     ZeroRanges zr{};
     zr.from[0] = 0;
     zr.bytes[0] = sl.mask_off;                                                   // counters (all planes start on 256-byte boundaries)
@@ -140,9 +141,10 @@ class HessianFork {
         float kside, kmid;
         deriv_weights(le.sigma_size, kside, kmid);
         uint8_t* mask = sl.mask_all + le.pix_offset;
-        if (!(i < f->n_strip_levels &&
-              launch_doh_strips(smooth, sl.Lxy[i], sl.Ldet[i], le.w, le.h, le.sigma_size, kside, kmid, le.border, AKAZE_DTHRESHOLD, mask, sl.status_all + le.pix_offset,
-                                sl.list[i], sl.list_count + i, s_doh, f->bt, f->dense_det)))
+        if (f->plan.level[i].doh_strips)
+            launch_doh_strips(smooth, sl.Lxy[i], sl.Ldet[i], le.w, le.h, le.sigma_size, kside, kmid, le.border, AKAZE_DTHRESHOLD, mask, sl.status_all + le.pix_offset,
+                              sl.list[i], sl.list_count + i, s_doh, f->bt, f->dense_det);
+        else
             launch_doh_fused(smooth, sl.Lxy[i], sl.Ldet[i], le.w, le.h, le.sigma_size, kside, kmid, le.border, AKAZE_DTHRESHOLD, mask, sl.list[i], sl.list_count + i,
                              s_doh, f->bt);
     }
@@ -168,51 +170,55 @@ class HessianFork {
 };
 
 // ---- a1.1 / a1.2 / a1.3: gray, Lt[0] (= Lsmooth[0]) and the contrast factor of every octave
-void base_stage(const Frame& f, const void* img, int channels, size_t stride) {
+void base_stage(const Frame& f, BaseStage kind, const void* img, int channels, size_t stride) {
     const SlabLayout& sl = f.sl;
     const int W = f.ev[0].w, H = f.ev[0].h, L = f.levels(), n_oct = f.ev.back().octave + 1;
     const GaussTaps g16 = gauss_taps(9, (double)AKAZE_SOFFSET), g10 = gauss_taps(5, 1.0);
-    if (launch_base_strips(img, H, W, channels, stride, g16, g10, sl.Lt[0], sl.tmpF, sl.hmax_bits, L > 1, f.s, f.bt)) {   // large images: one fused pass
-        if (L > 1) launch_kcontrast(nullptr, sl.tmpF, W, H, sl.hmax_bits, sl.hist, sl.k_oct, n_oct, f.s, f.bt, /*gradient_done=*/true);
-    } else {
-        launch_gray(img, H, W, channels, stride, sl.gray, f.s, f.bt);
-        launch_gauss(sl.gray, sl.Lt[0], W, H, g16, 4, f.s, f.bt);
-        if (L > 1) {
-            launch_gauss(sl.gray, sl.tmpS, W, H, g10, 2, f.s, f.bt);
-            launch_kcontrast(sl.tmpS, sl.tmpF, W, H, sl.hmax_bits, sl.hist, sl.k_oct, n_oct, f.s, f.bt);
-        }
+    switch (kind) {
+        case BaseStage::Strips:   // large images: one fused pass
+            launch_base_strips(img, H, W, channels, stride, g16, g10, sl.Lt[0], sl.tmpF, sl.hmax_bits, L > 1, f.s, f.bt);
+            if (L > 1) launch_kcontrast(nullptr, sl.tmpF, W, H, sl.hmax_bits, sl.hist, sl.k_oct, n_oct, f.s, f.bt, /*gradient_done=*/true);
+            break;
+        case BaseStage::Separate:
+            launch_gray(img, H, W, channels, stride, sl.gray, f.s, f.bt);
+            launch_gauss(sl.gray, sl.Lt[0], W, H, g16, 4, f.s, f.bt);
+            if (L > 1) {
+                launch_gauss(sl.gray, sl.tmpS, W, H, g10, 2, f.s, f.bt);
+                launch_kcontrast(sl.tmpS, sl.tmpF, W, H, sl.hmax_bits, sl.hist, sl.k_oct, n_oct, f.s, f.bt);
+            }
+            break;
     }
 }
 
-// ---- a1.4 / a1.5 per level: start image, Lsmooth -> the level's Hessian kernel, conductivity, FED passes ping-ponging into Lt[i]
+// ---- a1.4 / a1.5 per level, as the plan says: start image, a separate smoothing pass or a head that smooths (either makes the level's
+// Lsmooth, which its Hessian kernel waits for), FED passes ping-ponging into Lt[i], the Hessian kernel.
 // Round 4: the launch that finishes the last level of an octave also writes the next octave's start image (the 2 x 2 area means of its
 // Lt, into tmpH) when its kernel family can (level_stream, nld_strip, level_fused): half_sample_kernel - 40 + 14 + 5 us of passes over
 // finished planes on the critical path of a 4096^2 frame - then does not run. APDS_HALF_FUSE=0: always the separate kernel.
 struct LevelChain {
     const Frame& f;
     HessianFork& fork;
-    const float* fused_start = nullptr;   // set by level i - 1 when it wrote level i's start image
     const GaussTaps g10 = gauss_taps(5, 1.0);
 
     // the level's starting image: the previous level's Lt, or at the start of an octave its half-size image
     const float* start_image(int i, const LevelPlan& p) {
         const LevelDesc &e = f.ev[i], &prev = f.ev[i - 1];
         const SlabLayout& sl = f.sl;
-        const float* my_start = fused_start;
-        fused_start = nullptr;
-        if (e.octave == prev.octave) return sl.Lt[i - 1];
-        if (my_start) return my_start;   // written by the previous level's last launch
         float* dst = p.start_in_lt() ? sl.Lt[i] : sl.tmpP;
-        if (prev.w == 2 * e.w && prev.h == 2 * e.h) {
-            launch_half_sample(sl.Lt[i - 1], prev.w, dst, e.w, e.h, f.s, f.bt);
-        } else {
-            std::vector<int> xo, yo, xc, yc;
-            std::vector<float> xw, yw;
-            area_tables(prev.w, e.w, xo, xw, xc);
-            area_tables(prev.h, e.h, yo, yw, yc);
-            HIP_CHECK(hipStreamSynchronize(f.s));   // host tables must outlive the async copies
-            launch_area_resize(sl.Lt[i - 1], prev.w, dst, e.w, e.h, upload(xo, f.s), upload(xw, f.s), upload(xc, f.s), upload(yo, f.s), upload(yw, f.s), upload(yc, f.s), f.s, f.bt);
-            HIP_CHECK(hipStreamSynchronize(f.s));
+        switch (p.start) {
+            case Start::PrevLt: return sl.Lt[i - 1];
+            case Start::Written: return sl.tmpH;
+            case Start::HalfSample: launch_half_sample(sl.Lt[i - 1], prev.w, dst, e.w, e.h, f.s, f.bt); break;
+            case Start::AreaResize: {
+                std::vector<int> xo, yo, xc, yc;
+                std::vector<float> xw, yw;
+                area_tables(prev.w, e.w, xo, xw, xc);
+                area_tables(prev.h, e.h, yo, yw, yc);
+                HIP_CHECK(hipStreamSynchronize(f.s));   // host tables must outlive the async copies
+                launch_area_resize(sl.Lt[i - 1], prev.w, dst, e.w, e.h, upload(xo, f.s), upload(xw, f.s), upload(xc, f.s), upload(yo, f.s), upload(yw, f.s), upload(yc, f.s), f.s, f.bt);
+                HIP_CHECK(hipStreamSynchronize(f.s));
+                break;
+            }
         }
         return dst;
     }
@@ -222,72 +228,49 @@ struct LevelChain {
         const SlabLayout& sl = f.sl;
         const hipStream_t s = f.s;
         const Batch& bt = f.bt;
-        const int L = f.levels();
         if (i == 0) {
             fork.smooth_ready(0);
             fork.hessian(0, sl.Lt[0]);
             return;
         }
-        const LevelPlan p = plan_level(e, bt.n, config().level_fuse, config().level_strip, level_fused_max_steps());
-        // does the NEXT level start an octave from exactly half this level's size (the 2 x 2 mean; odd sizes take the general area resize)?
-        const bool want_half = config().half_fuse && i + 1 < L && f.ev[i + 1].octave > e.octave && e.w == 2 * f.ev[i + 1].w && e.h == 2 * f.ev[i + 1].h;
+        const LevelPlan& p = f.plan.level[i];
         const float* P = start_image(i, p);
         const float* kptr = sl.k_oct + e.octave;
         float* const smooth = sl.lsm[i];
         float st[32];
-        const float* in = P;
-        int pass = 0;
-        bool did_half = false, smooth_done = false;
-        // pass `q`: its step sizes into st, whether it finishes a level that should leave the next octave's start image, where it lands
+        // pass `q`: its step sizes into st, where it lands, whether it also leaves the next octave's start image
         struct Pass {
             int n;
             float* out;
             float* half_out;
         };
-        const auto prepare = [&e, &p, &sl, want_half, i](int q, float* st) {
+        const auto prepare = [&](int q) {
             for (int j = 0; j < p.steps[q]; j++) st[j] = e.tau[p.first[q] + j] * 0.5f;
-            return Pass{p.steps[q], p.lands_in_lt(q) ? sl.Lt[i] : sl.tmpP, want_half && p.first[q] + p.steps[q] == e.nsteps ? sl.tmpH : nullptr};
+            return Pass{p.steps[q], p.lands_in_lt(q) ? sl.Lt[i] : sl.tmpP, q == p.half_pass ? sl.tmpH : nullptr};
         };
-        // large levels: the smoothing pass and the first group of FED steps in one pass over register strips
-        if (p.try_strips) {
-            const Pass a = prepare(0, st);
-            float* flow = p.launches > 1 ? sl.tmpF : nullptr;
-            bool ran = false;
-            if (launch_level_stream(P, smooth, flow, a.out, e.w, e.h, g10, kptr, st, a.n, s, bt, a.half_out)) {
-                ran = true;
-                did_half = a.half_out != nullptr;
-            } else {
-                ran = launch_level_strips(P, smooth, flow, a.out, e.w, e.h, g10, kptr, st, a.n, s, bt);
-            }
-            if (ran) {
-                smooth_done = true;
-                in = a.out;
-                pass = 1;
-                fork.smooth_ready(i);
-            }
-        }
-        // the last level's Hessian kernel is on the critical path (nothing follows to hide it): its Lsmooth comes from a separate
-        // smoothing pass, so that it runs beside the level's FED steps
-        const bool smooth_first = !smooth_done && (!p.fused_level || (fork.on && i == L - 1));
+        const bool smooth_first = p.smooth != Smooth::None;
         if (smooth_first) {
-            launch_smooth_flow(P, smooth, sl.tmpF, e.w, e.h, g10, kptr, s, bt);   // Lsmooth and the conductivity in one pass
+            launch_smooth_flow(P, smooth, sl.tmpF, e.w, e.h, g10, kptr, s, bt, p.smooth == Smooth::Strips);   // Lsmooth and the conductivity in one pass
             fork.smooth_ready(i);
         }
-        // small levels: Lsmooth, conductivity and the first (usually all) FED steps in ONE launch (level_fused_kernel)
-        if (p.fused_level) {
-            const Pass a = prepare(0, st);
-            launch_level_fused(P, smooth, !smooth_first && a.n < e.nsteps ? sl.tmpF : nullptr, smooth_first ? sl.tmpF : nullptr, a.out, e.w, e.h, g10, kptr, st, a.n, s, bt, a.half_out);
-            did_half = did_half || a.half_out != nullptr;
-            in = a.out;
-            pass = 1;
+        const float* in = P;
+        if (p.head != Head::None) {
+            const Pass a = prepare(0);
+            float* flow = !smooth_first && p.launches > 1 ? sl.tmpF : nullptr;   // the conductivity, for the passes that follow
+            switch (p.head) {
+                case Head::Stream: launch_level_stream(P, smooth, flow, a.out, e.w, e.h, g10, kptr, st, a.n, s, bt, a.half_out); break;
+                case Head::Strips: launch_level_strips(P, smooth, flow, a.out, e.w, e.h, g10, kptr, st, a.n, s, bt); break;
+                default: launch_level_fused(P, smooth, flow, smooth_first ? sl.tmpF : nullptr, a.out, e.w, e.h, g10, kptr, st, a.n, s, bt, a.half_out); break;
+            }
             if (!smooth_first) fork.smooth_ready(i);
-        }
-        for (; pass < p.launches; pass++) {
-            const Pass a = prepare(pass, st);
-            if (launch_nld_multi(in, sl.tmpF, a.out, e.w, e.h, st, a.n, s, bt, a.half_out)) did_half = true;
             in = a.out;
         }
-        if (did_half) fused_start = sl.tmpH;
+        for (int q = p.first_fed_pass(); q < p.launches; q++) {
+            const Pass a = prepare(q);
+            if (p.strip_pass[q]) launch_nld_strips(in, sl.tmpF, a.out, e.w, e.h, st, a.n, s, bt, a.half_out);
+            else launch_nld_tiles(in, sl.tmpF, a.out, e.w, e.h, st, a.n, s, bt);
+            in = a.out;
+        }
         if (e.nsteps == 0 && P != sl.Lt[i])   // (never with AKAZE's parameters: every level but the first has FED steps)
             for (int bi = 0; bi < bt.n; bi++)
                 HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(sl.Lt[i]) + (size_t)bi * bt.stride, reinterpret_cast<const char*>(P) + (size_t)bi * bt.stride,
@@ -415,12 +398,15 @@ int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, i
     AkazeDebugRequest& dbg = akaze_debug_request();
     const int B = n_img;
 
-    // ---- plan: the evolution list (Allocate_Memory_Evolution) and whether the Hessian kernels fork
+    // ---- plan: the evolution list (Allocate_Memory_Evolution), whether the Hessian kernels fork, and which kernels serve every stage
     Frame f{c, s, Batch{}, akaze_levels(cols, rows), SlabLayout{}};
     const int L = f.levels();
     HessianFork fork(c, s);
     f.dense_det = dbg.armed;
-    while (f.n_strip_levels < L && doh_strips_eligible(f.ev[f.n_strip_levels].w, f.ev[f.n_strip_levels].h, f.ev[f.n_strip_levels].sigma_size, B)) f.n_strip_levels++;
+    const Config& cf = config();
+    const PlanSwitches sw{cf.nld_strip, cf.sf_strip, cf.base_strip, cf.level_strip, cf.level_fuse, cf.level_stream, cf.doh_strip, cf.half_fuse, fork.on};
+    f.plan = plan_extraction(f.ev, B, sw);
+    const BaseStage base = plan_base(rows, cols, channels, stride, reinterpret_cast<uintptr_t>(img), img_bstride, B, sw);
 
     // ---- slab: one per image, the same layout `bytes` apart
     f.sl.lay_out(nullptr, f.ev, fork.on);
@@ -432,7 +418,7 @@ int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, i
     int* counts_dev = B > 1 ? c.alloc_n<int>(B) : nullptr;
 
     // ---- scale space: base stage, then the level chain with every level's Hessian kernel forked off it, joined at the end
-    base_stage(f, img, channels, stride);
+    base_stage(f, base, img, channels, stride);
     fork.open(f);
     LevelChain chain{f, fork};
     for (int i = 0; i < L; i++) chain.step(i);

@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256) void deriv_pair_kernel(const float* __restrict
 #ifndef APDS_SF_THREADS
 #define APDS_SF_THREADS 1024
 #endif
-static constexpr int FW = 64, FH = 32, FNT = APDS_SF_THREADS;
+static constexpr int FW = SF_TILE_W, FH = SF_TILE_H, FNT = APDS_SF_THREADS;
 
 // Persistent blocks: each block walks a strided list of tiles of its XCD's band and issues the loads of its NEXT tile (into
 // registers) before it computes the current one, so the HBM latency of a tile hides behind the three LDS passes of the previous
@@ -648,9 +648,6 @@ __device__ __forceinline__ float nld_point(const float* __restrict__ st, const f
 // S FED steps in one pass: inputs are loaded with an S-pixel halo; step j is evaluated on the tile + (S - j) rings, ping-ponging
 // between two LDS planes; the last step writes the tile. Only positions inside the image are evaluated; a border pixel's
 // out-of-image neighbour is read (whatever LDS holds) but never used, exactly as in the single-step kernel.
-struct NldSteps {
-    float v[8];
-};
 
 // a point with all four neighbours inside the image: nld_point without the border cases (same expression, same order)
 __device__ __forceinline__ float nld_point_interior(const float* __restrict__ st, const float* __restrict__ sf, int c, int pitch, float step_size) {
@@ -780,8 +777,9 @@ struct LevelSteps {
     float v[32];
 };
 static constexpr int LFT = 32;              // output tile (square)
-static constexpr int LF_MAX_STEPS = 29;     // 1024 threads: 3 x 3 patches cover (32 + 2 * 29)^2; 3 planes x 96^2 floats = 108 KB of LDS
+static constexpr int LF_MAX_STEPS = 29;     // (the plan's LEVEL_FUSED_MAX_STEPS) 1024 threads: 3 x 3 patches cover (32 + 2 * 29)^2; 3 planes x 96^2 floats = 108 KB of LDS
 static constexpr int LF_MAX_STEPS_512 = 17; // 512 threads: 3 x 3 patches cover (32 + 2 * 17)^2
+static_assert(LF_MAX_STEPS == LEVEL_FUSED_MAX_STEPS, "the plan gives level_fused_kernel as many steps as it holds");
 
 __device__ __forceinline__ int div_small(int i, float inv) { return (int)(((float)i + 0.5f) * inv); }   // floor(i / d): exact for i < 2^15, d < 2^7
 
@@ -1155,12 +1153,6 @@ __device__ __forceinline__ void nld_strip(const float* __restrict__ Lt, const fl
 }
 
 template <int S, int RB, bool HALF = false>
-#ifndef APDS_STRIP_WAVES
-#define APDS_STRIP_WAVES 4
-#endif
-#ifndef APDS_STRIP_RB
-#define APDS_STRIP_RB 16
-#endif
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(APDS_STRIP_WAVES, 8))) void nld_strip_kernel(const float* __restrict__ Lt, const float* __restrict__ Lf, float* __restrict__ Lnew, int w, int h,
                                                          NldSteps steps, int strips, int nwaves, size_t bstride, float* __restrict__ half) {
     APDS_RAISE_WAVE_PRIORITY();
@@ -1415,14 +1407,14 @@ void launch_gauss(const float* src, float* dst, int w, int h, const GaussTaps& t
 
 static size_t deriv_lds_bytes(int s) { return (size_t)((TH + 2 * s) * (TW + 2 * s) + 2 * (TH + 2 * s) * TW) * sizeof(float); }
 
-void launch_smooth_flow(const float* src, float* smooth, float* flow, int w, int h, const GaussTaps& taps, const float* kptr, hipStream_t s, const Batch& b) {
+void launch_smooth_flow(const float* src, float* smooth, float* flow, int w, int h, const GaussTaps& taps, const float* kptr, hipStream_t s, const Batch& b,
+                        bool strips_on) {
     const int tiles_x = ceil_div(w, FW), tiles_y = ceil_div(h, FH), ntiles = tiles_x * tiles_y;
     // tiles [1, txi) x [1, tyi) lie inside the image with their 3-pixel halo: register strips; the frame around them: LDS tiles
-    const int strip_mode = config().sf_strip;
-    const int txi = w >= FW + 67 ? (w - 67) / FW + 1 : 1, tyi = h >= FH + 35 ? (h - 35) / FH + 1 : 1;
-    // the strips pay once the launch has enough pixels to be throughput-bound: a batch counts as a whole
-    const bool strips_on = strip_mode && txi > 1 && tyi > 1 && (size_t)w * h < ((size_t)1 << 29) && ((size_t)w * h * b.n >= ((size_t)1 << 21) || strip_mode == 2);
+    int txi, tyi;
+    smooth_flow_interior(w, h, txi, tyi);
     if (strips_on) {
+        APDS_REQUIRE(txi > 1 && tyi > 1 && fits_32bit_offsets(w, h), APDS_ERR_INTERNAL, "smooth_flow strips: an interior tile, 32-bit offsets");
         const int rx0 = FW, ry0 = FH, rx1 = txi * FW, ry1 = tyi * FH;
         const int strips = ceil_div(rx1 - rx0, SF_VW), nwaves = strips * ceil_div(ry1 - ry0, SF_RB);
         hipLaunchKernelGGL(smooth_flow_strip_kernel, dim3(ceil_div(nwaves, 4), 1, b.n), dim3(256), 0, s, src, smooth, flow, w, h, taps, kptr, rx0, ry0, rx1, ry1,
@@ -1448,14 +1440,11 @@ void launch_kcontrast(const float* smooth, float* modg_tmp, int w, int h, unsign
     hipLaunchKernelGGL(kcontrast_hist_kernel<16>, dim3(hist_blocks, 1, b.n), dim3(256), 0, s, modg_tmp, w, h, hmax_bits, hist, b.stride);
     hipLaunchKernelGGL(kcontrast_finish_kernel, dim3(1, 1, b.n), dim3(64), 0, s, hist, hmax_bits, w, h, k_oct, n_oct, b.stride);
 }
-// image -> Lt[0] (and, if want_modg, |grad| of the sigma = 1 image + its interior maximum) in one pass on register strips. Returns
-// false when the image is too small to pay (the launch-bound small tiles keep the separate kernels) or does not fit 32-bit offsets.
-bool launch_base_strips(const void* img, int rows, int cols, int channels, size_t stride, const GaussTaps& g16, const GaussTaps& g10, float* Lt0, float* modg,
+// image -> Lt[0] (and, if want_modg, |grad| of the sigma = 1 image + its interior maximum) in one pass on register strips
+void launch_base_strips(const void* img, int rows, int cols, int channels, size_t stride, const GaussTaps& g16, const GaussTaps& g10, float* Lt0, float* modg,
                         unsigned int* hmax_bits, bool want_modg, hipStream_t s, const Batch& b) {
-    const int strip_mode = config().base_strip;
-    const size_t px = (size_t)rows * cols;
-    if (!strip_mode || (px * b.n < ((size_t)1 << 21) && strip_mode != 2) || px >= ((size_t)1 << 29) || (size_t)rows * stride >= ((size_t)1 << 31)) return false;
-    if (channels == 4 && ((reinterpret_cast<uintptr_t>(img) | stride | b.img_stride) & 3)) return false;   // dword loads of the BGRA pixels
+    APDS_REQUIRE((size_t)rows * cols < ((size_t)1 << 29) && (size_t)rows * stride < ((size_t)1 << 31), APDS_ERR_INTERNAL, "base_strips: 32-bit offsets");
+    APDS_REQUIRE(channels != 4 || ((reinterpret_cast<uintptr_t>(img) | stride | b.img_stride) & 3) == 0, APDS_ERR_INTERNAL, "base_strips: dword loads of the BGRA pixels");
     const int strips = ceil_div(cols, BS_VW), nwaves = strips * ceil_div(rows, BS_RB);
     auto go = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(ceil_div(nwaves, 4), 1, b.n), dim3(256), 0, s, static_cast<const uint8_t*>(img), cols, rows, (int)stride, g16, g10, Lt0,
@@ -1464,7 +1453,6 @@ bool launch_base_strips(const void* img, int rows, int cols, int channels, size_
     if (channels == 4) go(&base_strip_kernel<4>);
     else if (channels == 3) go(&base_strip_kernel<3>);
     else go(&base_strip_kernel<1>);
-    return true;
 }
 template <int S>
 static void nld_multi_launch(const float* Lt, const float* Lf, float* Lnew, int w, int h, const NldSteps& st, hipStream_t s, const Batch& b) {
@@ -1481,24 +1469,22 @@ static void nld_strip_launch(const float* Lt, const float* Lf, float* Lnew, int 
     else
         hipLaunchKernelGGL((nld_strip_kernel<S, RB, false>), dim3(ceil_div(nwaves, 4), 1, b.n), dim3(256), 0, s, Lt, Lf, Lnew, w, h, st, strips, nwaves, b.stride, (float*)nullptr);
 }
-// half_out (optional): ask the launch to write the 2 x 2 area means of Lnew as well (the next octave's start image). Returns whether it did
-// (the register-strip form can; the LDS-tile form of the small launches cannot: the caller then runs half_sample_kernel).
-bool launch_nld_multi(const float* Lt, const float* Lf, float* Lnew, int w, int h, const float* step_sizes, int nsteps, hipStream_t s, const Batch& b,
-                      float* half_out) {
+void launch_nld_strips(const float* Lt, const float* Lf, float* Lnew, int w, int h, const float* step_sizes, int nsteps, hipStream_t s, const Batch& b,
+                       float* half_out) {
+    APDS_REQUIRE(nsteps >= 1 && nsteps <= 4 && fits_32bit_offsets(w, h), APDS_ERR_INTERNAL, "nld_strips: 1..4 steps per launch, 32-bit offsets");
     NldSteps st{};
     for (int i = 0; i < nsteps; i++) st.v[i] = step_sizes[i];
-    // register strips for the throughput-bound launches (up to 4 steps on launches of at least 1 Mpx, a batch counted as a whole);
-    // the LDS tiles keep the deeply fused launches of the small, latency-bound octaves (their unrolled strip code would not fit the
-    // instruction cache)
-    const int strip_mode = config().nld_strip;
-    if (strip_mode && nsteps <= 4 && ((size_t)w * h * b.n >= ((size_t)1 << 20) || strip_mode == 2) && (size_t)w * h < ((size_t)1 << 29)) {   // 32-bit byte offsets
-        switch (nsteps) {
-            case 1: nld_strip_launch<1>(Lt, Lf, Lnew, w, h, st, s, b, half_out); return half_out != nullptr;
-            case 2: nld_strip_launch<2>(Lt, Lf, Lnew, w, h, st, s, b, half_out); return half_out != nullptr;
-            case 3: nld_strip_launch<3>(Lt, Lf, Lnew, w, h, st, s, b, half_out); return half_out != nullptr;
-            default: nld_strip_launch<4>(Lt, Lf, Lnew, w, h, st, s, b, half_out); return half_out != nullptr;
-        }
+    switch (nsteps) {
+        case 1: nld_strip_launch<1>(Lt, Lf, Lnew, w, h, st, s, b, half_out); break;
+        case 2: nld_strip_launch<2>(Lt, Lf, Lnew, w, h, st, s, b, half_out); break;
+        case 3: nld_strip_launch<3>(Lt, Lf, Lnew, w, h, st, s, b, half_out); break;
+        default: nld_strip_launch<4>(Lt, Lf, Lnew, w, h, st, s, b, half_out); break;
     }
+}
+void launch_nld_tiles(const float* Lt, const float* Lf, float* Lnew, int w, int h, const float* step_sizes, int nsteps, hipStream_t s, const Batch& b) {
+    APDS_REQUIRE(nsteps >= 1 && nsteps <= 8, APDS_ERR_INTERNAL, "nld_multi: 1..8 steps per launch");
+    NldSteps st{};
+    for (int i = 0; i < nsteps; i++) st.v[i] = step_sizes[i];
     switch (nsteps) {
         case 1: nld_multi_launch<1>(Lt, Lf, Lnew, w, h, st, s, b); break;
         case 2: nld_multi_launch<2>(Lt, Lf, Lnew, w, h, st, s, b); break;
@@ -1507,14 +1493,11 @@ bool launch_nld_multi(const float* Lt, const float* Lf, float* Lnew, int w, int 
         case 5: nld_multi_launch<5>(Lt, Lf, Lnew, w, h, st, s, b); break;
         case 6: nld_multi_launch<6>(Lt, Lf, Lnew, w, h, st, s, b); break;
         case 7: nld_multi_launch<7>(Lt, Lf, Lnew, w, h, st, s, b); break;
-        case 8: nld_multi_launch<8>(Lt, Lf, Lnew, w, h, st, s, b); break;
-        default: fail(APDS_ERR_INTERNAL, "nld_multi: 1..8 steps per launch");
+        default: nld_multi_launch<8>(Lt, Lf, Lnew, w, h, st, s, b); break;
     }
-    return false;
 }
 // one launch for a level: Lsmooth, conductivity (kept in LDS; written to flow_out only if the caller continues with more steps)
-// and `nsteps` <= level_fused_max_steps() FED steps from `src` into `Lnew` (src, smooth, Lnew distinct planes)
-int level_fused_max_steps() { return LF_MAX_STEPS; }
+// and `nsteps` <= LF_MAX_STEPS FED steps from `src` into `Lnew` (src, smooth, Lnew distinct planes)
 void launch_level_fused(const float* src, float* smooth, float* flow_out, const float* flow_in, float* Lnew, int w, int h, const GaussTaps& taps,
                         const float* kptr, const float* step_sizes, int nsteps, hipStream_t s, const Batch& b, float* half_out) {
     APDS_REQUIRE(nsteps >= 1 && nsteps <= LF_MAX_STEPS, APDS_ERR_INTERNAL, "level_fused: 1..29 steps");

@@ -223,13 +223,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     else level_stream_rows<S, false, false, FLOW_OUT, HALF>(a, strip, band);
 }
 
-// Lsmooth, conductivity and the level's first `nsteps` (1 .. 4) FED steps, streaming form. False: not a level for it (the caller takes
-// level_strip_kernel).
-bool launch_level_stream(const float* src, float* smooth, float* flow_out, float* Lnew, int w, int h, const GaussTaps& taps, const float* kptr,
+// Lsmooth, conductivity and the level's first `nsteps` (1 .. 4) FED steps, streaming form.
+void launch_level_stream(const float* src, float* smooth, float* flow_out, float* Lnew, int w, int h, const GaussTaps& taps, const float* kptr,
                          const float* step_sizes, int nsteps, hipStream_t s, const Batch& b, float* half_out) {
-    const int mode = config().level_stream;
-    if (mode == 0 || nsteps < 1 || nsteps > 4 || (size_t)w * h >= ((size_t)1 << 29) || w < 64 || h < 32) return false;
-    if (mode != 2 && (size_t)w * h * b.n < ((size_t)1 << 23)) return false;
+    APDS_REQUIRE(nsteps >= 1 && nsteps <= 4 && fits_32bit_offsets(w, h) && w >= 64 && h >= 32, APDS_ERR_INTERNAL, "level_stream: 1..4 steps, 32-bit offsets, at least 64 x 32");
     const int H = nsteps + 3, vw = 64 - 2 * H;
     const int strips = ceil_div(w, vw);
     LevelStreamArgs a{src, smooth, flow_out, Lnew, half_out, kptr, w, h, strips, 0, 0, taps, {}};
@@ -265,7 +262,6 @@ bool launch_level_stream(const float* src, float* smooth, float* flow_out, float
             default: go(&level_stream_kernel<4, false>); break;
         }
     }
-    return true;
 }
 
 }  // namespace apds

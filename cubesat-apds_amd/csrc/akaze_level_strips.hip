@@ -19,15 +19,6 @@ __device__ __forceinline__ float dpp_prev(float v) {   // lane i <- lane i - 1
 }
 __device__ __forceinline__ float dpp_from_next_lane(float v) { return dpp_next(v); }   // wave_shl:1 (lane 63: unspecified, a halo lane)
 __device__ __forceinline__ float dpp_from_prev_lane(float v) { return dpp_prev(v); }   // wave_shr:1 (lane 0: unspecified, a halo lane)
-struct NldSteps {
-    float v[8];
-};
-#ifndef APDS_STRIP_WAVES
-#define APDS_STRIP_WAVES 4
-#endif
-#ifndef APDS_STRIP_RB
-#define APDS_STRIP_RB 16
-#endif
 #ifndef APDS_STRIP_WIDE_FROM
 #define APDS_STRIP_WIDE_FROM 3   // level_strip_kernel<S> with S >= this may use up to 168 VGPRs (three waves per SIMD) instead of spilling at 128
 #endif
@@ -190,7 +181,7 @@ void level_strip_kernel(const float* __restrict__ src, float* __restrict__ smoot
 }
 
 // Lsmooth, conductivity and the level's first `nsteps` (1 .. 4) FED steps on register strips, borders included: src -> smooth, Lnew
-// (and flow_out when the caller continues with more steps). False when the level does not fit 32-bit byte offsets.
+// (and flow_out when the caller continues with more steps).
 template <int S>
 static void level_strip_launch(const float* src, float* smooth, float* flow_out, float* Lnew, int w, int h, const GaussTaps& taps, const float* kptr,
                                const NldSteps& st, hipStream_t s, const Batch& b) {
@@ -202,9 +193,9 @@ static void level_strip_launch(const float* src, float* smooth, float* flow_out,
     else
         hipLaunchKernelGGL((level_strip_kernel<S, RB, false>), grid, dim3(256), 0, s, src, smooth, flow_out, Lnew, w, h, taps, kptr, st, strips, nwaves, b.stride);
 }
-bool launch_level_strips(const float* src, float* smooth, float* flow_out, float* Lnew, int w, int h, const GaussTaps& taps, const float* kptr,
+void launch_level_strips(const float* src, float* smooth, float* flow_out, float* Lnew, int w, int h, const GaussTaps& taps, const float* kptr,
                          const float* step_sizes, int nsteps, hipStream_t s, const Batch& b) {
-    if (nsteps < 1 || nsteps > 4 || (size_t)w * h >= ((size_t)1 << 29) || w < 2 || h < 2) return false;
+    APDS_REQUIRE(nsteps >= 1 && nsteps <= 4 && fits_32bit_offsets(w, h) && w >= 2 && h >= 2, APDS_ERR_INTERNAL, "level_strips: 1..4 steps, 32-bit offsets, at least 2 x 2");
     NldSteps st{};
     for (int i = 0; i < nsteps; i++) st.v[i] = step_sizes[i];
     switch (nsteps) {
@@ -213,7 +204,6 @@ bool launch_level_strips(const float* src, float* smooth, float* flow_out, float
         case 3: level_strip_launch<3>(src, smooth, flow_out, Lnew, w, h, taps, kptr, st, s, b); break;
         default: level_strip_launch<4>(src, smooth, flow_out, Lnew, w, h, taps, kptr, st, s, b); break;
     }
-    return true;
 }
 
 }  // namespace apds

@@ -1,6 +1,7 @@
 // csrc/akaze_plan.h — the host arithmetic of an AKAZE extraction: what is decided before the first launch. Plain C++17 without a GPU
 // (tests/cpp/akaze_plan_host.cpp compiles it with g++): the evolution list, the FED step sizes, the Gaussian and INTER_AREA tap tables, the
-// derivative weights, how many launches a level's FED steps take and where each pass lands, and the layout of one image's workspace slab.
+// derivative weights, which kernel family serves the base stage and every level (plan_extraction: the table the driver executes), how many
+// launches a level's FED steps take and where each pass lands, and the layout of one image's workspace slab.
 //
 // Replaces OpenCV AKAZEFeatures::Allocate_Memory_Evolution, fed_tau_by_process_time, getGaussianKernel, the tap tables of resize(INTER_AREA)
 // and compute_derivative_kernels (the Scharr weights of a scaled 3 x 3 stencil).
@@ -159,24 +160,59 @@ inline void deriv_weights(int sc, float& kside, float& kmid) {
     }
 }
 
-// ---- how a level's FED steps are launched -----------------------------------------------------------------------------------------------
+// ---- which kernels serve an extraction ---------------------------------------------------------------------------------------------------
+// Everything that picks a kernel family is decided here, before the first launch: plan_extraction (per level: Hessian kernel, start image,
+// smoothing pass, head, FED passes, who writes the next octave's start image) and plan_base (the base stage). The driver
+// (akaze_extract.hip) executes the table; a launcher launches what it is told and APDS_REQUIREs what its kernel cannot do.
+//
 // FED steps are issued in fused groups of up to `fuse` steps (temporal blocking in LDS): `launches` passes ping-pong between the level's Lt
 // and a scratch plane and must end in Lt. Deeper fusion for the small octaves, whose launches are latency-bound. Small levels do Lsmooth,
-// the conductivity and the first (usually all) steps in ONE launch (level_fused_kernel, up to `fused_max_steps` steps: pass 0); large
+// the conductivity and the first (usually all) steps in ONE launch (level_fused_kernel, up to LEVEL_FUSED_MAX_STEPS steps: pass 0); large
 // levels may do the smoothing pass and pass 0 in one pass over register strips (level_stream_kernel / level_strip_kernel, up to 4 steps).
-// The steps are spread evenly over the passes that follow (e.g. 11 steps, fuse 8 -> 6 + 5).
+// Such a pass 0 is the level's HEAD. The steps are spread evenly over the passes that follow (e.g. 11 steps, fuse 8 -> 6 + 5).
+
+// The values of the switches (config.h) that the plan depends on - 0 never, 1 by size, 2 always - and whether the Hessian kernels fork.
+struct PlanSwitches {
+    int nld_strip = 1, sf_strip = 1, base_strip = 1, level_strip = 1, level_fuse = 1, level_stream = 1, doh_strip = 1, half_fuse = 1;
+    bool fork = false;
+};
+
+static constexpr int LEVEL_FUSED_MAX_STEPS = 29;      // level_fused_kernel's capacity (akaze_filters.hip asserts its LF_MAX_STEPS against it)
+static constexpr int SF_TILE_W = 64, SF_TILE_H = 32;  // smooth_flow_kernel's tile
+
+enum class Head { None, Stream, Strips, Fused };      // pass 0 with the smoothing in it: level_stream / level_strip / level_fused_kernel
+enum class Smooth { None, Tiles, Strips };            // a separate smooth_flow pass: LDS tiles, or register strips + a frame of tiles
+enum class Start { PrevLt, Written, HalfSample, AreaResize };   // Written: by the launch that finished the previous level (into tmpH)
+enum class BaseStage { Strips, Separate };            // base_strip_kernel, or gray + two Gaussians + the gradient kernel
+
 struct LevelPlan {
     static constexpr int MAX_PASSES = 18;   // <= 64 steps in groups of >= 4, + the fused head
     int fuse = 0;               // most steps of a pass (of pass 0 of a fused level: fused_max_steps)
     bool fused_level = false;   // pass 0 is level_fused_kernel's
-    bool try_strips = false;    // pass 0 is offered to the register-strip kernels first
+    bool try_strips = false;    // pass 0 goes to a register-strip head if one can take the level
     int launches = 0;
     int first[MAX_PASSES] = {}, steps[MAX_PASSES] = {};   // pass p runs FED steps [first[p], first[p] + steps[p])
     bool lands_in_lt(int pass) const { return (launches - 1 - pass) % 2 == 0; }
     bool start_in_lt() const { return launches % 2 == 0; }   // where a resampled start image goes, so that the last pass lands in Lt
+    // filled by plan_extraction
+    bool doh_strips = false;    // the Hessian kernel: doh_strip_kernel, else doh_fused_kernel
+    Start start = Start::PrevLt;
+    Smooth smooth = Smooth::None;
+    Head head = Head::None;
+    bool strip_pass[MAX_PASSES] = {};   // a pass that is not the head: nld_strip_kernel, else nld_multi_kernel (LDS tiles)
+    int half_pass = -1;         // the pass that also writes the next octave's start image (the last one), or -1: the next level resamples
+    int first_fed_pass() const { return head == Head::None ? 0 : 1; }
 };
 
-// level_fuse, level_strip: the values of APDS_LEVEL_FUSE and APDS_LEVEL_STRIP (0 never, 1 by size, 2 always)
+inline bool fits_32bit_offsets(int w, int h) { return (size_t)w * h < (size_t)1 << 29; }   // byte offsets into a float plane (buffer loads)
+
+// smooth_flow's tiles [1, txi) x [1, tyi) lie inside the image with their 3-pixel halo (the strips' region; the frame around them: LDS tiles)
+inline void smooth_flow_interior(int w, int h, int& txi, int& tyi) {
+    txi = w >= SF_TILE_W + 67 ? (w - 67) / SF_TILE_W + 1 : 1;
+    tyi = h >= SF_TILE_H + 35 ? (h - 35) / SF_TILE_H + 1 : 1;
+}
+
+// The pass arithmetic of one level. level_fuse, level_strip: the values of APDS_LEVEL_FUSE and APDS_LEVEL_STRIP
 inline LevelPlan plan_level(const LevelDesc& e, int batch, int level_fuse, int level_strip, int fused_max_steps) {
     LevelPlan p;
     const size_t lpx = (size_t)e.w * e.h * batch;
@@ -204,6 +240,73 @@ inline LevelPlan plan_level(const LevelDesc& e, int batch, int level_fuse, int l
     // against 1.83 in another; 2048^2: 0.79 against 0.82. APDS_LEVEL_STRIP=2: every level whatever its size, 0: never)
     p.try_strips = !p.fused_level && e.nsteps > 0 && level_strip && (level_strip == 2 || lpx >= (size_t)1 << 20) && p.steps[0] <= 4;
     return p;
+}
+
+struct ExtractionPlan {
+    std::vector<LevelPlan> level;   // level[0]: only doh_strips (Lt[0] comes from the base stage)
+    int n_strip_levels = 0;         // the levels, a prefix of the list, whose Hessian kernel is the streaming one
+};
+
+// The thresholds (a batch counts as a whole: the strip and streaming kernels pay once a LAUNCH has enough pixels to be throughput-bound):
+// streaming kernels from 8 Mpx (below that a level has too few 64-column strips to fill the chip with bands of a useful height - 2048^2: 41
+// strips; bands of 16 rows spend half their walk on the warm-up rows - and the LDS tiles are quicker), FED strips from 1 Mpx (the LDS
+// tiles keep the deeply fused launches of the small, latency-bound octaves: their unrolled strip code would not fit the instruction
+// cache), smooth_flow's strips from 2 Mpx.
+inline ExtractionPlan plan_extraction(const std::vector<LevelDesc>& ev, int batch, const PlanSwitches& sw) {
+    const int L = (int)ev.size();
+    ExtractionPlan plan;
+    plan.level.resize(L);
+    bool strip_prefix = true;
+    for (int i = 0; i < L; i++) {
+        const LevelDesc& e = ev[i];
+        const size_t bpx = (size_t)e.w * e.h * batch;
+        const bool fits = fits_32bit_offsets(e.w, e.h);
+        LevelPlan& p = plan.level[i];
+        if (i > 0) p = plan_level(e, batch, sw.level_fuse, sw.level_strip, LEVEL_FUSED_MAX_STEPS);
+        // doh_strip_kernel writes the mask and status bytes of its whole level, and zero_slab_heads skips a PREFIX of the levels
+        strip_prefix = strip_prefix && sw.doh_strip && e.sigma_size >= 2 && e.sigma_size <= 4 && e.w >= 64 && e.h >= 64 &&
+                       (sw.doh_strip == 2 || bpx >= (size_t)1 << 23);
+        p.doh_strips = strip_prefix;
+        plan.n_strip_levels += strip_prefix ? 1 : 0;
+        if (i == 0) continue;
+
+        const LevelDesc& prev = ev[i - 1];
+        if (e.octave == prev.octave) p.start = Start::PrevLt;
+        else if (plan.level[i - 1].half_pass >= 0) p.start = Start::Written;
+        else p.start = prev.w == 2 * e.w && prev.h == 2 * e.h ? Start::HalfSample : Start::AreaResize;   // (odd sizes: the general area resize)
+
+        if (p.fused_level) {
+            p.head = Head::Fused;
+        } else if (p.try_strips && p.steps[0] >= 1 && p.steps[0] <= 4 && fits) {
+            if (sw.level_stream && e.w >= 64 && e.h >= 32 && (sw.level_stream == 2 || bpx >= (size_t)1 << 23)) p.head = Head::Stream;
+            else if (e.w >= 2 && e.h >= 2) p.head = Head::Strips;
+        }
+        // the last level's Hessian kernel is on the critical path (nothing follows to hide it): when it forks, its Lsmooth comes from a
+        // separate smoothing pass, so that it runs beside the level's FED steps
+        if (p.head != Head::Stream && p.head != Head::Strips && (!p.fused_level || (sw.fork && i == L - 1))) {
+            int txi, tyi;
+            smooth_flow_interior(e.w, e.h, txi, tyi);
+            const bool strips = sw.sf_strip && txi > 1 && tyi > 1 && fits && (bpx >= (size_t)1 << 21 || sw.sf_strip == 2);
+            p.smooth = strips ? Smooth::Strips : Smooth::Tiles;
+        }
+        for (int q = p.first_fed_pass(); q < p.launches; q++)
+            p.strip_pass[q] = sw.nld_strip && p.steps[q] <= 4 && (bpx >= (size_t)1 << 20 || sw.nld_strip == 2) && fits;
+        // does the NEXT level start an octave from exactly half this level's size (the 2 x 2 mean)? Then the pass that finishes this
+        // level writes that image too, if its kernel can: not level_strip_kernel, not the LDS tiles
+        const bool want_half = sw.half_fuse && i + 1 < L && ev[i + 1].octave > e.octave && e.w == 2 * ev[i + 1].w && e.h == 2 * ev[i + 1].h;
+        const int last = p.launches - 1;
+        if (want_half && last >= 0 && (last < p.first_fed_pass() ? p.head == Head::Stream || p.head == Head::Fused : p.strip_pass[last])) p.half_pass = last;
+    }
+    return plan;
+}
+
+// The base stage: one fused pass on register strips for large images (the launch-bound small tiles keep the separate kernels), if the
+// image fits 32-bit offsets and, with four channels, dword loads of the BGRA pixels. img: the address of the first image.
+inline BaseStage plan_base(int rows, int cols, int channels, size_t stride, uintptr_t img, size_t img_stride, int batch, const PlanSwitches& sw) {
+    const size_t px = (size_t)rows * cols;
+    const bool strips = sw.base_strip && (px * batch >= (size_t)1 << 21 || sw.base_strip == 2) && px < (size_t)1 << 29 &&
+                        (size_t)rows * stride < (size_t)1 << 31 && (channels != 4 || ((img | stride | img_stride) & 3) == 0);
+    return strips ? BaseStage::Strips : BaseStage::Separate;
 }
 
 // ---- one image's workspace slab -------------------------------------------------------------------------------------------------------

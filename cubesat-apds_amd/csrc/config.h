@@ -5,6 +5,9 @@
 // of the match's work-item plan (now constants in match_hamming.hip: plan_chunks). Round 4 and the matrix-core matcher grew the table to 38;
 // round 4's two variants of the fork to the Hessian stream lost their measurements and are deleted as well (the value fork and the early
 // fork: HessianFork in akaze_extract.hip, DESIGN_HISTORY.md): 36 switches.
+// Who reads a switch: the eight that pick an AKAZE level's or the base stage's kernel family (nld_strip .. doh_strip, half_fuse) and
+// akaze_fork are read by the extraction driver alone, once per call, into the PlanSwitches that akaze_plan.h turns into the table it executes;
+// the filter launchers read only the two band-height test hooks and fed_shrink.
 #pragma once
 
 namespace apds {

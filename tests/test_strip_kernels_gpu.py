@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -63,6 +64,48 @@ def test_akaze_parity_with_the_streaming_kernels_on_every_level(gpu_pkg):
     clamped columns, partial last bands; once with 16-row bands and once with tall ones."""
     _rerun({"APDS_DOH_STRIP": "2", "APDS_DOH_STRIP_ROWS": "16", "APDS_LEVEL_STREAM": "2", "APDS_LEVEL_STREAM_ROWS": "16", "APDS_LEVEL_STRIP": "2", "APDS_LEVEL_FUSE": "0"})
     _rerun({"APDS_DOH_STRIP": "2", "APDS_DOH_STRIP_ROWS": "112", "APDS_LEVEL_STREAM": "2", "APDS_LEVEL_STREAM_ROWS": "100", "APDS_LEVEL_STRIP": "2", "APDS_LEVEL_FUSE": "0"})
+
+
+STREAMING_SET = {"APDS_DOH_STRIP": "2", "APDS_LEVEL_STREAM": "2", "APDS_LEVEL_STRIP": "2", "APDS_LEVEL_FUSE": "0"}
+BORDER_SIZES = [(63, 64), (64, 31), (64, 63), (64, 64), (70, 33)]   # w x h
+
+
+@pytest.mark.parametrize("w,h", BORDER_SIZES)
+def test_levels_beside_the_streaming_kernels_smallest_sizes_equal_oracle(gpu_pkg, oracle_mod, w, h):
+    """Single-octave images on either side of the streaming kernels' smallest sizes (level_stream_kernel: 64 x 32, doh_strip_kernel:
+    64 x 64): Lt and Ldet of every level and the keypoints equal the oracle's exactly (the planes, because such an image may have no
+    keypoint at all). Under the process's switches; the test below runs it with the streaming set forced, where the plan hands a level
+    below those sizes to level_strip_kernel / doh_fused_kernel."""
+    forced = os.environ.get("APDS_TEST_EXPECT_SWITCHES")
+    if forced:
+        assert all(os.environ.get(k) == v for k, v in STREAMING_SET.items()), "the child process lost its switches"
+    tile = gpu_pkg.synth.make_tile(h, w, frame_index=w + h, channels=1)
+    ref = oracle_mod.akaze(tile, keep_planes=True)
+    assert len(ref.levels) == 4 and all((lv["w"], lv["h"]) == (w, h) for lv in ref.levels)
+    lib, ptr = gpu_pkg.lib(), gpu_pkg._lib.ptr
+    for level in range(4):
+        for name, which in (("Lt", 0), ("Ldet", 4)):
+            got = np.zeros((h, w), np.float32)
+            gpu_pkg._lib.check(lib.apds_akaze_debug_plane(ptr(tile), h, w, 1, tile.strides[0], level, which, ptr(got)))
+            want = ref.plane(level, which)
+            assert np.array_equal(got, want), (level, name, np.abs(got - want).max())
+    got = gpu_pkg.feature_extraction.akaze_keypoint_descriptor_extraction_def(tile, None)
+    assert len(got.keypoints) == len(ref.keypoints)
+    for f in ("x", "y", "size", "response", "angle", "octave", "class_id"):
+        assert np.array_equal(got.keypoints[f], ref.keypoints[f]), f
+    assert np.array_equal(got.descriptors, ref.descriptors)
+
+
+def test_the_plan_hands_levels_below_the_streaming_sizes_to_the_other_family(gpu_pkg):
+    """The test above in a child process with APDS_DOH_STRIP=2 APDS_LEVEL_STREAM=2 APDS_LEVEL_STRIP=2 APDS_LEVEL_FUSE=0: 64 x 64 takes both
+    streaming kernels, 70 x 33 and 64 x 63 the streaming level kernel and the LDS-tile Hessian kernel, 63 x 64 and 64 x 31 neither - the
+    plan decides, no launcher is asked and refuses."""
+    env = dict(os.environ, APDS_TEST_EXPECT_SWITCHES="1", **STREAMING_SET)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join("tests", "test_strip_kernels_gpu.py"), "-k",
+                        "test_levels_beside_the_streaming_kernels_smallest_sizes_equal_oracle", "-q", "-m", "gpu", "-x", "-p", "no:cacheprovider"],
+                       env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-1000:])
+    assert f"{len(BORDER_SIZES)} passed" in r.stdout and "failed" not in r.stdout
 
 
 def test_akaze_parity_with_separate_launches_and_the_current_keypoint_kernels(gpu_pkg):
