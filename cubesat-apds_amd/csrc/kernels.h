@@ -88,7 +88,7 @@ void mosaic_check_window(const Mosaic* m, int level, const int32_t* xy0, int n_t
 void mosaic_read_device(const Mosaic* m, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample, float* out, hipStream_t s);
 void mosaic_min_max(Mosaic* m, double* minmax6);   // cached in the handle; resets the calling thread's workspace when it computes
 
-// homography.hip
+// homography.hip (the refit it drives: homography.h, homography_refit.hip)
 int find_homography_device(const float* src, const float* dst, int n, int method, double thr, int max_iters, double confidence,
                            double* H_host, uint8_t* mask_dev, hipStream_t s);
 

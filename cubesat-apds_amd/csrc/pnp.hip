@@ -13,6 +13,7 @@
 #include "config.h"
 #include "kernels.h"
 #include "pnp_core.h"
+#include "ransac_loop.h"
 #include "sqpnp_core.h"
 #include "ippe_core.h"
 
@@ -148,31 +149,6 @@ __global__ void pnp_mask_kernel(const float* __restrict__ obj, const float* __re
     const double rv[3] = {model[0], model[1], model[2]}, tv[3] = {model[3], model[4], model[5]};
     pnp::rotation_from_rvec(rv, R);
     mask[i] = pnp::reprojection_sqerr(R, tv, cam, obj[3 * (size_t)i], obj[3 * (size_t)i + 1], obj[3 * (size_t)i + 2], img[2 * (size_t)i], img[2 * (size_t)i + 1]) <= t;
-}
-
-// getSubset with the default checkSubset: `model_points` distinct indices from the cv::RNG stream
-void next_sample(int count, int* idx, pnp::MwcRng& rng, int model_points) {
-    for (int i = 0; i < model_points; ++i) {
-        int v;
-        for (;;) {
-            v = (int)(rng.next() % (unsigned)count);
-            bool dup = false;
-            for (int j = 0; j < i; j++) dup |= idx[j] == v;
-            if (!dup) break;
-        }
-        idx[i] = v;
-    }
-}
-
-int update_num_iters(double p, double ep, int modelPoints, int maxIters) {   // ptsetreg.cpp RANSACUpdateNumIters
-    p = std::min(std::max(p, 0.), 1.);
-    ep = std::min(std::max(ep, 0.), 1.);
-    double num = std::max(1. - p, DBL_MIN);
-    double denom = 1. - std::pow(1. - ep, modelPoints);
-    if (denom < DBL_MIN) return 0;
-    num = std::log(num);
-    denom = std::log(denom);
-    return denom >= 0 || -num >= maxIters * (-denom) ? maxIters : (int)lrint(num / denom);
 }
 
 // EPnP on host arrays (float for the n == 5 shortcut, double for the all-inlier solve), then Rodrigues
@@ -512,26 +488,103 @@ int pnp_checked_method(int n, int method) {
     return method;
 }
 
-// host-array front: solvePnPRansac converts CV_64F points to CV_32F before anything else; the float copies go to the device
+namespace {
+
+// the RANSAC kernel of a batch of samples: P3P / AP3P on 4 points (valid[h] = 0: no pose), EPnP on 5 (valid is not written)
+void launch_pose_hypotheses(bool p3p, bool ap3p, const float* obj_dev, const float* img_dev, const int* idx_dev, int B, const Camera& cam, double* models_dev,
+                            uint8_t* valid_dev, hipStream_t s) {
+    if (ap3p)
+        hipLaunchKernelGGL(p3p_hypothesis_kernel<true>, dim3(ceil_div(B, 64)), dim3(64), 0, s, obj_dev, img_dev, idx_dev, B, cam, models_dev, valid_dev);
+    else if (p3p)
+        hipLaunchKernelGGL(p3p_hypothesis_kernel<false>, dim3(ceil_div(B, 64)), dim3(64), 0, s, obj_dev, img_dev, idx_dev, B, cam, models_dev, valid_dev);
+    else
+        hipLaunchKernelGGL(pnp_hypothesis_kernel, dim3(ceil_div(B, PNP_THREADS)), dim3(PNP_THREADS), PNP_LDS_BYTES, s, obj_dev, img_dev, idx_dev, B, cam, models_dev);
+}
+
+// solvePnPRansac converts CV_64F points to CV_32F before anything else; the float copies go to the device (workspace of the calling thread)
+void upload_as_float(const double* obj_xyz, const double* img_xy, int n, float** obj_dev, float** img_dev, hipStream_t s) {
+    std::vector<float> op(3 * (size_t)n), ip(2 * (size_t)n);
+    for (size_t i = 0; i < op.size(); i++) op[i] = (float)obj_xyz[i];
+    for (size_t i = 0; i < ip.size(); i++) ip[i] = (float)img_xy[i];
+    ThreadCtx& c = ctx();
+    *obj_dev = c.alloc_n<float>(op.size());
+    *img_dev = c.alloc_n<float>(ip.size());
+    HIP_CHECK(hipMemcpyAsync(*obj_dev, op.data(), op.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(*img_dev, ip.data(), ip.size() * sizeof(float), hipMemcpyHostToDevice, s));
+}
+
+// model_points == npoints: one direct solve on the host, every point an inlier
+int solve_minimal(const float* op, const float* ip, int n, const Camera& cam, bool p3p, bool ap3p, double* rvec, double* tvec, int32_t* inliers, int* n_inliers) {
+    if (p3p) {
+        if (!host_p3p<float>(op, ip, cam, rvec, tvec, ap3p)) return 0;
+    } else {
+        host_epnp<float>(op, ip, n, cam, rvec, tvec);
+    }
+    if (inliers)
+        for (int i = 0; i < n; i++) inliers[i] = i;
+    *n_inliers = n;
+    return 1;
+}
+
+// the correspondences mask selects, as doubles converted back from the float copies, in index order (what the final pose is solved from);
+// their indices go to inliers unless null. Returns their number.
+int gather_inliers(const std::vector<uint8_t>& mask, const float* op, const float* ip, int32_t* inliers, std::vector<double>& oi, std::vector<double>& ii) {
+    int cnt = 0;
+    for (size_t i = 0; i < mask.size(); i++)
+        if (mask[i]) {
+            for (int k = 0; k < 3; k++) oi.push_back((double)op[3 * i + k]);
+            for (int k = 0; k < 2; k++) ii.push_back((double)ip[2 * i + k]);
+            if (inliers) inliers[cnt] = (int32_t)i;
+            cnt++;
+        }
+    return cnt;
+}
+
+// The last solvePnP of solvePnPRansac: `method` over the cnt inliers (oi: cnt x 3, ii: cnt x 2 doubles, index order). best: the RANSAC model.
+// Returns 0 where solvePnPRansac returns false (rvec / tvec then hold the RANSAC model).
+int final_pose(int method, const double* oi, const double* ii, int cnt, const Camera& cam, const double* best, double* rvec, double* tvec, hipStream_t s) {
+    // SOLVEPNP_IPPE_SQUARE: the RANSAC kernel was EPnP on 5 points (or the direct P3P solve for n == 4), and the final solvePnP over
+    // the >= 5 inliers starts with CV_Assert(npoints == 4): solvePnPRansac rethrows it, the reference returns Err(MatError::Opencv)
+    APDS_REQUIRE(method != APDS_SOLVEPNP_IPPE_SQUARE, APDS_ERR_ASSERT, "SOLVEPNP_IPPE_SQUARE: solvePnP asserts npoints == 4 on the inlier set");
+    if (method == APDS_SOLVEPNP_ITERATIVE) {   // no extrinsic guess (mod.rs:354): homography / DLT start, then Levenberg-Marquardt
+        double pose[6];
+        std::memcpy(pose, best, sizeof(pose));   // (what stays when five non-planar inliers cannot start the DLT)
+        if (iterative_start_pose(oi, ii, cnt, cam, pose, s)) PoseRefiner{oi, ii, cnt, cam, {}, {}}.run(pose);
+        std::memcpy(rvec, pose, 3 * sizeof(double));
+        std::memcpy(tvec, pose + 3, 3 * sizeof(double));
+    } else if (method == APDS_SOLVEPNP_SQPNP || method == APDS_SOLVEPNP_IPPE) {
+        // the RANSAC kernel stayed EPnP; the last solvePnP over the inliers is SQPnP (sqpnp_core.h) or IPPE (ippe_core.h: planar targets;
+        // inliers that are not coplanar have no IPPE pose)
+        const bool posed = method == APDS_SOLVEPNP_IPPE ? ippe::solve(oi, ii, cnt, cam, rvec, tvec) : sqpnp::solve(oi, ii, cnt, cam, rvec, tvec);
+        if (!posed) {   // no pose: solvePnPRansac hands back the RANSAC model and returns false
+            std::memcpy(rvec, best, 3 * sizeof(double));
+            std::memcpy(tvec, best + 3, 3 * sizeof(double));
+            return 0;
+        }
+    } else {
+        host_epnp<double>(oi, ii, cnt, cam, rvec, tvec);
+    }
+    return 1;
+}
+
+}  // namespace
+
+// host-array front of pnp_ransac_core
 int pnp_ransac_device(const double* obj_xyz, const double* img_xy, int n, const double* K, int iterations, float reproj_thr, double confidence, int method,
                       double* rvec, double* tvec, int32_t* inliers, int* n_inliers, hipStream_t s) {
     APDS_REQUIRE(n_inliers, APDS_ERR_BAD_ARG, "null argument");
     *n_inliers = 0;
     APDS_REQUIRE(obj_xyz && img_xy && K && rvec && tvec && inliers, APDS_ERR_BAD_ARG, "null argument");
     (void)pnp_checked_method(n, method);
-    std::vector<float> op(3 * (size_t)n), ip(2 * (size_t)n);
-    for (size_t i = 0; i < op.size(); i++) op[i] = (float)obj_xyz[i];
-    for (size_t i = 0; i < ip.size(); i++) ip[i] = (float)img_xy[i];
-    ThreadCtx& c = ctx();
-    float* obj_dev = c.alloc_n<float>(op.size());
-    float* img_dev = c.alloc_n<float>(ip.size());
-    HIP_CHECK(hipMemcpyAsync(obj_dev, op.data(), op.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(img_dev, ip.data(), ip.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    float *obj_dev, *img_dev;
+    upload_as_float(obj_xyz, img_xy, n, &obj_dev, &img_dev, s);
     return pnp_ransac_core(obj_dev, img_dev, n, K, iterations, reproj_thr, confidence, method, rvec, tvec, inliers, n_inliers, s);
 }
 
-// The RANSAC loop on float correspondences that are already on the device (ordered on s); the host solves read the n x 5 floats it downloads.
-// inliers may be null (the pipeline's pose stage reports the count only). Scratch comes from the calling thread's workspace.
+// The RANSAC loop (ransac_loop.h) on float correspondences that are already on the device (ordered on s): the cv::RNG sample stream is drawn
+// ahead on the host, a batch is solved and scored in two launches, the controller replays the sequential accept / shorten logic. The host
+// solves read the n x 5 floats it downloads. inliers may be null (the pipeline's pose stage reports the count only). Scratch comes from the
+// calling thread's workspace.
 int pnp_ransac_core(const float* obj_dev, const float* img_dev, int n, const double* K, int iterations, float reproj_thr, double confidence, int method,
                     double* rvec, double* tvec, int32_t* inliers, int* n_inliers, hipStream_t s) {
     APDS_REQUIRE(n_inliers, APDS_ERR_BAD_ARG, "null argument");
@@ -546,109 +599,56 @@ int pnp_ransac_core(const float* obj_dev, const float* img_dev, int n, const dou
     std::vector<float> op(3 * (size_t)n), ip(2 * (size_t)n);
     HIP_CHECK(hipMemcpyAsync(op.data(), obj_dev, op.size() * sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(ip.data(), img_dev, ip.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (n == model_points) {   // model_points == npoints: one direct solve, every point an inlier
+    if (n == model_points) {
         HIP_CHECK(hipStreamSynchronize(s));
-        if (p3p) {
-            if (!host_p3p<float>(op.data(), ip.data(), cam, rvec, tvec, ap3p)) return 0;
-        } else {
-            host_epnp<float>(op.data(), ip.data(), n, cam, rvec, tvec);
-        }
-        if (inliers)
-            for (int i = 0; i < n; i++) inliers[i] = i;
-        *n_inliers = n;
-        return 1;
+        return solve_minimal(op.data(), ip.data(), n, cam, p3p, ap3p, rvec, tvec, inliers, n_inliers);
     }
     ThreadCtx& c = ctx();
 
     // a batch costs about the same wall time up to ~16 k samples (one thread each, latency-bound): speculate deep
-    const int batch_env = config().pnp_batch;
-    int niters = std::max(iterations, 1), maxGood = 0, iter = 0;
-    const int batch = std::max(PNP_HT, std::min(batch_env, niters));
+    const int batch = std::max(PNP_HT, std::min(config().pnp_batch, std::max(iterations, 1)));
     const float t = (float)((double)reproj_thr * (double)reproj_thr);
     int* idx_dev = c.alloc_n<int>((size_t)batch * model_points);
     double* models_dev = c.alloc_n<double>((size_t)batch * 6);
     int* good_dev = c.alloc_n<int>(batch);
     uint8_t* valid_dev = c.alloc_n<uint8_t>(batch);
     uint8_t* mask_dev = c.alloc_n<uint8_t>(n);
-    std::vector<int> idx((size_t)batch * model_points), good(batch);
-    std::vector<uint8_t> valid(batch, 1);
-    std::vector<double> models((size_t)batch * 6);
-    double best[6] = {0, 0, 0, 0, 0, 0};
-    pnp::MwcRng rng{(uint64_t)-1};
-    while (iter < niters) {
-        const int B = std::min(batch, niters - iter);
-        for (int b = 0; b < B; b++) next_sample(n, &idx[(size_t)b * model_points], rng, model_points);
-        HIP_CHECK(hipMemcpyAsync(idx_dev, idx.data(), (size_t)B * model_points * sizeof(int), hipMemcpyHostToDevice, s));
+    CvRng rng((uint64_t)-1);
+    auto draw = [&](int* idx) {
+        next_sample(n, idx, rng, model_points);
+        return true;
+    };
+    auto evaluate = [&](const int* idx, int B, int* good, uint8_t* valid, double* models) {
+        HIP_CHECK(hipMemcpyAsync(idx_dev, idx, (size_t)B * model_points * sizeof(int), hipMemcpyHostToDevice, s));
         HIP_CHECK(hipMemsetAsync(good_dev, 0, (size_t)B * sizeof(int), s));
-        if (ap3p)
-            hipLaunchKernelGGL(p3p_hypothesis_kernel<true>, dim3(ceil_div(B, 64)), dim3(64), 0, s, (const float*)obj_dev, (const float*)img_dev, (const int*)idx_dev, B,
-                               cam, models_dev, valid_dev);
-        else if (p3p)
-            hipLaunchKernelGGL(p3p_hypothesis_kernel<false>, dim3(ceil_div(B, 64)), dim3(64), 0, s, (const float*)obj_dev, (const float*)img_dev, (const int*)idx_dev, B,
-                               cam, models_dev, valid_dev);
-        else
-            hipLaunchKernelGGL(pnp_hypothesis_kernel, dim3(ceil_div(B, PNP_THREADS)), dim3(PNP_THREADS), PNP_LDS_BYTES, s, (const float*)obj_dev,
-                               (const float*)img_dev, (const int*)idx_dev, B, cam, models_dev);
+        launch_pose_hypotheses(p3p, ap3p, obj_dev, img_dev, idx_dev, B, cam, models_dev, valid_dev, s);
         {
             KernelTimer timer("pnp_score", s);
             const int parts = std::max(1, std::min(64, ceil_div(256 * 8, ceil_div(B, PNP_HT))));
-            hipLaunchKernelGGL(pnp_score_kernel, dim3(ceil_div(B, PNP_HT), parts), dim3(256), 0, s, (const float*)obj_dev, (const float*)img_dev, n,
-                               (const double*)models_dev, B, cam, t, good_dev);
+            hipLaunchKernelGGL(pnp_score_kernel, dim3(ceil_div(B, PNP_HT), parts), dim3(256), 0, s, obj_dev, img_dev, n, (const double*)models_dev, B, cam, t,
+                               good_dev);
         }
-        HIP_CHECK(hipMemcpyAsync(good.data(), good_dev, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipMemcpyAsync(models.data(), models_dev, (size_t)B * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (p3p) HIP_CHECK(hipMemcpyAsync(valid.data(), valid_dev, (size_t)B, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(good, good_dev, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(models, models_dev, (size_t)B * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (p3p)   // a P3P sample without a pose yields no model; EPnP always has one
+            HIP_CHECK(hipMemcpyAsync(valid, valid_dev, (size_t)B, hipMemcpyDeviceToHost, s));
+        else
+            std::memset(valid, 1, B);
         HIP_CHECK(hipStreamSynchronize(s));
-        // replay the sequential loop over the speculated iterations (samples beyond a shortened budget are discarded)
-        for (int b = 0; b < B && iter < niters; b++, iter++) {
-            if (!valid[b]) continue;   // P3P found no pose for this sample: the iteration yields no model
-            if (good[b] > std::max(maxGood, model_points - 1)) {
-                std::memcpy(best, &models[(size_t)b * 6], sizeof(best));
-                maxGood = good[b];
-                niters = update_num_iters(confidence, (double)(n - good[b]) / n, model_points, niters);
-            }
-        }
-    }
+    };
+    const RansacResult r = speculative_ransac(n, model_points, 6, iterations, confidence, batch, batch, draw, evaluate);
     HIP_CHECK(hipGetLastError());
-    if (maxGood <= 0) return 0;
+    if (!r.found) return 0;
+    const double* best = r.model.data();
     std::vector<uint8_t> mask(n);
-    HIP_CHECK(hipMemcpyAsync(models_dev, best, sizeof(best), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(pnp_mask_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, (const float*)obj_dev, (const float*)img_dev, n, (const double*)models_dev, cam, t,
-                       mask_dev);
+    HIP_CHECK(hipMemcpyAsync(models_dev, best, 6 * sizeof(double), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(pnp_mask_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, obj_dev, img_dev, n, (const double*)models_dev, cam, t, mask_dev);
     HIP_CHECK(hipMemcpyAsync(mask.data(), mask_dev, n, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    // final pose from all inliers (as doubles converted back from the float copies), in index order
     std::vector<double> oi, ii;
-    int cnt = 0;
-    for (int i = 0; i < n; i++)
-        if (mask[i]) {
-            for (int k = 0; k < 3; k++) oi.push_back((double)op[3 * (size_t)i + k]);
-            for (int k = 0; k < 2; k++) ii.push_back((double)ip[2 * (size_t)i + k]);
-            if (inliers) inliers[cnt] = i;
-            cnt++;
-        }
-    APDS_REQUIRE(cnt == maxGood, APDS_ERR_INTERNAL, "inlier mask disagrees with the scored count");
-    // SOLVEPNP_IPPE_SQUARE: the RANSAC kernel was EPnP on 5 points (or the direct P3P solve above for n == 4), and the final solvePnP over
-    // the >= 5 inliers starts with CV_Assert(npoints == 4): solvePnPRansac rethrows it, the reference returns Err(MatError::Opencv)
-    APDS_REQUIRE(method != APDS_SOLVEPNP_IPPE_SQUARE, APDS_ERR_ASSERT, "SOLVEPNP_IPPE_SQUARE: solvePnP asserts npoints == 4 on the inlier set");
-    if (method == APDS_SOLVEPNP_ITERATIVE) {   // no extrinsic guess (mod.rs:354): homography / DLT start, then Levenberg-Marquardt
-        double pose[6];
-        std::memcpy(pose, best, sizeof(pose));   // (what stays when five non-planar inliers cannot start the DLT)
-        if (iterative_start_pose(oi.data(), ii.data(), cnt, cam, pose, s)) PoseRefiner{oi.data(), ii.data(), cnt, cam, {}, {}}.run(pose);
-        std::memcpy(rvec, pose, 3 * sizeof(double));
-        std::memcpy(tvec, pose + 3, 3 * sizeof(double));
-    } else if (method == APDS_SOLVEPNP_SQPNP || method == APDS_SOLVEPNP_IPPE) {
-        // the RANSAC kernel stayed EPnP; the last solvePnP over the inliers is SQPnP (sqpnp_core.h) or IPPE (ippe_core.h: planar targets;
-        // inliers that are not coplanar have no IPPE pose)
-        const bool posed = method == APDS_SOLVEPNP_IPPE ? ippe::solve(oi.data(), ii.data(), cnt, cam, rvec, tvec) : sqpnp::solve(oi.data(), ii.data(), cnt, cam, rvec, tvec);
-        if (!posed) {   // no pose: solvePnPRansac hands back the RANSAC model and returns false
-            std::memcpy(rvec, best, 3 * sizeof(double));
-            std::memcpy(tvec, best + 3, 3 * sizeof(double));
-            return 0;
-        }
-    } else {
-        host_epnp<double>(oi.data(), ii.data(), cnt, cam, rvec, tvec);
-    }
+    const int cnt = gather_inliers(mask, op.data(), ip.data(), inliers, oi, ii);
+    APDS_REQUIRE(cnt == r.max_good, APDS_ERR_INTERNAL, "inlier mask disagrees with the scored count");
+    if (!final_pose(method, oi.data(), ii.data(), cnt, cam, best, rvec, tvec, s)) return 0;
     *n_inliers = cnt;
     return 1;
 }
@@ -679,27 +679,14 @@ void pnp_hypotheses_device(const double* obj_xyz, const double* img_xy, int n, c
                  "bad argument");
     for (int i = 0; i < B * model_points; i++) APDS_REQUIRE(idx5[i] >= 0 && idx5[i] < n, APDS_ERR_OUT_OF_RANGE, "sample index out of range");
     const Camera cam{K[0], K[4], K[2], K[5]};
-    std::vector<float> op(3 * (size_t)n), ip(2 * (size_t)n);
-    for (size_t i = 0; i < op.size(); i++) op[i] = (float)obj_xyz[i];
-    for (size_t i = 0; i < ip.size(); i++) ip[i] = (float)img_xy[i];
+    float *obj_dev, *img_dev;
+    upload_as_float(obj_xyz, img_xy, n, &obj_dev, &img_dev, s);
     ThreadCtx& c = ctx();
-    float* obj_dev = c.alloc_n<float>(op.size());
-    float* img_dev = c.alloc_n<float>(ip.size());
     int* idx_dev = c.alloc_n<int>((size_t)B * model_points);
     double* models_dev = c.alloc_n<double>((size_t)B * 6);
     uint8_t* valid_dev = c.alloc_n<uint8_t>(B);
-    HIP_CHECK(hipMemcpyAsync(obj_dev, op.data(), op.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(img_dev, ip.data(), ip.size() * sizeof(float), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(idx_dev, idx5, (size_t)B * model_points * sizeof(int), hipMemcpyHostToDevice, s));
-    if (model_points == 4 && ap3p)
-        hipLaunchKernelGGL(p3p_hypothesis_kernel<true>, dim3(ceil_div(B, 64)), dim3(64), 0, s, (const float*)obj_dev, (const float*)img_dev, (const int*)idx_dev, B, cam,
-                           models_dev, valid_dev);
-    else if (model_points == 4)
-        hipLaunchKernelGGL(p3p_hypothesis_kernel<false>, dim3(ceil_div(B, 64)), dim3(64), 0, s, (const float*)obj_dev, (const float*)img_dev, (const int*)idx_dev, B, cam,
-                           models_dev, valid_dev);
-    else
-        hipLaunchKernelGGL(pnp_hypothesis_kernel, dim3(ceil_div(B, PNP_THREADS)), dim3(PNP_THREADS), PNP_LDS_BYTES, s, (const float*)obj_dev,
-                           (const float*)img_dev, (const int*)idx_dev, B, cam, models_dev);
+    launch_pose_hypotheses(model_points == 4, ap3p, obj_dev, img_dev, idx_dev, B, cam, models_dev, valid_dev, s);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(models_host, models_dev, (size_t)B * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
     if (model_points == 4) {

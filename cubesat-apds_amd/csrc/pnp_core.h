@@ -13,6 +13,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "ransac_loop.h"   // CvRng
+
 namespace apds {
 namespace pnp {
 
@@ -34,14 +36,6 @@ struct Strided {
     T* p;
     PNP_HD T& operator[](int i) const { return p[i * STRIDE]; }
     PNP_HD Strided sub(int off) const { return Strided{p + off * STRIDE}; }
-};
-
-struct MwcRng {   // cv::RNG
-    uint64_t state;
-    PNP_HD unsigned next() {
-        state = (uint64_t)(unsigned)state * 4164903690U + (unsigned)(state >> 32);
-        return (unsigned)state;
-    }
 };
 
 // ---- elementary functions with a fixed evaluation order ---------------------------------------------------------------
@@ -192,7 +186,7 @@ PNP_HD void svd_rows(AT At, int m, int n, WA W, VT Vt) {
                 }
         }
     }
-    MwcRng rng{0x12345678};
+    CvRng rng(0x12345678);
     for (int i = 0; i < n; i++) {
         double sd = W[i];
         for (int ii = 0; ii < 100 && sd <= minval; ii++) {

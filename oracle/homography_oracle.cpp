@@ -471,7 +471,7 @@ void lm_refine(const P2f* M, const P2f* m, int count, double* H, int maxIters) {
 
 // ---- the refit over MANY points: the summation order of the GPU's reduction ---------------------------------------------------
 // Above 256 selected points the product sums the per-point terms of runKernel and of the LM normal equations with a parallel
-// reduction (csrc/homography.hip reduce_kernel: 64 blocks x 256 threads, thread (b, t) takes the points b*256 + t + 16384 j in
+// reduction (csrc/homography_refit.hip reduce_kernel: 64 blocks x 256 threads, thread (b, t) takes the points b*256 + t + 16384 j in
 // order; a wave folds its 64 partial sums with the shuffle-down tree 32, 16, ..., 1; the four waves of a block, then the 64 blocks,
 // are added in order). Floating-point sums depend on their order, so a sequential loop here could only agree to ~1e-6 (round 1).
 // This restates that ORDER ("mirror the device reduction tree on the CPU side"), with the per-point terms written

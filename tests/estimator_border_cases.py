@@ -1,18 +1,20 @@
 """Inputs of the estimator border tests: shared by test_estimator_borders_gpu.py (HIP path against the oracle) and
 test_estimator_border_inputs_cpu.py (the oracle alone: does every input sit on the border it names?). Not a test module.
 
-Every number below is derived from a named constant of csrc/homography.hip, csrc/homography_rho.hip or csrc/pnp.hip; the constants are
-restated here so that a change of one of them in the source shows up against this table in review."""
+Every number below is derived from a named constant of csrc/homography.hip, csrc/homography_refit.hip, csrc/homography.h,
+csrc/homography_rho.hip or csrc/pnp.hip, and update_num_iters restates csrc/ransac_loop.h; the constants are restated here so that a
+change of one of them in the source shows up against this table in review."""
 import numpy as np
 
-# ---- csrc/homography.hip ---------------------------------------------------------------------------------------------------------------
-HOST_REFIT_MAX = 256                       # refit on the host up to this many selected points, reduce_kernel above
-RED_BLOCKS, RED_THREADS = 64, 256          # reduce_kernel's grid
+# ---- csrc/homography.h, csrc/homography_refit.hip --------------------------------------------------------------------------------------
+HOST_REFIT_MAX = 256                       # homography.h: refit on the host up to this many selected points, reduce_kernel above
+RED_BLOCKS, RED_THREADS = 64, 256          # homography_refit.hip: reduce_kernel's grid
 RED_STRIDE = RED_BLOCKS * RED_THREADS      # 16384: thread (b, t) adds the points b * 256 + t + 16384 j
+# ---- csrc/homography.hip ---------------------------------------------------------------------------------------------------------------
 HT = 8                                     # hypotheses per block of score_kernel
 COOP_PER_BLOCK = 16                        # models per block of hypothesis_coop_kernel
 RANSAC_FIRST_BATCH = 512                   # config().ransac_batch (APDS_RANSAC_BATCH's default, csrc/runtime.cpp)
-RANSAC_MAX_BATCH = 4096                    # find_homography_device: max_batch's cap
+RANSAC_MAX_BATCH = 4096                    # ransac(): max_batch's cap
 SCORE_THREADS = 256                        # score_kernel / pnp_score_kernel: points per pass of a part
 KTH_THREADS = 1024                         # kth_select_kernel's block
 # ---- csrc/homography_rho.hip -----------------------------------------------------------------------------------------------------------
@@ -22,16 +24,27 @@ RHO_GRID_POINTS = RHO_BLOCK * RHO_GRID_CAP  # 262144: above this rho_inlier_bits
 PNP_HT = 4                                 # hypotheses per block of pnp_score_kernel
 PNP_THREADS = 32                           # models per block of pnp_hypothesis_kernel (EPnP)
 P3P_THREADS = 64                           # models per block of p3p_hypothesis_kernel (P3P, AP3P)
-PNP_BATCH = 2048                           # config().pnp_batch
+PNP_BATCH = 2048                           # config().pnp_batch (pnp_ransac_core: batch)
 
 LMEDS, RANSAC, RHO = 4, 8, 16
 
 
-def ransac_batches(max_iters):
-    """The batch sizes B find_homography_device launches while the budget stays at max_iters (first_batch / max_batch / the loop's
-    `iter + B < niters`), and the point parts of each score_kernel launch."""
+def ransac_batch_sizes(max_iters):
+    """first_batch, max_batch of csrc/homography.hip's ransac()"""
     first = max(8, min(RANSAC_FIRST_BATCH, max(max_iters, 8)))
-    cap = max(first, min(RANSAC_MAX_BATCH, max(max_iters, 8)))
+    return first, max(first, min(RANSAC_MAX_BATCH, max(max_iters, 8)))
+
+
+def pnp_batch_size(iterations):
+    """batch of csrc/pnp.hip's pnp_ransac_core, the first and every later batch alike"""
+    return max(PNP_HT, min(PNP_BATCH, max(iterations, 1)))
+
+
+def ransac_batches(max_iters, sizes=None):
+    """The batch sizes B that speculative_ransac (csrc/ransac_loop.h) hands to find_homography_device's launches while the budget stays at
+    max_iters (first_batch / max_batch / the loop's `iter + B < niters`), and the point parts of each score_kernel launch. sizes: another
+    (first, later) pair, e.g. PnP's."""
+    first, cap = sizes or ransac_batch_sizes(max_iters)
     out, it = [], 0
     while it < max(max_iters, 1):
         B = min(first if it == 0 else cap, max(max_iters, 1) - it)
@@ -46,7 +59,7 @@ def score_parts(B, ht=HT):
 
 
 def update_num_iters(p, ep, model_points, max_iters):
-    """cv::RANSACUpdateNumIters (ptsetreg.cpp), restated from OpenCV"""
+    """cv::RANSACUpdateNumIters (ptsetreg.cpp), restated from OpenCV (the product's: update_num_iters in csrc/ransac_loop.h)"""
     p = min(max(p, 0.0), 1.0)
     ep = min(max(ep, 0.0), 1.0)
     num = max(1.0 - p, np.finfo(np.float64).tiny)
