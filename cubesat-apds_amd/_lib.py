@@ -37,10 +37,13 @@ SYMBOLS = [
     "apds_mosaic_create", "apds_mosaic_destroy", "apds_mosaic_info", "apds_mosaic_min_max", "apds_resample_weights", "apds_mosaic_window",
     "apds_mosaic_tile_extract", "apds_mosaic_tile_extract_batch",
     "apds_overview_weights", "apds_mosaic_build_overviews", "apds_mosaic_level_info", "apds_mosaic_best_level", "apds_mosaic_window_level",
+    "apds_akaze_extract_masked", "apds_akaze_extract_batch_masked", "apds_dev_akaze_extract_masked", "apds_dev_akaze_extract_batch_masked",
+    "apds_tile_extract_ex", "apds_tile_extract_batch_ex", "apds_mosaic_tile_extract_ex", "apds_mosaic_tile_extract_batch_ex",
 ]
 
 RESAMPLE_NEAREST, RESAMPLE_LANCZOS = 0, 1
 RESAMPLE_MODES = {"nearest": RESAMPLE_NEAREST, "lanczos": RESAMPLE_LANCZOS}
+TILE_MASK_NONE, TILE_MASK_ALPHA = 0, 1     # APDS_TILE_MASK_*: the mask_mode of the apds_*tile_extract*_ex calls
 
 
 def resample_mode(name):
@@ -255,6 +258,14 @@ def lib():
             "apds_mosaic_level_info": (i, [vp, i, ip, ip]),
             "apds_mosaic_best_level": (i, [vp, i, i, i, i, ip]),
             "apds_mosaic_window_level": (i, [vp, i, i, i, i, i, i, i, i, vp]),
+            "apds_akaze_extract_masked": (i, [vp, i, i, i, sz, vp, sz, i, pp, pp, ip, ip]),
+            "apds_akaze_extract_batch_masked": (i, [vp, i, sz, i, i, i, sz, vp, sz, i, pp, pp, ip, ip]),
+            "apds_dev_akaze_extract_masked": (i, [vp, i, i, i, sz, vp, sz, i, vp, vp, i, ip, vp]),
+            "apds_dev_akaze_extract_batch_masked": (i, [vp, i, sz, i, i, i, sz, vp, sz, sz, i, vp, vp, i, ip, vp]),
+            "apds_tile_extract_ex": (i, [vp, vp, vp, i, i, sz, vp, i, i, pp, pp, ip, ip]),
+            "apds_tile_extract_batch_ex": (i, [vp, vp, vp, i, i, i, sz, vp, i, i, pp, pp, ip, ip]),
+            "apds_mosaic_tile_extract_ex": (i, [vp, i, i, i, i, i, i, i, vp, i, i, pp, pp, ip, ip]),
+            "apds_mosaic_tile_extract_batch_ex": (i, [vp, vp, i, i, i, i, i, i, vp, i, i, pp, pp, ip, ip]),
         }
         for name, (rt, at) in sig.items():
             fn = getattr(L, name)

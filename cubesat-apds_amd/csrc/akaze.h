@@ -105,8 +105,9 @@ void suppress_all_levels(const std::vector<LevelDesc>& ev, const SlabLayout& sl,
 
 // akaze_compact.hip: sub-pixel refinement and ordered compaction (level-major, row-major).
 // All levels of every image of the batch: keypoints to kps + image * capacity (at most `capacity` each), the image's count to kp_base[1] of
-// its slab. APDS_KP_RANKED: the candidates place themselves; 0: two passes over the masks.
-void compact_all_levels(const LevelTable& T, const SlabLayout& sl, apds_keypoint* kps, int capacity, hipStream_t s, const Batch& b);
+// its slab. APDS_KP_RANKED: the candidates place themselves; 0: two passes over the masks. pmask (common.h): the detection mask, applied to
+// the refined positions where the refinement's own drop is - what it removes never counts, so the max_points cut comes after it.
+void compact_all_levels(const LevelTable& T, const SlabLayout& sl, const PixelMask& pmask, apds_keypoint* kps, int capacity, hipStream_t s, const Batch& b);
 // The keypoints of image `bi` (Tb: its level table, bstride 0), all n_all of them, then the `keep` strongest (response descending, ties by
 // detection order) to `out`. The masks are final and filtered: compact_all_levels has run.
 void compact_strongest(const LevelTable& Tb, const SlabLayout& sl, size_t slab_bytes, int bi, int n_all, int keep, apds_keypoint* out, hipStream_t s);

@@ -42,9 +42,20 @@ __device__ __forceinline__ Refined refine(const float* __restrict__ ldet, int co
     return r;
 }
 
-// drop candidates whose refinement is unstable, so bit 0 of the concatenated masks becomes the final keypoint flag (the levels of a
+// The detection mask (KeyPointsFilter::runByPixelsMask behind detectAndCompute's `mask`): a refined keypoint goes iff the mask byte under
+// its rounded position - (int)(pt + 0.5f) per axis, f32 addition, truncation; pt in full-resolution pixels whatever the level - is zero.
+// By construction the rounded position lies inside the image (border >= 1 at every level, pt.x <= W - ratio / 2 - 1 / 2): the clamp is for
+// memory safety alone. A null base is uniform over the launch: no access, no divergence.
+__device__ __forceinline__ bool masked_out(const PixelMask& M, float x, float y) {
+    if (!M.base) return false;
+    const int mx = min(max((int)(x + 0.5f), 0), M.cols - 1);
+    const int my = min(max((int)(y + 0.5f), 0), M.rows - 1);
+    return M.base[(size_t)blockIdx.z * M.img_stride + (size_t)my * M.row_stride + (size_t)mx * M.pix_stride] == 0;
+}
+
+// drop candidates whose refinement is unstable or whose refined position the detection mask excludes, so bit 0 of the concatenated masks becomes the final keypoint flag (the levels of a
 // stage are final by now: no suppression pass reads their masks as victims any more)
-__global__ void subpixel_filter_kernel(LevelTable T, const int* __restrict__ list_count, int lvl0) {
+__global__ void subpixel_filter_kernel(LevelTable T, PixelMask M, const int* __restrict__ list_count, int lvl0) {
     APDS_RAISE_WAVE_PRIORITY();
     const int lvl = lvl0 + blockIdx.y;
     const int cnt = bofs(list_count, T.bstride)[lvl];
@@ -57,7 +68,8 @@ __global__ void subpixel_filter_kernel(LevelTable T, const int* __restrict__ lis
         const size_t p = (size_t)y * T.w[lvl] + x;
         if (!mask[p]) continue;
         const Refined r = refine(ldet, T.w[lvl], x, y, T.ratio[lvl]);
-        if (!r.ok) mask[p] = 2;   // survived the suppression, dropped by the refinement: bit 0 (= "is a keypoint") clear, byte non-zero
+        // survived the suppression, dropped by the refinement or the detection mask: bit 0 (= "is a keypoint") clear, byte non-zero
+        if (!r.ok || masked_out(M, r.x, r.y)) mask[p] = 2;
     }
 }
 
@@ -72,7 +84,8 @@ __global__ void subpixel_filter_kernel(LevelTable T, const int* __restrict__ lis
 // (one cache line of the mask). Same keypoints, same order, same values as the mask-scan path.
 static constexpr uint32_t REF_DEAD = 0xFFFFFFFFu;
 
-__global__ void subpixel_count_kernel(LevelTable T, const int* __restrict__ list_count, int lvl0, int* __restrict__ fine, int* __restrict__ coarse) {
+__global__ void subpixel_count_kernel(LevelTable T, PixelMask M, const int* __restrict__ list_count, int lvl0, int* __restrict__ fine,
+                                      int* __restrict__ coarse) {
     APDS_RAISE_WAVE_PRIORITY();
     const int lvl = lvl0 + blockIdx.y;
     const int cnt = bofs(list_count, T.bstride)[lvl];
@@ -90,8 +103,8 @@ __global__ void subpixel_count_kernel(LevelTable T, const int* __restrict__ list
         Refined r{};
         if (keep) {
             r = refine(ldet, T.w[lvl], x, y, T.ratio[lvl]);
-            if (!r.ok) {
-                mask[p] = 2;   // survived the suppression, dropped by the refinement: bit 0 (= "is a keypoint") clear, byte non-zero
+            if (!r.ok || masked_out(M, r.x, r.y)) {
+                mask[p] = 2;   // survived the suppression, dropped by the refinement or the detection mask: bit 0 (= "is a keypoint") clear, byte non-zero
                 keep = false;
             }
         }
@@ -335,18 +348,18 @@ __global__ __launch_bounds__(256) void rank_select_kernel(const apds_keypoint* _
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-void compact_all_levels(const LevelTable& T, const SlabLayout& sl, apds_keypoint* kps, int capacity, hipStream_t s, const Batch& b) {
+void compact_all_levels(const LevelTable& T, const SlabLayout& sl, const PixelMask& pmask, apds_keypoint* kps, int capacity, hipStream_t s, const Batch& b) {
     const int B = b.n;
     const size_t kp_bstride = (size_t)capacity * sizeof(apds_keypoint);
     if (config().kp_ranked) {
         // the candidates count and place themselves (no pass over the masks)
         const dim3 cgrid(B > 1 ? 16 : 128, T.n, B);
-        hipLaunchKernelGGL(subpixel_count_kernel, cgrid, dim3(256), 0, s, T, (const int*)sl.list_count, 0, sl.fine_counts, sl.coarse_counts);
+        hipLaunchKernelGGL(subpixel_count_kernel, cgrid, dim3(256), 0, s, T, pmask, (const int*)sl.list_count, 0, sl.fine_counts, sl.coarse_counts);
         hipLaunchKernelGGL(kp_scan_fine_kernel, dim3(ceil_div(sl.n_fine, 1024), 1, B), dim3(1024), 0, s, sl.fine_counts, (const int*)sl.coarse_counts, sl.n_fine, sl.kp_base, b.stride);
         hipLaunchKernelGGL(emit_ranked_kernel, cgrid, dim3(256), 0, s, T, (const int*)sl.list_count, 0, (const uint8_t*)sl.mask_all,
                            (const int*)sl.fine_counts, kps, capacity, kp_bstride);
     } else {
-        hipLaunchKernelGGL(subpixel_filter_kernel, dim3(B > 1 ? 16 : 64, T.n, B), dim3(256), 0, s, T, (const int*)sl.list_count, 0);
+        hipLaunchKernelGGL(subpixel_filter_kernel, dim3(B > 1 ? 16 : 64, T.n, B), dim3(256), 0, s, T, pmask, (const int*)sl.list_count, 0);
         const long long lo = 0, hi = sl.total_pix;
         hipLaunchKernelGGL(kp_block_counts_kernel, dim3(sl.nblocks, 1, B), dim3(SCAN_BLOCK), 0, s, (const uint8_t*)sl.mask_all, lo, hi, sl.block_counts, b.stride);
         hipLaunchKernelGGL(kp_scan_offsets_kernel, dim3(1, 1, B), dim3(1024), 0, s, sl.block_counts, sl.nblocks, sl.kp_base, b.stride);

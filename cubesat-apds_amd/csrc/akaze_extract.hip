@@ -381,8 +381,10 @@ void select_strongest(const Frame& f, const LevelTable& T, const int* K, const i
 // feature_extraction/src/lib.rs:61-92 on `n_img` device images of one size (a batch goes through every kernel's grid together:
 // gridDim.z = n_img; a single image is a batch of one). Image i starts `img_bstride` bytes after image i-1; its keypoints go to
 // kps_out + i * capacity, its descriptors to desc64_out + i * capacity * 64, its count to counts[i] (host). Returns the largest count.
-int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, int rows, int cols, int channels, size_t stride, int max_points,
-                               apds_keypoint* kps_out, uint8_t* desc64_out, int capacity, int* counts, hipStream_t s) {
+// pmask: the detection mask (a null base = none): keypoints whose refined position rounds onto a zero byte are dropped before the count,
+// so max_points and `capacity` are about the survivors.
+int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, int rows, int cols, int channels, size_t stride, const PixelMask& pmask,
+                               int max_points, apds_keypoint* kps_out, uint8_t* desc64_out, int capacity, int* counts, hipStream_t s) {
     APDS_REQUIRE(img != nullptr, APDS_ERR_BAD_ARG, "null image");
     APDS_REQUIRE(n_img >= 1 && n_img <= 4096, APDS_ERR_BAD_ARG, "batch must hold 1 .. 4096 images");
     APDS_REQUIRE(channels == 1 || channels == 3 || channels == 4, APDS_ERR_ASSERT, "image must have 1, 3 or 4 channels");
@@ -390,6 +392,12 @@ int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, i
     APDS_REQUIRE(rows < 65536 && cols < 65536, APDS_ERR_ASSERT, "image side must be < 65536");
     APDS_REQUIRE(stride >= (size_t)cols * channels, APDS_ERR_ASSERT, "row stride smaller than a row");
     APDS_REQUIRE(n_img == 1 || img_bstride >= (size_t)rows * stride, APDS_ERR_ASSERT, "image stride smaller than an image");
+    if (pmask.base) {   // detectAndCompute: CV_Assert(mask.empty() || mask.size() == image.size())
+        APDS_REQUIRE(pmask.rows == rows && pmask.cols == cols, APDS_ERR_ASSERT, "mask must have the image's size");
+        APDS_REQUIRE(pmask.pix_stride >= 1 && pmask.row_stride >= (size_t)cols * pmask.pix_stride, APDS_ERR_ASSERT, "mask row stride smaller than a row");
+        APDS_REQUIRE(n_img == 1 || pmask.img_stride == 0 || pmask.img_stride >= (size_t)rows * pmask.row_stride, APDS_ERR_ASSERT,
+                     "mask image stride smaller than a mask");
+    }
     if (max_points <= 0) max_points = APDS_MAX_POINTS;
     ThreadCtx& c = ctx();
     KernelTimer whole("akaze_extract", s);   // whole extraction (all kernels + the count read-backs), for bench.py
@@ -428,7 +436,7 @@ int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, i
     // ---- the keypoint stage: once every level has its Hessian, all levels are made final and emitted
     const LevelTable T = level_table(f);
     suppress_all_levels(f.ev, f.sl, s, f.bt);
-    compact_all_levels(T, f.sl, kps_out, capacity, s, f.bt);
+    compact_all_levels(T, f.sl, pmask, kps_out, capacity, s, f.bt);
     // The image's keypoint count (kp_base[1]) is final here, before orientation and descriptors: its copy to the host goes out now, so that
     // the call can return ~0.3 ms before the stream is idle (APDS_EARLY_COUNT).
     int* K = nullptr;
@@ -470,9 +478,10 @@ int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, i
     return kmax;
 }
 
-int akaze_extract_device(const void* img, int rows, int cols, int channels, size_t stride, int max_points, apds_keypoint* kps_out, uint8_t* desc64_out, int capacity, hipStream_t s) {
+int akaze_extract_device(const void* img, int rows, int cols, int channels, size_t stride, const PixelMask& pmask, int max_points, apds_keypoint* kps_out,
+                         uint8_t* desc64_out, int capacity, hipStream_t s) {
     int count = 0;
-    akaze_extract_batch_device(img, 1, 0, rows, cols, channels, stride, max_points, kps_out, desc64_out, capacity, &count, s);
+    akaze_extract_batch_device(img, 1, 0, rows, cols, channels, stride, pmask, max_points, kps_out, desc64_out, capacity, &count, s);
     return count;
 }
 

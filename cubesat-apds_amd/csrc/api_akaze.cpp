@@ -9,14 +9,46 @@ using namespace apds;
 
 extern "C" {
 
+// APDS_TILE_MASK_ALPHA: the alpha bytes of `n_img` packed BGRA images band_merger has just written are the detection mask - no buffer,
+// no pass; APDS_TILE_MASK_NONE: none
+static PixelMask tile_mask(int mask_mode, const uint8_t* bgra, int rows, int cols) {
+    PixelMask m;
+    if (mask_mode == APDS_TILE_MASK_ALPHA) {
+        m.base = bgra + 3;
+        m.pix_stride = 4;
+        m.row_stride = (size_t)cols * 4;
+        m.img_stride = (size_t)rows * cols * 4;
+        m.rows = rows;
+        m.cols = cols;
+    }
+    return m;
+}
+static void check_mask_mode(int mask_mode) {
+    APDS_REQUIRE(mask_mode == APDS_TILE_MASK_NONE || mask_mode == APDS_TILE_MASK_ALPHA, APDS_ERR_BAD_ARG, "unknown mask_mode");
+}
+
+// a mask plane of the caller's on the device (rows x cols bytes, any strides)
+static PixelMask plane_mask(const void* mask_dev, size_t row_stride, size_t img_stride, int rows, int cols) {
+    PixelMask m;
+    if (mask_dev) {
+        APDS_REQUIRE(row_stride >= (size_t)cols, APDS_ERR_ASSERT, "mask row stride smaller than a row");   // CV_Assert(mask.size() == image.size())
+        m.base = static_cast<const uint8_t*>(mask_dev);
+        m.row_stride = row_stride;
+        m.img_stride = img_stride;
+        m.rows = rows;
+        m.cols = cols;
+    }
+    return m;
+}
+
 // device image -> host keypoints + 61-byte descriptors (malloc'ed, the caller frees them with apds_free)
-static void extract_to_host(ThreadCtx& c, hipStream_t s, const uint8_t* dimg, int rows, int cols, int channels, size_t dstride, int max_points,
-                            apds_keypoint** kps, uint8_t** desc, int* n) {
+static void extract_to_host(ThreadCtx& c, hipStream_t s, const uint8_t* dimg, int rows, int cols, int channels, size_t dstride, const PixelMask& pmask,
+                            int max_points, apds_keypoint** kps, uint8_t** desc, int* n) {
     // strict 3x3 maxima are never adjacent: at most ceil(w/2)*ceil(h/2) per level, and the cap is max_points
     const int capacity = max_points;
     apds_keypoint* dk = c.alloc_n<apds_keypoint>(capacity);
     uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * 64);
-    const int K = akaze_extract_device(dimg, rows, cols, channels, dstride, max_points, dk, dd, capacity, s);
+    const int K = akaze_extract_device(dimg, rows, cols, channels, dstride, pmask, max_points, dk, dd, capacity, s);
     apds_keypoint* hk = static_cast<apds_keypoint*>(std::malloc(std::max<size_t>(1, (size_t)K * sizeof(apds_keypoint))));
     uint8_t* hd = static_cast<uint8_t*>(std::malloc(std::max<size_t>(1, (size_t)K * APDS_DESC_BYTES)));
     if (!hk || !hd) {
@@ -42,9 +74,8 @@ static void extract_to_host(ThreadCtx& c, hipStream_t s, const uint8_t* dimg, in
     *n = K;
 }
 
-int apds_akaze_extract(const uint8_t* img, int rows, int cols, int channels, size_t stride, int max_points, apds_keypoint** kps, uint8_t** desc,
-                       int* n, int* desc_bytes) {
-    APDS_RANGE("apds_akaze_extract");
+static int akaze_extract_host(const uint8_t* img, int rows, int cols, int channels, size_t stride, const uint8_t* mask, size_t mask_stride, int max_points,
+                              apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes) {
     return guarded([&] {
         APDS_REQUIRE(kps && desc && n && desc_bytes, APDS_ERR_BAD_ARG, "null output");
         *kps = nullptr;
@@ -54,6 +85,7 @@ int apds_akaze_extract(const uint8_t* img, int rows, int cols, int channels, siz
         APDS_REQUIRE(img != nullptr && rows > 0 && cols > 0, APDS_ERR_ASSERT, "empty image");   // CV_Assert(!image.empty())
         APDS_REQUIRE(channels == 1 || channels == 3 || channels == 4, APDS_ERR_ASSERT, "image must have 1, 3 or 4 channels");
         APDS_REQUIRE(stride >= (size_t)cols * channels, APDS_ERR_ASSERT, "row stride smaller than a row");
+        APDS_REQUIRE(!mask || mask_stride >= (size_t)cols, APDS_ERR_ASSERT, "mask row stride smaller than a row");   // CV_Assert(mask.size() == image.size())
         if (max_points <= 0) max_points = APDS_MAX_POINTS;
         ThreadCtx& c = ctx();
         c.ws_reset();
@@ -62,14 +94,32 @@ int apds_akaze_extract(const uint8_t* img, int rows, int cols, int channels, siz
         const size_t dstride = (row_bytes + 3) & ~size_t(3);
         uint8_t* dimg = c.alloc_n<uint8_t>(dstride * rows);
         HIP_CHECK(hipMemcpy2DAsync(dimg, dstride, img, stride, row_bytes, rows, hipMemcpyHostToDevice, s));
-        extract_to_host(c, s, dimg, rows, cols, channels, dstride, max_points, kps, desc, n);
+        uint8_t* dmask = nullptr;
+        if (mask) {
+            dmask = c.alloc_n<uint8_t>((size_t)rows * cols);
+            HIP_CHECK(hipMemcpy2DAsync(dmask, cols, mask, mask_stride, cols, rows, hipMemcpyHostToDevice, s));
+        }
+        extract_to_host(c, s, dimg, rows, cols, channels, dstride, plane_mask(dmask, cols, 0, rows, cols), max_points, kps, desc, n);
     });
+}
+
+int apds_akaze_extract(const uint8_t* img, int rows, int cols, int channels, size_t stride, int max_points, apds_keypoint** kps, uint8_t** desc,
+                       int* n, int* desc_bytes) {
+    APDS_RANGE("apds_akaze_extract");
+    return akaze_extract_host(img, rows, cols, channels, stride, nullptr, 0, max_points, kps, desc, n, desc_bytes);
+}
+
+// cv::Feature2D::detectAndCompute(img, mask, ..): the call above passes Mat::default() (feature_extraction/src/lib.rs:75-79)
+int apds_akaze_extract_masked(const uint8_t* img, int rows, int cols, int channels, size_t stride, const uint8_t* mask, size_t mask_stride, int max_points,
+                              apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes) {
+    APDS_RANGE("apds_akaze_extract_masked");
+    return akaze_extract_host(img, rows, cols, channels, stride, mask, mask_stride, max_points, kps, desc, n, desc_bytes);
 }
 
 // One tile of the preprocessor in one call (preprocessor/src/main.rs:258-277): the three f32 band windows go up once, band_merger
 // writes BGRA (geotiff_extractor mod.rs:346-378 fused with homographier raster_to_mat mod.rs:183-197) and AKAZE reads it on the device.
-int apds_tile_extract(const float* red, const float* green, const float* blue, int rows, int cols, size_t row_stride, const double* minmax6,
-                      int max_points, apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes) {
+int apds_tile_extract_ex(const float* red, const float* green, const float* blue, int rows, int cols, size_t row_stride, const double* minmax6,
+                         int max_points, int mask_mode, apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes) {
     APDS_RANGE("apds_tile_extract");
     return guarded([&] {
         APDS_REQUIRE(kps && desc && n && desc_bytes, APDS_ERR_BAD_ARG, "null output");
@@ -78,6 +128,7 @@ int apds_tile_extract(const float* red, const float* green, const float* blue, i
         *n = 0;
         *desc_bytes = APDS_DESC_BYTES;
         APDS_REQUIRE(red && green && blue && minmax6, APDS_ERR_BAD_ARG, "null argument");
+        check_mask_mode(mask_mode);
         APDS_REQUIRE(rows > 0 && cols > 0, APDS_ERR_ASSERT, "empty tile");
         APDS_REQUIRE(row_stride >= (size_t)cols, APDS_ERR_ASSERT, "row stride smaller than a row");
         if (max_points <= 0) max_points = APDS_MAX_POINTS;
@@ -91,8 +142,13 @@ int apds_tile_extract(const float* red, const float* green, const float* blue, i
             HIP_CHECK(hipMemcpy2DAsync(bands + b * px, (size_t)cols * 4, src[b], row_stride * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, s));
         uint8_t* dimg = c.alloc_n<uint8_t>(px * 4);
         band_merger_device(bands, bands + px, bands + 2 * px, px, minmax6, /*bgra=*/1, dimg, s);
-        extract_to_host(c, s, dimg, rows, cols, 4, (size_t)cols * 4, max_points, kps, desc, n);
+        extract_to_host(c, s, dimg, rows, cols, 4, (size_t)cols * 4, tile_mask(mask_mode, dimg, rows, cols), max_points, kps, desc, n);
     });
+}
+
+int apds_tile_extract(const float* red, const float* green, const float* blue, int rows, int cols, size_t row_stride, const double* minmax6,
+                      int max_points, apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes) {
+    return apds_tile_extract_ex(red, green, blue, rows, cols, row_stride, minmax6, max_points, APDS_TILE_MASK_NONE, kps, desc, n, desc_bytes);
 }
 
 // Test hook (tests/test_akaze_gpu.py): run the extraction and copy one intermediate plane of `level` to out_plane.
@@ -159,8 +215,8 @@ static void batch_results_to_host(ThreadCtx& c, hipStream_t s, const apds_keypoi
 // B tiles of the preprocessor in one call (preprocessor/src/main.rs:227-245 spawns one task per tile; 258-277 is the per-tile chain): the
 // band windows of all tiles go up (3 B strided copies), ONE band_merger pass writes the B BGRA images and the batched extraction runs
 // every kernel once for all of them. red / green / blue: n_tiles pointers each (windows of one size, row_stride elements between rows).
-int apds_tile_extract_batch(const float* const* red, const float* const* green, const float* const* blue, int n_tiles, int rows, int cols, size_t row_stride,
-                            const double* minmax6, int max_points, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes) {
+int apds_tile_extract_batch_ex(const float* const* red, const float* const* green, const float* const* blue, int n_tiles, int rows, int cols, size_t row_stride,
+                               const double* minmax6, int max_points, int mask_mode, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes) {
     APDS_RANGE("apds_tile_extract_batch");
     return guarded([&] {
         APDS_REQUIRE(kps && desc && counts && desc_bytes, APDS_ERR_BAD_ARG, "null output");
@@ -168,6 +224,7 @@ int apds_tile_extract_batch(const float* const* red, const float* const* green, 
         *desc = nullptr;
         *desc_bytes = APDS_DESC_BYTES;
         APDS_REQUIRE(red && green && blue && minmax6, APDS_ERR_BAD_ARG, "null argument");
+        check_mask_mode(mask_mode);
         APDS_REQUIRE(n_tiles >= 1 && n_tiles <= 4096, APDS_ERR_BAD_ARG, "batch must hold 1 .. 4096 tiles");
         APDS_REQUIRE(rows > 0 && cols > 0, APDS_ERR_ASSERT, "empty tile");
         APDS_REQUIRE(row_stride >= (size_t)cols, APDS_ERR_ASSERT, "row stride smaller than a row");
@@ -189,15 +246,21 @@ int apds_tile_extract_batch(const float* const* red, const float* const* green, 
         const int capacity = batch_capacity(rows, cols, max_points);
         apds_keypoint* dk = c.alloc_n<apds_keypoint>((size_t)capacity * n_tiles);
         uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * 64 * n_tiles);
-        akaze_extract_batch_device(dimg, n_tiles, px * 4, rows, cols, 4, (size_t)cols * 4, max_points, dk, dd, capacity, counts, s);
+        akaze_extract_batch_device(dimg, n_tiles, px * 4, rows, cols, 4, (size_t)cols * 4, tile_mask(mask_mode, dimg, rows, cols), max_points, dk, dd, capacity,
+                                   counts, s);
         batch_results_to_host(c, s, dk, dd, capacity, n_tiles, counts, kps, desc);
     });
 }
 
+int apds_tile_extract_batch(const float* const* red, const float* const* green, const float* const* blue, int n_tiles, int rows, int cols, size_t row_stride,
+                            const double* minmax6, int max_points, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes) {
+    return apds_tile_extract_batch_ex(red, green, blue, n_tiles, rows, cols, row_stride, minmax6, max_points, APDS_TILE_MASK_NONE, kps, desc, counts, desc_bytes);
+}
+
 // apds_tile_extract on a window of the resident mosaic (geotiff_extractor mod.rs:332-343 read_as(.., Lanczos) in front of the chain): the
 // resampled bands, the BGRA image and the extraction all stay on the device.
-int apds_mosaic_tile_extract(void* mosaic, int x0, int y0, int win_w, int win_h, int out_w, int out_h, int resample, const double* minmax6, int max_points,
-                             apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes) {
+int apds_mosaic_tile_extract_ex(void* mosaic, int x0, int y0, int win_w, int win_h, int out_w, int out_h, int resample, const double* minmax6, int max_points,
+                                int mask_mode, apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes) {
     APDS_RANGE("apds_mosaic_tile_extract");
     return guarded([&] {
         APDS_REQUIRE(kps && desc && n && desc_bytes, APDS_ERR_BAD_ARG, "null output");
@@ -205,6 +268,7 @@ int apds_mosaic_tile_extract(void* mosaic, int x0, int y0, int win_w, int win_h,
         *desc = nullptr;
         *n = 0;
         *desc_bytes = APDS_DESC_BYTES;
+        check_mask_mode(mask_mode);
         Mosaic* m = static_cast<Mosaic*>(mosaic);
         const int32_t xy0[2] = {x0, y0};
         mosaic_check_window(m, 0, xy0, 1, win_w, win_h, out_w, out_h, resample);
@@ -222,20 +286,26 @@ int apds_mosaic_tile_extract(void* mosaic, int x0, int y0, int win_w, int win_h,
         uint8_t* dimg = c.alloc_n<uint8_t>(px * 4);
         mosaic_read_device(m, xy0, 1, win_w, win_h, out_w, out_h, resample, bands, s);
         band_merger_device(bands, bands + px, bands + 2 * px, px, minmax6, /*bgra=*/1, dimg, s);
-        extract_to_host(c, s, dimg, out_h, out_w, 4, (size_t)out_w * 4, max_points, kps, desc, n);
+        extract_to_host(c, s, dimg, out_h, out_w, 4, (size_t)out_w * 4, tile_mask(mask_mode, dimg, out_h, out_w), max_points, kps, desc, n);
     });
+}
+
+int apds_mosaic_tile_extract(void* mosaic, int x0, int y0, int win_w, int win_h, int out_w, int out_h, int resample, const double* minmax6, int max_points,
+                             apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes) {
+    return apds_mosaic_tile_extract_ex(mosaic, x0, y0, win_w, win_h, out_w, out_h, resample, minmax6, max_points, APDS_TILE_MASK_NONE, kps, desc, n, desc_bytes);
 }
 
 // apds_tile_extract_batch on n_tiles windows of the resident mosaic: ONE resampling launch per pass, ONE band_merger pass and ONE batched
 // extraction serve all tiles.
-int apds_mosaic_tile_extract_batch(void* mosaic, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample, const double* minmax6,
-                                   int max_points, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes) {
+int apds_mosaic_tile_extract_batch_ex(void* mosaic, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample,
+                                      const double* minmax6, int max_points, int mask_mode, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes) {
     APDS_RANGE("apds_mosaic_tile_extract_batch");
     return guarded([&] {
         APDS_REQUIRE(kps && desc && counts && desc_bytes, APDS_ERR_BAD_ARG, "null output");
         *kps = nullptr;
         *desc = nullptr;
         *desc_bytes = APDS_DESC_BYTES;
+        check_mask_mode(mask_mode);
         Mosaic* m = static_cast<Mosaic*>(mosaic);
         mosaic_check_window(m, 0, xy0, n_tiles, win_w, win_h, out_w, out_h, resample);
         if (max_points <= 0) max_points = APDS_MAX_POINTS;
@@ -256,16 +326,22 @@ int apds_mosaic_tile_extract_batch(void* mosaic, const int32_t* xy0, int n_tiles
         uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * 64 * n_tiles);
         mosaic_read_device(m, xy0, n_tiles, win_w, win_h, out_w, out_h, resample, bands, s);
         band_merger_device(bands, bands + all, bands + 2 * all, all, minmax6, /*bgra=*/1, dimg, s);
-        akaze_extract_batch_device(dimg, n_tiles, px * 4, out_h, out_w, 4, (size_t)out_w * 4, max_points, dk, dd, capacity, counts, s);
+        akaze_extract_batch_device(dimg, n_tiles, px * 4, out_h, out_w, 4, (size_t)out_w * 4, tile_mask(mask_mode, dimg, out_h, out_w), max_points, dk, dd,
+                                   capacity, counts, s);
         batch_results_to_host(c, s, dk, dd, capacity, n_tiles, counts, kps, desc);
     });
 }
 
+int apds_mosaic_tile_extract_batch(void* mosaic, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample, const double* minmax6,
+                                   int max_points, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes) {
+    return apds_mosaic_tile_extract_batch_ex(mosaic, xy0, n_tiles, win_w, win_h, out_w, out_h, resample, minmax6, max_points, APDS_TILE_MASK_NONE, kps, desc, counts,
+                                             desc_bytes);
+}
+
 // n_images equal-sized host images in one call: one upload, one batched extraction (every kernel's grid covers all images), one download.
 // Outputs: concatenated keypoints / 61-byte descriptors (image 0's rows first), counts[i] rows per image.
-int apds_akaze_extract_batch(const uint8_t* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride, int max_points,
-                             apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes) {
-    APDS_RANGE("apds_akaze_extract_batch");
+static int akaze_extract_batch_host(const uint8_t* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride,
+                                    const uint8_t* const* masks, size_t mask_stride, int max_points, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes) {
     return guarded([&] {
         APDS_REQUIRE(kps && desc && counts && desc_bytes, APDS_ERR_BAD_ARG, "null output");
         *kps = nullptr;
@@ -292,31 +368,70 @@ int apds_akaze_extract_batch(const uint8_t* imgs, int n_images, size_t image_str
         const int capacity = batch_capacity(rows, cols, max_points);
         apds_keypoint* dk = c.alloc_n<apds_keypoint>((size_t)capacity * n_images);
         uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * 64 * n_images);
-        akaze_extract_batch_device(dimg, n_images, dimg_bytes, rows, cols, channels, dstride, max_points, dk, dd, capacity, counts, s);
+        // the masks go into one device buffer, a plane per image; an image without one gets all ones
+        uint8_t* dmask = nullptr;
+        const size_t mpx = (size_t)rows * cols;
+        bool any = false;
+        for (int i = 0; masks && i < n_images; i++) any |= masks[i] != nullptr;
+        if (any) {
+            APDS_REQUIRE(mask_stride >= (size_t)cols, APDS_ERR_ASSERT, "mask row stride smaller than a row");   // CV_Assert(mask.size() == image.size())
+            dmask = c.alloc_n<uint8_t>(mpx * n_images);
+            for (int i = 0; i < n_images; i++) {
+                if (masks[i]) HIP_CHECK(hipMemcpy2DAsync(dmask + i * mpx, cols, masks[i], mask_stride, cols, rows, hipMemcpyHostToDevice, s));
+                else HIP_CHECK(hipMemsetAsync(dmask + i * mpx, 0xFF, mpx, s));
+            }
+        }
+        akaze_extract_batch_device(dimg, n_images, dimg_bytes, rows, cols, channels, dstride, plane_mask(dmask, cols, mpx, rows, cols), max_points, dk, dd, capacity,
+                                   counts, s);
         batch_results_to_host(c, s, dk, dd, capacity, n_images, counts, kps, desc);
+    });
+}
+
+int apds_akaze_extract_batch(const uint8_t* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride, int max_points,
+                             apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes) {
+    APDS_RANGE("apds_akaze_extract_batch");
+    return akaze_extract_batch_host(imgs, n_images, image_stride, rows, cols, channels, stride, nullptr, 0, max_points, kps, desc, counts, desc_bytes);
+}
+
+int apds_akaze_extract_batch_masked(const uint8_t* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride,
+                                    const uint8_t* const* masks, size_t mask_stride, int max_points, apds_keypoint** kps, uint8_t** desc, int* counts,
+                                    int* desc_bytes) {
+    APDS_RANGE("apds_akaze_extract_batch_masked");
+    return akaze_extract_batch_host(imgs, n_images, image_stride, rows, cols, channels, stride, masks, mask_stride, max_points, kps, desc, counts, desc_bytes);
+}
+
+int apds_dev_akaze_extract_batch_masked(const void* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride, const void* mask_dev,
+                                        size_t mask_stride, size_t mask_image_stride, int max_points, void* kps, void* desc64, int capacity, int* counts,
+                                        void* stream) {
+    APDS_RANGE("apds_dev_akaze_extract_batch");
+    return guarded([&] {
+        APDS_REQUIRE(counts && kps && desc64, APDS_ERR_BAD_ARG, "null output");
+        ctx().ws_reset(pick_stream(stream));
+        akaze_extract_batch_device(imgs, n_images, image_stride, rows, cols, channels, stride, plane_mask(mask_dev, mask_stride, mask_image_stride, rows, cols),
+                                   max_points, static_cast<apds_keypoint*>(kps), static_cast<uint8_t*>(desc64), capacity, counts, pick_stream(stream));
     });
 }
 
 int apds_dev_akaze_extract_batch(const void* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride, int max_points,
                                  void* kps, void* desc64, int capacity, int* counts, void* stream) {
-    APDS_RANGE("apds_dev_akaze_extract_batch");
+    return apds_dev_akaze_extract_batch_masked(imgs, n_images, image_stride, rows, cols, channels, stride, nullptr, 0, 0, max_points, kps, desc64, capacity, counts,
+                                               stream);
+}
+
+int apds_dev_akaze_extract_masked(const void* img, int rows, int cols, int channels, size_t stride, const void* mask_dev, size_t mask_stride, int max_points,
+                                  void* kps, void* desc64, int capacity, int* n, void* stream) {
+    APDS_RANGE("apds_dev_akaze_extract");
     return guarded([&] {
-        APDS_REQUIRE(counts && kps && desc64, APDS_ERR_BAD_ARG, "null output");
+        APDS_REQUIRE(n && kps && desc64, APDS_ERR_BAD_ARG, "null output");
         ctx().ws_reset(pick_stream(stream));
-        akaze_extract_batch_device(imgs, n_images, image_stride, rows, cols, channels, stride, max_points, static_cast<apds_keypoint*>(kps),
-                                   static_cast<uint8_t*>(desc64), capacity, counts, pick_stream(stream));
+        *n = akaze_extract_device(img, rows, cols, channels, stride, plane_mask(mask_dev, mask_stride, 0, rows, cols), max_points,
+                                  static_cast<apds_keypoint*>(kps), static_cast<uint8_t*>(desc64), capacity, pick_stream(stream));
     });
 }
 
 int apds_dev_akaze_extract(const void* img, int rows, int cols, int channels, size_t stride, int max_points, void* kps, void* desc64, int capacity,
                            int* n, void* stream) {
-    APDS_RANGE("apds_dev_akaze_extract");
-    return guarded([&] {
-        APDS_REQUIRE(n && kps && desc64, APDS_ERR_BAD_ARG, "null output");
-        ctx().ws_reset(pick_stream(stream));
-        *n = akaze_extract_device(img, rows, cols, channels, stride, max_points, static_cast<apds_keypoint*>(kps), static_cast<uint8_t*>(desc64), capacity,
-                                  pick_stream(stream));
-    });
+    return apds_dev_akaze_extract_masked(img, rows, cols, channels, stride, nullptr, 0, max_points, kps, desc64, capacity, n, stream);
 }
 
 }  // extern "C"

@@ -164,4 +164,15 @@ int guarded(F&& f) {
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// The detection mask of an extraction (cv::Feature2D::detectAndCompute's `mask`), handed to the keypoint kernels by value: one u8 per
+// image pixel on the device, non-zero = keep. Any layout a byte plane can have: a plane of its own, or the alpha bytes of the BGRA image
+// itself (base = image + 3, pix_stride 4).
+struct PixelMask {
+    const uint8_t* base = nullptr;   // null: no mask
+    size_t row_stride = 0;           // bytes between rows
+    size_t pix_stride = 1;           // bytes between pixels of a row
+    size_t img_stride = 0;           // bytes between the masks of consecutive images of a batch; 0: one mask shared by all of them
+    int rows = 0, cols = 0;          // the image's
+};
+
 }  // namespace apds

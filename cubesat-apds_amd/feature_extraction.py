@@ -52,14 +52,31 @@ class ExtractedKeyPoint:
                 for i in range(len(kp))]
 
 
-def akaze_keypoint_descriptor_extraction_def(img, max_points=None):
-    """lib.rs:61-92 — AKAZE(MLDB, 0, 3, 0.001, 4 octaves, 4 layers, PM_G2, max_points or MAX_POINTS).detectAndCompute.
-    img: HxW, HxWx3 (BGR) or HxWx4 (BGRA) uint8."""
+def _image(img):
     img = np.asarray(img)
     if img.dtype != np.uint8 or img.ndim not in (2, 3) or img.size == 0:
         raise ApdsError(_lib.ERR_ASSERT, "image must be a non-empty uint8 HxW[xC] array")
     if not img.flags["C_CONTIGUOUS"] and not (img.ndim == 3 and img.strides[2] == 1 and img.strides[1] == img.shape[2]):
         img = np.ascontiguousarray(img)
+    return img
+
+
+def _mask_plane(mask, h, w):
+    """detectAndCompute's mask: uint8 (or bool) HxW of the image's size (OpenCV asserts it); rows may be strided, as a Mat's may."""
+    m = np.asarray(mask)
+    if m.dtype == np.bool_:
+        m = m.view(np.uint8)
+    if m.dtype != np.uint8 or m.shape != (h, w):
+        raise ApdsError(_lib.ERR_ASSERT, "mask must be a uint8 array of the image's height and width")
+    if m.strides[1] != 1 or m.strides[0] < w:
+        m = np.ascontiguousarray(m)
+    return m
+
+
+def akaze_keypoint_descriptor_extraction_def(img, max_points=None):
+    """lib.rs:61-92 — AKAZE(MLDB, 0, 3, 0.001, 4 octaves, 4 layers, PM_G2, max_points or MAX_POINTS).detectAndCompute.
+    img: HxW, HxWx3 (BGR) or HxWx4 (BGRA) uint8."""
+    img = _image(img)
     ch = 1 if img.ndim == 2 else img.shape[2]
     kps, desc = C.c_void_p(), C.c_void_p()
     n, nb = C.c_int(0), C.c_int(0)
@@ -71,11 +88,31 @@ def akaze_keypoint_descriptor_extraction_def(img, max_points=None):
     return ExtractedKeyPoint(k, d)
 
 
-def akaze_keypoint_descriptor_extraction_batch(imgs, max_points=None):
+def akaze_keypoint_descriptor_extraction(img, mask=None, max_points=None):
+    """The same call with the mask argument lib.rs:75-79 leaves empty (`&Mat::default()`): detection runs unmasked, then a keypoint goes iff
+    mask[int(y + 0.5), int(x + 0.5)] == 0 (f32, truncation; x, y the refined full-resolution position), and max_points cuts what is left.
+    mask: uint8 HxW, non-zero = keep; None = akaze_keypoint_descriptor_extraction_def."""
+    if mask is None:
+        return akaze_keypoint_descriptor_extraction_def(img, max_points)
+    img = _image(img)
+    m = _mask_plane(mask, img.shape[0], img.shape[1])
+    ch = 1 if img.ndim == 2 else img.shape[2]
+    kps, desc = C.c_void_p(), C.c_void_p()
+    n, nb = C.c_int(0), C.c_int(0)
+    check(lib().apds_akaze_extract_masked(ptr(img), img.shape[0], img.shape[1], ch, img.strides[0], ptr(m), m.strides[0],
+                                          MAX_POINTS if max_points is None else int(max_points),
+                                          C.byref(kps), C.byref(desc), C.byref(n), C.byref(nb)))
+    k = take(kps, n.value, KEYPOINT_DTYPE)
+    d = take(desc, n.value * nb.value, np.uint8).reshape(n.value, nb.value)
+    return ExtractedKeyPoint(k, d)
+
+
+def akaze_keypoint_descriptor_extraction_batch(imgs, max_points=None, mask=None):
     """lib.rs:61-92 for a batch of equal-sized images (array [B, H, W] or [B, H, W, C] uint8, or a list of such images) in ONE library
     call: the batch goes through every kernel's grid together. Returns a list of ExtractedKeyPoint, each exactly what
     akaze_keypoint_descriptor_extraction_def returns for that image. This is how a caller that extracts one tile per task
-    (preprocessor/src/main.rs:227-245,277) should hand its tiles over: a single small tile is launch-latency-bound."""
+    (preprocessor/src/main.rs:227-245,277) should hand its tiles over: a single small tile is launch-latency-bound.
+    mask: None, or one entry per image, each None or a mask as akaze_keypoint_descriptor_extraction takes it."""
     a = np.ascontiguousarray(np.stack([np.asarray(i) for i in imgs]) if isinstance(imgs, (list, tuple)) else np.asarray(imgs))
     if a.dtype != np.uint8 or a.ndim not in (3, 4) or a.size == 0:
         raise ApdsError(_lib.ERR_ASSERT, "images must be a non-empty uint8 [B, H, W[, C]] array")
@@ -83,8 +120,16 @@ def akaze_keypoint_descriptor_extraction_batch(imgs, max_points=None):
     ch = 1 if a.ndim == 3 else a.shape[3]
     kps, desc = C.c_void_p(), C.c_void_p()
     counts, nb = (C.c_int * b)(), C.c_int(0)
-    check(lib().apds_akaze_extract_batch(ptr(a), b, a.strides[0], h, w, ch, a.strides[1], MAX_POINTS if max_points is None else int(max_points),
-                                         C.byref(kps), C.byref(desc), counts, C.byref(nb)))
+    mp = MAX_POINTS if max_points is None else int(max_points)
+    if mask is None:
+        check(lib().apds_akaze_extract_batch(ptr(a), b, a.strides[0], h, w, ch, a.strides[1], mp, C.byref(kps), C.byref(desc), counts, C.byref(nb)))
+    else:
+        if len(mask) != b:
+            raise ApdsError(_lib.ERR_ASSERT, "one mask (or None) per image")
+        planes = [None if m is None else np.ascontiguousarray(_mask_plane(m, h, w)) for m in mask]      # one row stride for all: packed
+        mptrs = (C.c_void_p * b)(*[None if m is None else m.ctypes.data for m in planes])
+        check(lib().apds_akaze_extract_batch_masked(ptr(a), b, a.strides[0], h, w, ch, a.strides[1], mptrs, w, mp, C.byref(kps), C.byref(desc), counts,
+                                                    C.byref(nb)))
     total = sum(counts)
     k = take(kps, total, KEYPOINT_DTYPE)
     d = take(desc, total * nb.value, np.uint8).reshape(total, nb.value)
@@ -95,10 +140,15 @@ def akaze_keypoint_descriptor_extraction_batch(imgs, max_points=None):
     return out
 
 
-def tile_keypoint_descriptor_extraction(red, green, blue, min_max, max_points=None):
+def _mask_mode(mask_nodata):
+    return _lib.TILE_MASK_ALPHA if mask_nodata else _lib.TILE_MASK_NONE
+
+
+def tile_keypoint_descriptor_extraction(red, green, blue, min_max, max_points=None, mask_nodata=False):
     """One preprocessor tile (preprocessor/src/main.rs:258-277): to_rgb's band_merger, raster_to_mat and the extraction above in one
     library call — red/green/blue are equal-shape 2-D float32 views (row-strided views into the mosaic are taken as they are), the
-    RGBA/BGRA image exists on the device only. Same result as the three separate calls."""
+    RGBA/BGRA image exists on the device only. Same result as the three separate calls. mask_nodata: the tile's alpha (0 where all three
+    bands are NaN) is the extraction's mask, as akaze_keypoint_descriptor_extraction(tile, mask=tile[..., 3]) would apply it."""
     bands = [np.asarray(b) for b in (red, green, blue)]
     h, w = bands[0].shape
     if any(b.dtype != np.float32 or b.ndim != 2 or b.shape != (h, w) for b in bands) or h == 0 or w == 0:
@@ -110,14 +160,15 @@ def tile_keypoint_descriptor_extraction(red, green, blue, min_max, max_points=No
     mm = min_max.as_array()
     kps, desc = C.c_void_p(), C.c_void_p()
     n, nb = C.c_int(0), C.c_int(0)
-    check(lib().apds_tile_extract(bands[0].ctypes.data, bands[1].ctypes.data, bands[2].ctypes.data, h, w, stride // 4, ptr(mm),
-                                  MAX_POINTS if max_points is None else int(max_points), C.byref(kps), C.byref(desc), C.byref(n), C.byref(nb)))
+    check(lib().apds_tile_extract_ex(bands[0].ctypes.data, bands[1].ctypes.data, bands[2].ctypes.data, h, w, stride // 4, ptr(mm),
+                                     MAX_POINTS if max_points is None else int(max_points), _mask_mode(mask_nodata), C.byref(kps), C.byref(desc), C.byref(n),
+                                     C.byref(nb)))
     k = take(kps, n.value, KEYPOINT_DTYPE)
     d = take(desc, n.value * nb.value, np.uint8).reshape(n.value, nb.value)
     return ExtractedKeyPoint(k, d)
 
 
-def tiles_keypoint_descriptor_extraction(windows, min_max, max_points=None):
+def tiles_keypoint_descriptor_extraction(windows, min_max, max_points=None, mask_nodata=False):
     """A batch of preprocessor tiles in ONE library call: `windows` = list of [3, h, w] float32 band windows of one size (strided views
     into the mosaic are taken as they are). Returns a list of ExtractedKeyPoint, each exactly what tile_keypoint_descriptor_extraction
     returns for that tile."""
@@ -137,8 +188,8 @@ def tiles_keypoint_descriptor_extraction(windows, min_max, max_points=None):
     mm = min_max.as_array()
     kps, desc = C.c_void_p(), C.c_void_p()
     counts, nb = (C.c_int * b)(), C.c_int(0)
-    check(lib().apds_tile_extract_batch(ptrs[0], ptrs[1], ptrs[2], b, h, w, stride // 4, ptr(mm), MAX_POINTS if max_points is None else int(max_points),
-                                        C.byref(kps), C.byref(desc), counts, C.byref(nb)))
+    check(lib().apds_tile_extract_batch_ex(ptrs[0], ptrs[1], ptrs[2], b, h, w, stride // 4, ptr(mm), MAX_POINTS if max_points is None else int(max_points),
+                                           _mask_mode(mask_nodata), C.byref(kps), C.byref(desc), counts, C.byref(nb)))
     total = sum(counts)
     k = take(kps, total, KEYPOINT_DTYPE)
     d = take(desc, total * nb.value, np.uint8).reshape(total, nb.value)
@@ -149,22 +200,23 @@ def tiles_keypoint_descriptor_extraction(windows, min_max, max_points=None):
     return out
 
 
-def mosaic_tile_keypoint_descriptor_extraction(mosaic, window, window_size, size, resample="nearest", min_max=None, max_points=None):
+def mosaic_tile_keypoint_descriptor_extraction(mosaic, window, window_size, size, resample="nearest", min_max=None, max_points=None, mask_nodata=False):
     """tile_keypoint_descriptor_extraction on a window of a geotiff_extractor.DeviceMosaic: window (x, y) and window_size (w, h) in raster
     pixels, resampled to size (w, h) on the device ("nearest" | "lanczos"), then band_merger, raster_to_mat and the extraction, all in one
-    library call. min_max None = the mosaic's own."""
+    library call. min_max None = the mosaic's own. mask_nodata: as in tile_keypoint_descriptor_extraction (under "lanczos" a NaN spreads over
+    the filter footprint, and so does the masked area)."""
     mm = None if min_max is None else min_max.as_array()
     kps, desc = C.c_void_p(), C.c_void_p()
     n, nb = C.c_int(0), C.c_int(0)
-    check(lib().apds_mosaic_tile_extract(mosaic.handle, int(window[0]), int(window[1]), int(window_size[0]), int(window_size[1]), int(size[0]), int(size[1]),
-                                         _lib.resample_mode(resample), None if mm is None else ptr(mm), MAX_POINTS if max_points is None else int(max_points),
-                                         C.byref(kps), C.byref(desc), C.byref(n), C.byref(nb)))
+    check(lib().apds_mosaic_tile_extract_ex(mosaic.handle, int(window[0]), int(window[1]), int(window_size[0]), int(window_size[1]), int(size[0]), int(size[1]),
+                                            _lib.resample_mode(resample), None if mm is None else ptr(mm), MAX_POINTS if max_points is None else int(max_points),
+                                            _mask_mode(mask_nodata), C.byref(kps), C.byref(desc), C.byref(n), C.byref(nb)))
     k = take(kps, n.value, KEYPOINT_DTYPE)
     d = take(desc, n.value * nb.value, np.uint8).reshape(n.value, nb.value)
     return ExtractedKeyPoint(k, d)
 
 
-def mosaic_tiles_keypoint_descriptor_extraction(mosaic, windows, window_size, size, resample="nearest", min_max=None, max_points=None):
+def mosaic_tiles_keypoint_descriptor_extraction(mosaic, windows, window_size, size, resample="nearest", min_max=None, max_points=None, mask_nodata=False):
     """A batch of tiles of a DeviceMosaic in ONE library call: `windows` = list of (x, y) origins of one window_size and size. Returns a
     list of ExtractedKeyPoint, each exactly what mosaic_tile_keypoint_descriptor_extraction returns for that tile."""
     xy = np.ascontiguousarray(np.asarray(list(windows), np.int64).reshape(-1, 2), np.int32)
@@ -174,9 +226,10 @@ def mosaic_tiles_keypoint_descriptor_extraction(mosaic, windows, window_size, si
     mm = None if min_max is None else min_max.as_array()
     kps, desc = C.c_void_p(), C.c_void_p()
     counts, nb = (C.c_int * b)(), C.c_int(0)
-    check(lib().apds_mosaic_tile_extract_batch(mosaic.handle, ptr(xy), b, int(window_size[0]), int(window_size[1]), int(size[0]), int(size[1]),
-                                               _lib.resample_mode(resample), None if mm is None else ptr(mm),
-                                               MAX_POINTS if max_points is None else int(max_points), C.byref(kps), C.byref(desc), counts, C.byref(nb)))
+    check(lib().apds_mosaic_tile_extract_batch_ex(mosaic.handle, ptr(xy), b, int(window_size[0]), int(window_size[1]), int(size[0]), int(size[1]),
+                                                  _lib.resample_mode(resample), None if mm is None else ptr(mm),
+                                                  MAX_POINTS if max_points is None else int(max_points), _mask_mode(mask_nodata), C.byref(kps), C.byref(desc),
+                                                  counts, C.byref(nb)))
     total = sum(counts)
     k = take(kps, total, KEYPOINT_DTYPE)
     d = take(desc, total * nb.value, np.uint8).reshape(total, nb.value)

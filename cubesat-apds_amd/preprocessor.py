@@ -27,21 +27,26 @@ def tile_grid(image_resolution, amount_lod, lod):
     return tile_size, columns, rows
 
 
-def extract_tile(dataset, tile_size, column, row, lod, fused=True, resample="nearest"):
+def extract_tile(dataset, tile_size, column, row, lod, fused=True, resample="nearest", mask_nodata=False):
     """main.rs:258-277 — the part of one tile that does not touch the database: read, convert, extract. Thread-safe (the C ABI
     gives every calling thread its own stream and workspace, as the reference's rayon workers each own their OpenCV objects).
     resample: how a level > 0 window becomes a tile ("nearest", or "lanczos" as the reference reads it, mod.rs:339). A DeviceMosaic
-    dataset is read, resampled and extracted on the device in one call."""
+    dataset is read, resampled and extracted on the device in one call.
+    mask_nodata: the tile's alpha, which band_merger sets to 0 where all three bands are NaN (mod.rs:346-378) and the reference never reads
+    again, is the extraction's mask (detectAndCompute's `mask`, empty at lib.rs:75-79): the edges of a nodata area leave no rows."""
     span = (tile_size[0] * 2 ** lod, tile_size[1] * 2 ** lod)
     if isinstance(dataset, DeviceMosaic):
-        return feature_extraction.mosaic_tile_keypoint_descriptor_extraction(dataset, (column * span[0], row * span[1]), span, tile_size, resample)
+        return feature_extraction.mosaic_tile_keypoint_descriptor_extraction(dataset, (column * span[0], row * span[1]), span, tile_size, resample,
+                                                                             mask_nodata=mask_nodata)
     extra = {} if resample == "nearest" else {"resample": resample}
     if fused:
         # the same three steps inside the library: the band windows go to the GPU once and the 8-bit image never comes back
         win = dataset.window((column * span[0], row * span[1]), span, tile_size, **extra)
-        return feature_extraction.tile_keypoint_descriptor_extraction(win[0], win[1], win[2], dataset.datasets_min_max(), None)
+        return feature_extraction.tile_keypoint_descriptor_extraction(win[0], win[1], win[2], dataset.datasets_min_max(), None, mask_nodata)
     tile = dataset.to_rgb((column * span[0], row * span[1]), span, tile_size, **extra)            # main.rs:258-272
     tile_mat = homographier.raster_to_mat(tile, tile_size[0], tile_size[1])                       # main.rs:274
+    if mask_nodata:
+        return feature_extraction.akaze_keypoint_descriptor_extraction(tile_mat.mat, tile_mat.mat[..., 3], None)
     return feature_extraction.akaze_keypoint_descriptor_extraction_def(tile_mat.mat, None)        # main.rs:277
 
 
@@ -55,18 +60,19 @@ def store_tile(table, images, keypoints, tile_size, column, row, lod):
     return image_id, len(keypoints.keypoints)
 
 
-def feature_extraction_to_database(table, images, dataset, tile_size, column, row, lod, fused=True, resample="nearest"):
+def feature_extraction_to_database(table, images, dataset, tile_size, column, row, lod, fused=True, resample="nearest", mask_nodata=False):
     """main.rs:248-327 — one tile: read, convert, extract, insert the image row and its keypoints. Returns (image_id, n_keypoints)."""
-    return store_tile(table, images, extract_tile(dataset, tile_size, column, row, lod, fused, resample), tile_size, column, row, lod)
+    return store_tile(table, images, extract_tile(dataset, tile_size, column, row, lod, fused, resample, mask_nodata), tile_size, column, row, lod)
 
 
-def downscale_from_lod(table, images, dataset, amount_lod, lod, workers=1, fused=True, batch=1, resample="nearest"):
+def downscale_from_lod(table, images, dataset, amount_lod, lod, workers=1, fused=True, batch=1, resample="nearest", mask_nodata=False):
     """main.rs:197-246 — every tile of one level. The reference spawns the tiles on a rayon pool (main.rs:233-243) and image ids
     follow whatever order the inserts reach Postgres in; here the rows are stored in row-major tile order, so ids and table contents
     depend neither on `workers` nor on `batch`. Small tiles are launch-latency-bound on the GPU, so either `batch` tiles go through
     ONE library call (apds_tile_extract_batch: every kernel's grid covers all of them; the preferred form, one host thread) or
     `workers` threads extract tiles concurrently on their own streams. With a DeviceMosaic dataset the batch call is
-    apds_mosaic_tile_extract_batch: one resampling launch per pass for the whole group, no band window crosses PCIe."""
+    apds_mosaic_tile_extract_batch: one resampling launch per pass for the whole group, no band window crosses PCIe.
+    mask_nodata (see extract_tile) reaches all three forms."""
     tile_size, columns, rows = tile_grid(dataset.raster_size(), amount_lod, lod)
     cells = [(j, i) for i in range(rows) for j in range(columns)]
     extra = {} if resample == "nearest" else {"resample": resample}
@@ -77,21 +83,21 @@ def downscale_from_lod(table, images, dataset, amount_lod, lod, workers=1, fused
             group = cells[k:k + batch]
             if isinstance(dataset, DeviceMosaic):
                 extracted = feature_extraction.mosaic_tiles_keypoint_descriptor_extraction(dataset, [(j * span[0], i * span[1]) for j, i in group], span,
-                                                                                           tile_size, resample)
+                                                                                           tile_size, resample, mask_nodata=mask_nodata)
             else:
                 wins = [dataset.window((j * span[0], i * span[1]), span, tile_size, **extra) for j, i in group]
-                extracted = feature_extraction.tiles_keypoint_descriptor_extraction(wins, dataset.datasets_min_max(), None)
+                extracted = feature_extraction.tiles_keypoint_descriptor_extraction(wins, dataset.datasets_min_max(), None, mask_nodata)
             for (j, i), kp in zip(group, extracted):
                 out.append(store_tile(table, images, kp, tile_size, j, i, lod))
         return out
     if workers <= 1:
-        return [feature_extraction_to_database(table, images, dataset, tile_size, j, i, lod, fused, resample) for j, i in cells]
+        return [feature_extraction_to_database(table, images, dataset, tile_size, j, i, lod, fused, resample, mask_nodata) for j, i in cells]
     from concurrent.futures import ThreadPoolExecutor, wait
     import threading
     from ._lib import lib
 
     def work(cell):
-        return extract_tile(dataset, tile_size, cell[0], cell[1], lod, fused, resample)
+        return extract_tile(dataset, tile_size, cell[0], cell[1], lod, fused, resample, mask_nodata)
 
     # every pool thread gives its stream + device workspace back before the pool goes away: the barrier makes each of the
     # `workers` threads take exactly one release task
@@ -134,6 +140,6 @@ def downscale_from_lod(table, images, dataset, amount_lod, lod, workers=1, fused
     return out
 
 
-def process_lod_from_mosaic(table, images, dataset, lod, workers=1, fused=True, batch=1, resample="nearest"):
+def process_lod_from_mosaic(table, images, dataset, lod, workers=1, fused=True, batch=1, resample="nearest", mask_nodata=False):
     """main.rs:175-194 — all levels 0 .. lod-1."""
-    return [downscale_from_lod(table, images, dataset, lod, i, workers, fused, batch, resample) for i in range(lod)]
+    return [downscale_from_lod(table, images, dataset, lod, i, workers, fused, batch, resample, mask_nodata) for i in range(lod)]

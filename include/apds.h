@@ -84,6 +84,19 @@ int apds_akaze_extract(const uint8_t* img, int rows, int cols, int channels, siz
  * of apds_akaze_extract. Outputs: *kps / *desc hold the images' rows back to back (image 0 first), counts[i] = rows of image i. */
 int apds_akaze_extract_batch(const uint8_t* imgs, int n_images, size_t image_stride_bytes, int rows, int cols, int channels, size_t stride_bytes,
                              int max_points, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes);
+/* The same two calls with detectAndCompute's `mask` argument, which lib.rs:75-79 leaves empty (OpenCV 4.8 AKAZE_Impl::detectAndCompute ->
+ * KeyPointsFilter::runByPixelsMask, restated from memory: DESIGN.md section 2). Detection runs unmasked; then a keypoint is removed iff
+ * mask[(int)(pt.y + 0.5f)][(int)(pt.x + 0.5f)] == 0 - pt the refined position in full-resolution pixels whatever its level, f32 additions,
+ * truncation. The survivors keep their order and every field and descriptor byte of the unmasked call; the max_points cut (strongest
+ * responses, ties by detection order) comes AFTER the mask. mask: rows x cols u8, mask_stride_bytes between rows, any non-zero value keeps.
+ * A NULL mask is the unmasked call; mask_stride_bytes < cols is APDS_ERR_ASSERT (OpenCV asserts mask.size() == image.size()).
+ * Batch form: masks = n_images pointers (or NULL: no mask at all), any of them NULL = that image unmasked; one mask_stride_bytes for all.
+ * Not eroded by keypoint size or descriptor support: a caller who wants that erodes the mask. */
+int apds_akaze_extract_masked(const uint8_t* img, int rows, int cols, int channels, size_t stride_bytes, const uint8_t* mask, size_t mask_stride_bytes,
+                              int max_points, apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes);
+int apds_akaze_extract_batch_masked(const uint8_t* imgs, int n_images, size_t image_stride_bytes, int rows, int cols, int channels, size_t stride_bytes,
+                                    const uint8_t* const* masks, size_t mask_stride_bytes, int max_points, apds_keypoint** kps, uint8_t** desc, int* counts,
+                                    int* desc_bytes);
 
 /* lib.rs:94-114  get_knn_matches(origin_desc, target_desc, k, filter_strength) -> Vector<DMatch>
  * Hamming k-NN of each origin (query) row over the target (train) rows, then keep m[0] iff
@@ -140,6 +153,20 @@ int apds_tile_extract(const float* red, const float* green, const float* blue, i
  * tiles. Per-tile results are exactly those of apds_tile_extract. Outputs as apds_akaze_extract_batch. */
 int apds_tile_extract_batch(const float* const* red, const float* const* green, const float* const* blue, int n_tiles, int rows, int cols, size_t row_stride,
                             const double* minmax6, int max_points, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes);
+/* The tile calls (these two and the two apds_mosaic_tile_extract calls below) with a detection mask made of the tile's own nodata: the _ex
+ * forms take one more argument, mask_mode. APDS_TILE_MASK_NONE is exactly the call without _ex. APDS_TILE_MASK_ALPHA masks the extraction
+ * (the rule of apds_akaze_extract_masked) with the alpha byte of the BGRA image band_merger has just written on the device: a keypoint whose
+ * refined position rounds onto a pixel of alpha 0 is removed. No mask buffer is allocated and no pass is added: the kernels read the
+ * image's own fourth byte. The alpha rule is band_merger's and unchanged: alpha 0 only where ALL three bands are NaN (a pixel that lost one
+ * or two bands keeps alpha 255 and masks nothing). Under APDS_RESAMPLE_LANCZOS a NaN propagates through every tap that touches it, so the
+ * masked area is the nodata area widened by the filter footprint (three source pixels times max(1, win / out) on every side). Any other
+ * mask_mode is APDS_ERR_BAD_ARG. Results equal apds_akaze_extract_masked on the BGRA tile with mask = its alpha plane. */
+#define APDS_TILE_MASK_NONE 0
+#define APDS_TILE_MASK_ALPHA 1
+int apds_tile_extract_ex(const float* red, const float* green, const float* blue, int rows, int cols, size_t row_stride, const double* minmax6,
+                         int max_points, int mask_mode, apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes);
+int apds_tile_extract_batch_ex(const float* const* red, const float* const* green, const float* const* blue, int n_tiles, int rows, int cols, size_t row_stride,
+                               const double* minmax6, int max_points, int mask_mode, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes);
 
 /* The mosaic resident in HBM and the preprocessor's window read on it: geotiff_extractor/src/image_extractor/mod.rs:332-343
  * read_as::<f32>(window, window_size, size, Some(ResampleAlg::Lanczos)), which preprocessor/src/main.rs:197-277 cuts every level of detail
@@ -175,6 +202,11 @@ int apds_mosaic_tile_extract(void* mosaic, int x0, int y0, int win_w, int win_h,
                              apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes);
 int apds_mosaic_tile_extract_batch(void* mosaic, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample, const double* minmax6,
                                    int max_points, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes);
+/* with mask_mode (APDS_TILE_MASK_*, see apds_tile_extract_ex) */
+int apds_mosaic_tile_extract_ex(void* mosaic, int x0, int y0, int win_w, int win_h, int out_w, int out_h, int resample, const double* minmax6, int max_points,
+                                int mask_mode, apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes);
+int apds_mosaic_tile_extract_batch_ex(void* mosaic, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample,
+                                      const double* minmax6, int max_points, int mask_mode, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes);
 
 /* The overview pyramid of the mosaic. The preprocessor opens its dataset as a COG (preprocessor/src/main.rs:142-161,
  * geotiff_extractor/src/image_extractor/mod.rs:141-164), and a COG carries overviews: GDAL serves read_as(window, tile * 2^lod, tile, ..)
@@ -533,6 +565,14 @@ int apds_dev_akaze_extract(const void* img, int rows, int cols, int channels, si
  * its count in counts[i] (host). capacity (rows per image) >= the largest count. */
 int apds_dev_akaze_extract_batch(const void* imgs, int n_images, size_t image_stride_bytes, int rows, int cols, int channels, size_t stride_bytes,
                                  int max_points, void* kps, void* desc64, int capacity, int* counts, void* stream);
+/* The two calls above with a detection mask on the device (the rule of apds_akaze_extract_masked): mask_dev = rows x cols u8,
+ * mask_stride_bytes between rows (< cols: APDS_ERR_ASSERT); NULL = unmasked. Batch: image i's mask starts i * mask_image_stride_bytes after
+ * mask_dev, 0 = one mask shared by every image. counts and capacity are about the survivors: capacity >= the largest masked count. */
+int apds_dev_akaze_extract_masked(const void* img, int rows, int cols, int channels, size_t stride_bytes, const void* mask_dev, size_t mask_stride_bytes,
+                                  int max_points, void* kps, void* desc64, int capacity, int* n, void* stream);
+int apds_dev_akaze_extract_batch_masked(const void* imgs, int n_images, size_t image_stride_bytes, int rows, int cols, int channels, size_t stride_bytes,
+                                        const void* mask_dev, size_t mask_stride_bytes, size_t mask_image_stride_bytes, int max_points, void* kps, void* desc64,
+                                        int capacity, int* counts, void* stream);
 
 /* gather matched coordinates on the device: pts1/pts2 n_matches x 2 float */
 int apds_dev_points_from_matches(const void* kp1, int n1, const void* kp2, int n2, const void* matches, int n_matches,

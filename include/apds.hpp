@@ -306,6 +306,25 @@ inline Result<ExtractedKeyPoint, Error> akaze_keypoint_descriptor_extraction_def
     apds_free(desc);
     return R::Ok(std::move(out));
 }
+/// The same with detectAndCompute's `mask` (lib.rs:75-79 passes Mat::default()): rows x cols u8, non-zero = keep, nullptr = unmasked. A keypoint
+/// goes iff mask[(int)(y + 0.5f)][(int)(x + 0.5f)] == 0 at its refined position; max_points cuts what is left.
+inline Result<ExtractedKeyPoint, Error> akaze_keypoint_descriptor_extraction(const uint8_t* img, int rows, int cols, int channels, size_t stride_bytes,
+                                                                            const uint8_t* mask, size_t mask_stride_bytes, std::optional<int> max_points) {
+    using R = Result<ExtractedKeyPoint, Error>;
+    apds_keypoint* kps = nullptr;
+    uint8_t* desc = nullptr;
+    int n = 0, nb = 0;
+    const int rc = apds_akaze_extract_masked(img, rows, cols, channels, stride_bytes, mask, mask_stride_bytes, max_points.value_or(MAX_POINTS), &kps, &desc, &n, &nb);
+    if (rc != 0) return R::Err(last_error(rc));
+    ExtractedKeyPoint out;
+    out.keypoints.assign(kps, kps + n);
+    out.descriptors.rows = n;
+    out.descriptors.cols = nb;
+    out.descriptors.data.assign(desc, desc + (size_t)n * nb);
+    apds_free(kps);
+    apds_free(desc);
+    return R::Ok(std::move(out));
+}
 inline Result<ExtractedKeyPoint, Error> akaze_keypoint_descriptor_extraction_def(const Mat<Vec4b>& img, std::optional<int> max_points) {
     return akaze_keypoint_descriptor_extraction_def(reinterpret_cast<const uint8_t*>(img.data.data()), img.rows, img.cols, 4, (size_t)img.cols * 4, max_points);
 }

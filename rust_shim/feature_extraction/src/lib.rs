@@ -68,11 +68,28 @@ impl ExtractedKeyPoint {
 
 /// lib.rs:61-92
 pub fn akaze_keypoint_descriptor_extraction_def(img: &Mat, max_points: Option<i32>) -> Result<ExtractedKeyPoint, Error> {
+    akaze_keypoint_descriptor_extraction(img, &Mat::default(), max_points)
+}
+
+/// lib.rs:61-92 with the `mask` of detect_and_compute (lib.rs:75-79 passes `&Mat::default()`): CV_8U, the image's size, non-zero = keep;
+/// an empty mask is the unmasked call. Keypoints whose refined position rounds onto a zero byte go; max_points cuts what is left.
+pub fn akaze_keypoint_descriptor_extraction(img: &Mat, mask: &Mat, max_points: Option<i32>) -> Result<ExtractedKeyPoint, Error> {
     let (mut kps, mut desc, mut n, mut nb) = (ptr::null_mut(), ptr::null_mut(), 0i32, 0i32);
     let stride = img.step1(0)? * img.elem_size1();
-    let rc = unsafe {
-        apds_sys::apds_akaze_extract(img.data(), img.rows(), img.cols(), img.channels(), stride, max_points.unwrap_or(MAX_POINTS),
-                                     &mut kps, &mut desc, &mut n, &mut nb)
+    let rc = if mask.empty() {
+        unsafe {
+            apds_sys::apds_akaze_extract(img.data(), img.rows(), img.cols(), img.channels(), stride, max_points.unwrap_or(MAX_POINTS),
+                                         &mut kps, &mut desc, &mut n, &mut nb)
+        }
+    } else {
+        if mask.typ() != CV_8U || mask.rows() != img.rows() || mask.cols() != img.cols() {
+            return Err(Error::new(-215, "mask must be CV_8U of the image's size"));
+        }
+        let mask_stride = mask.step1(0)? * mask.elem_size1();
+        unsafe {
+            apds_sys::apds_akaze_extract_masked(img.data(), img.rows(), img.cols(), img.channels(), stride, mask.data(), mask_stride,
+                                                max_points.unwrap_or(MAX_POINTS), &mut kps, &mut desc, &mut n, &mut nb)
+        }
     };
     if rc != 0 {
         return Err(apds_err(rc));
