@@ -39,11 +39,15 @@ SYMBOLS = [
     "apds_overview_weights", "apds_mosaic_build_overviews", "apds_mosaic_level_info", "apds_mosaic_best_level", "apds_mosaic_window_level",
     "apds_akaze_extract_masked", "apds_akaze_extract_batch_masked", "apds_dev_akaze_extract_masked", "apds_dev_akaze_extract_batch_masked",
     "apds_tile_extract_ex", "apds_tile_extract_batch_ex", "apds_mosaic_tile_extract_ex", "apds_mosaic_tile_extract_batch_ex",
+    "apds_akaze_extract_masked_support", "apds_akaze_extract_batch_masked_support", "apds_dev_akaze_extract_masked_support",
+    "apds_dev_akaze_extract_batch_masked_support", "apds_dev_mask_zero_sat",
 ]
 
 RESAMPLE_NEAREST, RESAMPLE_LANCZOS = 0, 1
 RESAMPLE_MODES = {"nearest": RESAMPLE_NEAREST, "lanczos": RESAMPLE_LANCZOS}
 TILE_MASK_NONE, TILE_MASK_ALPHA = 0, 1     # APDS_TILE_MASK_*: the mask_mode of the apds_*tile_extract*_ex calls
+TILE_MASK_ALPHA_SUPPORT = 3                # the alpha mask with MASK_SUPPORT_DESCRIPTOR
+MASK_SUPPORT_DESCRIPTOR = 15               # APDS_MASK_SUPPORT_DESCRIPTOR: the mask support that covers the descriptor lattice at any orientation
 
 
 def resample_mode(name):
@@ -266,6 +270,11 @@ def lib():
             "apds_tile_extract_batch_ex": (i, [vp, vp, vp, i, i, i, sz, vp, i, i, pp, pp, ip, ip]),
             "apds_mosaic_tile_extract_ex": (i, [vp, i, i, i, i, i, i, i, vp, i, i, pp, pp, ip, ip]),
             "apds_mosaic_tile_extract_batch_ex": (i, [vp, vp, i, i, i, i, i, i, vp, i, i, pp, pp, ip, ip]),
+            "apds_akaze_extract_masked_support": (i, [vp, i, i, i, sz, vp, sz, i, i, pp, pp, ip, ip]),
+            "apds_akaze_extract_batch_masked_support": (i, [vp, i, sz, i, i, i, sz, vp, sz, i, i, pp, pp, ip, ip]),
+            "apds_dev_akaze_extract_masked_support": (i, [vp, i, i, i, sz, vp, sz, i, i, vp, vp, i, ip, vp]),
+            "apds_dev_akaze_extract_batch_masked_support": (i, [vp, i, sz, i, i, i, sz, vp, sz, sz, i, i, vp, vp, i, ip, vp]),
+            "apds_dev_mask_zero_sat": (i, [vp, i, i, sz, sz, vp, vp]),
         }
         for name, (rt, at) in sig.items():
             fn = getattr(L, name)

@@ -45,6 +45,15 @@ struct LevelTable {
     float* ref[AKAZE_MAX_LEVELS];             // three floats per list entry: the refined (x, y, response) of a surviving candidate
 };
 
+// The mask support of an extraction, by value to the kernels that apply the detection mask: the zero-count summed-area table of the mask
+// (akaze_mask_sat.hip: (rows + 1) x (cols + 1) u32 per image) and every level's radius in full-resolution pixels, decided by the plan.
+// A null table: the mask is consulted at the keypoint's own pixel alone.
+struct MaskSupport {
+    const uint32_t* sat = nullptr;
+    size_t img_stride = 0;              // elements between the tables of consecutive images; 0: one table (one mask) for all
+    int radius[AKAZE_MAX_LEVELS] = {};
+};
+
 // A batched launch: `n` images of one size through one grid (gridDim.z = n). Every image owns an identical workspace slab, `stride`
 // bytes apart (so a plane of image i is the plane of image 0 + i * stride); the input images are `img_stride` bytes apart.
 struct Batch {
@@ -107,7 +116,14 @@ void suppress_all_levels(const std::vector<LevelDesc>& ev, const SlabLayout& sl,
 // All levels of every image of the batch: keypoints to kps + image * capacity (at most `capacity` each), the image's count to kp_base[1] of
 // its slab. APDS_KP_RANKED: the candidates place themselves; 0: two passes over the masks. pmask (common.h): the detection mask, applied to
 // the refined positions where the refinement's own drop is - what it removes never counts, so the max_points cut comes after it.
-void compact_all_levels(const LevelTable& T, const SlabLayout& sl, const PixelMask& pmask, apds_keypoint* kps, int capacity, hipStream_t s, const Batch& b);
+// support: a table makes the mask's rule "any zero byte in the square of the level's radius around that position" (four table reads).
+void compact_all_levels(const LevelTable& T, const SlabLayout& sl, const PixelMask& pmask, const MaskSupport& support, apds_keypoint* kps, int capacity,
+                        hipStream_t s, const Batch& b);
+
+// akaze_mask_sat.hip: S[y][x] = the zero bytes of the mask in rows < y, columns < x; `n_tables` masks M.img_stride bytes apart to tables
+// sat_img_stride elements apart (two launches on s; deterministic)
+size_t mask_zero_sat_elems(int rows, int cols);
+void mask_zero_sat_device(const PixelMask& M, int n_tables, uint32_t* sat, size_t sat_img_stride, hipStream_t s);
 // The keypoints of image `bi` (Tb: its level table, bstride 0), all n_all of them, then the `keep` strongest (response descending, ties by
 // detection order) to `out`. The masks are final and filtered: compact_all_levels has run.
 void compact_strongest(const LevelTable& Tb, const SlabLayout& sl, size_t slab_bytes, int bi, int n_all, int keep, apds_keypoint* out, hipStream_t s);

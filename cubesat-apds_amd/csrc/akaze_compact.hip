@@ -46,16 +46,24 @@ __device__ __forceinline__ Refined refine(const float* __restrict__ ldet, int co
 // its rounded position - (int)(pt + 0.5f) per axis, f32 addition, truncation; pt in full-resolution pixels whatever the level - is zero.
 // By construction the rounded position lies inside the image (border >= 1 at every level, pt.x <= W - ratio / 2 - 1 / 2): the clamp is for
 // memory safety alone. A null base is uniform over the launch: no access, no divergence.
-__device__ __forceinline__ bool masked_out(const PixelMask& M, float x, float y) {
+// With a mask support (S.sat, uniform over the launch as well) the keypoint goes iff ANY byte is zero in the square of the level's radius
+// around that pixel, clipped to the image (outside the image nothing is masked): the zero count of the square from four reads of the
+// mask's summed-area table, in u32 arithmetic modulo 2^32 (the count itself is exact). Radius 0 is the byte rule.
+__device__ __forceinline__ bool masked_out(const PixelMask& M, const MaskSupport& S, int lvl, float x, float y) {
     if (!M.base) return false;
     const int mx = min(max((int)(x + 0.5f), 0), M.cols - 1);
     const int my = min(max((int)(y + 0.5f), 0), M.rows - 1);
-    return M.base[(size_t)blockIdx.z * M.img_stride + (size_t)my * M.row_stride + (size_t)mx * M.pix_stride] == 0;
+    if (!S.sat) return M.base[(size_t)blockIdx.z * M.img_stride + (size_t)my * M.row_stride + (size_t)mx * M.pix_stride] == 0;
+    const int R = S.radius[lvl];
+    const size_t x0 = max(mx - R, 0), x1 = min(mx + R, M.cols - 1) + 1, y0 = max(my - R, 0), y1 = min(my + R, M.rows - 1) + 1;
+    const size_t pitch = (size_t)M.cols + 1;
+    const uint32_t* __restrict__ t = S.sat + (size_t)blockIdx.z * S.img_stride;
+    return t[y1 * pitch + x1] - t[y0 * pitch + x1] - t[y1 * pitch + x0] + t[y0 * pitch + x0] != 0;
 }
 
 // drop candidates whose refinement is unstable or whose refined position the detection mask excludes, so bit 0 of the concatenated masks becomes the final keypoint flag (the levels of a
 // stage are final by now: no suppression pass reads their masks as victims any more)
-__global__ void subpixel_filter_kernel(LevelTable T, PixelMask M, const int* __restrict__ list_count, int lvl0) {
+__global__ void subpixel_filter_kernel(LevelTable T, PixelMask M, MaskSupport S, const int* __restrict__ list_count, int lvl0) {
     APDS_RAISE_WAVE_PRIORITY();
     const int lvl = lvl0 + blockIdx.y;
     const int cnt = bofs(list_count, T.bstride)[lvl];
@@ -69,7 +77,7 @@ __global__ void subpixel_filter_kernel(LevelTable T, PixelMask M, const int* __r
         if (!mask[p]) continue;
         const Refined r = refine(ldet, T.w[lvl], x, y, T.ratio[lvl]);
         // survived the suppression, dropped by the refinement or the detection mask: bit 0 (= "is a keypoint") clear, byte non-zero
-        if (!r.ok || masked_out(M, r.x, r.y)) mask[p] = 2;
+        if (!r.ok || masked_out(M, S, lvl, r.x, r.y)) mask[p] = 2;
     }
 }
 
@@ -84,7 +92,7 @@ __global__ void subpixel_filter_kernel(LevelTable T, PixelMask M, const int* __r
 // (one cache line of the mask). Same keypoints, same order, same values as the mask-scan path.
 static constexpr uint32_t REF_DEAD = 0xFFFFFFFFu;
 
-__global__ void subpixel_count_kernel(LevelTable T, PixelMask M, const int* __restrict__ list_count, int lvl0, int* __restrict__ fine,
+__global__ void subpixel_count_kernel(LevelTable T, PixelMask M, MaskSupport S, const int* __restrict__ list_count, int lvl0, int* __restrict__ fine,
                                       int* __restrict__ coarse) {
     APDS_RAISE_WAVE_PRIORITY();
     const int lvl = lvl0 + blockIdx.y;
@@ -103,7 +111,7 @@ __global__ void subpixel_count_kernel(LevelTable T, PixelMask M, const int* __re
         Refined r{};
         if (keep) {
             r = refine(ldet, T.w[lvl], x, y, T.ratio[lvl]);
-            if (!r.ok || masked_out(M, r.x, r.y)) {
+            if (!r.ok || masked_out(M, S, lvl, r.x, r.y)) {
                 mask[p] = 2;   // survived the suppression, dropped by the refinement or the detection mask: bit 0 (= "is a keypoint") clear, byte non-zero
                 keep = false;
             }
@@ -348,18 +356,19 @@ __global__ __launch_bounds__(256) void rank_select_kernel(const apds_keypoint* _
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-void compact_all_levels(const LevelTable& T, const SlabLayout& sl, const PixelMask& pmask, apds_keypoint* kps, int capacity, hipStream_t s, const Batch& b) {
+void compact_all_levels(const LevelTable& T, const SlabLayout& sl, const PixelMask& pmask, const MaskSupport& support, apds_keypoint* kps, int capacity,
+                        hipStream_t s, const Batch& b) {
     const int B = b.n;
     const size_t kp_bstride = (size_t)capacity * sizeof(apds_keypoint);
     if (config().kp_ranked) {
         // the candidates count and place themselves (no pass over the masks)
         const dim3 cgrid(B > 1 ? 16 : 128, T.n, B);
-        hipLaunchKernelGGL(subpixel_count_kernel, cgrid, dim3(256), 0, s, T, pmask, (const int*)sl.list_count, 0, sl.fine_counts, sl.coarse_counts);
+        hipLaunchKernelGGL(subpixel_count_kernel, cgrid, dim3(256), 0, s, T, pmask, support, (const int*)sl.list_count, 0, sl.fine_counts, sl.coarse_counts);
         hipLaunchKernelGGL(kp_scan_fine_kernel, dim3(ceil_div(sl.n_fine, 1024), 1, B), dim3(1024), 0, s, sl.fine_counts, (const int*)sl.coarse_counts, sl.n_fine, sl.kp_base, b.stride);
         hipLaunchKernelGGL(emit_ranked_kernel, cgrid, dim3(256), 0, s, T, (const int*)sl.list_count, 0, (const uint8_t*)sl.mask_all,
                            (const int*)sl.fine_counts, kps, capacity, kp_bstride);
     } else {
-        hipLaunchKernelGGL(subpixel_filter_kernel, dim3(B > 1 ? 16 : 64, T.n, B), dim3(256), 0, s, T, pmask, (const int*)sl.list_count, 0);
+        hipLaunchKernelGGL(subpixel_filter_kernel, dim3(B > 1 ? 16 : 64, T.n, B), dim3(256), 0, s, T, pmask, support, (const int*)sl.list_count, 0);
         const long long lo = 0, hi = sl.total_pix;
         hipLaunchKernelGGL(kp_block_counts_kernel, dim3(sl.nblocks, 1, B), dim3(SCAN_BLOCK), 0, s, (const uint8_t*)sl.mask_all, lo, hi, sl.block_counts, b.stride);
         hipLaunchKernelGGL(kp_scan_offsets_kernel, dim3(1, 1, B), dim3(1024), 0, s, sl.block_counts, sl.nblocks, sl.kp_base, b.stride);

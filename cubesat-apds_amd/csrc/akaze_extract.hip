@@ -382,9 +382,10 @@ void select_strongest(const Frame& f, const LevelTable& T, const int* K, const i
 // gridDim.z = n_img; a single image is a batch of one). Image i starts `img_bstride` bytes after image i-1; its keypoints go to
 // kps_out + i * capacity, its descriptors to desc64_out + i * capacity * 64, its count to counts[i] (host). Returns the largest count.
 // pmask: the detection mask (a null base = none): keypoints whose refined position rounds onto a zero byte are dropped before the count,
-// so max_points and `capacity` are about the survivors.
+// so max_points and `capacity` are about the survivors. mask_support > 0: any zero byte within mask_support units of the keypoint's level
+// (akaze_plan.h: mask_support_unit) of that position drops it; the mask's summed-area table is built in the workspace for that.
 int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, int rows, int cols, int channels, size_t stride, const PixelMask& pmask,
-                               int max_points, apds_keypoint* kps_out, uint8_t* desc64_out, int capacity, int* counts, hipStream_t s) {
+                               int mask_support, int max_points, apds_keypoint* kps_out, uint8_t* desc64_out, int capacity, int* counts, hipStream_t s) {
     APDS_REQUIRE(img != nullptr, APDS_ERR_BAD_ARG, "null image");
     APDS_REQUIRE(n_img >= 1 && n_img <= 4096, APDS_ERR_BAD_ARG, "batch must hold 1 .. 4096 images");
     APDS_REQUIRE(channels == 1 || channels == 3 || channels == 4, APDS_ERR_ASSERT, "image must have 1, 3 or 4 channels");
@@ -398,6 +399,7 @@ int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, i
         APDS_REQUIRE(n_img == 1 || pmask.img_stride == 0 || pmask.img_stride >= (size_t)rows * pmask.row_stride, APDS_ERR_ASSERT,
                      "mask image stride smaller than a mask");
     }
+    APDS_REQUIRE(mask_support >= 0, APDS_ERR_BAD_ARG, "mask_support must be >= 0");
     if (max_points <= 0) max_points = APDS_MAX_POINTS;
     ThreadCtx& c = ctx();
     KernelTimer whole("akaze_extract", s);   // whole extraction (all kernels + the count read-backs), for bench.py
@@ -424,6 +426,17 @@ int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, i
     f.sl.lay_out(static_cast<char*>(c.alloc(f.sl.bytes * (size_t)B)), f.ev, fork.on);
     zero_slab_heads(f);
     int* counts_dev = B > 1 ? c.alloc_n<int>(B) : nullptr;
+    // the mask support: every level's radius from the plan, and the table of the mask(s), which depends on nothing but the mask - its two
+    // launches go out first and are long done when the sub-pixel stage reads it
+    MaskSupport support;
+    if (pmask.base && mask_support > 0) {
+        for (int i = 0; i < L; i++) support.radius[i] = mask_support_radius(mask_support, f.plan.level[i].support_unit);
+        const int n_tables = B > 1 && pmask.img_stride != 0 ? B : 1;
+        support.img_stride = n_tables > 1 ? (mask_zero_sat_elems(rows, cols) + 63) & ~(size_t)63 : 0;
+        uint32_t* sat = c.alloc_n<uint32_t>(n_tables > 1 ? support.img_stride * n_tables : mask_zero_sat_elems(rows, cols));
+        mask_zero_sat_device(pmask, n_tables, sat, support.img_stride, s);
+        support.sat = sat;
+    }
 
     // ---- scale space: base stage, then the level chain with every level's Hessian kernel forked off it, joined at the end
     base_stage(f, base, img, channels, stride);
@@ -436,7 +449,7 @@ int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, i
     // ---- the keypoint stage: once every level has its Hessian, all levels are made final and emitted
     const LevelTable T = level_table(f);
     suppress_all_levels(f.ev, f.sl, s, f.bt);
-    compact_all_levels(T, f.sl, pmask, kps_out, capacity, s, f.bt);
+    compact_all_levels(T, f.sl, pmask, support, kps_out, capacity, s, f.bt);
     // The image's keypoint count (kp_base[1]) is final here, before orientation and descriptors: its copy to the host goes out now, so that
     // the call can return ~0.3 ms before the stream is idle (APDS_EARLY_COUNT).
     int* K = nullptr;
@@ -478,10 +491,10 @@ int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, i
     return kmax;
 }
 
-int akaze_extract_device(const void* img, int rows, int cols, int channels, size_t stride, const PixelMask& pmask, int max_points, apds_keypoint* kps_out,
-                         uint8_t* desc64_out, int capacity, hipStream_t s) {
+int akaze_extract_device(const void* img, int rows, int cols, int channels, size_t stride, const PixelMask& pmask, int mask_support, int max_points,
+                         apds_keypoint* kps_out, uint8_t* desc64_out, int capacity, hipStream_t s) {
     int count = 0;
-    akaze_extract_batch_device(img, 1, 0, rows, cols, channels, stride, pmask, max_points, kps_out, desc64_out, capacity, &count, s);
+    akaze_extract_batch_device(img, 1, 0, rows, cols, channels, stride, pmask, mask_support, max_points, kps_out, desc64_out, capacity, &count, s);
     return count;
 }
 

@@ -201,8 +201,20 @@ struct LevelPlan {
     Head head = Head::None;
     bool strip_pass[MAX_PASSES] = {};   // a pass that is not the head: nld_strip_kernel, else nld_multi_kernel (LDS tiles)
     int half_pass = -1;         // the pass that also writes the next octave's start image (the last one), or -1: the next level resamples
+    int support_unit = 0;       // mask_support_unit of the level: a mask support of n reaches n * support_unit full-resolution pixels
     int first_fed_pass() const { return head == Head::None ? 0 : 1; }
 };
+
+// The unit of a keypoint's descriptor support in full-resolution pixels, constant per level: scale * ratio, where scale is what
+// akaze_describe.hip rounds from the keypoint's size, rint(0.5f * size / ratio) to nearest even with size = (esigma * 1.5f) * 2.0f (the
+// M-LDB lattice and the orientation samples are laid out in steps of `scale` level pixels), and ratio = 2^octave. The mask support of an
+// extraction (apds_akaze_extract_masked_support) is a whole number of these units per side of the keypoint's square.
+inline int mask_support_unit(const LevelDesc& e) {
+    const float size = (e.esigma * AKAZE_DERIVATIVE_FACTOR) * 2.0f;
+    return (int)lrintf(0.5f * size / e.ratio) * (int)e.ratio;
+}
+// The radius a support of `support` units gives a level; past the largest image side every square is the whole image
+inline int mask_support_radius(int support, int support_unit) { return (int)std::min<long long>((long long)support * support_unit, 65536); }
 
 inline bool fits_32bit_offsets(int w, int h) { return (size_t)w * h < (size_t)1 << 29; }   // byte offsets into a float plane (buffer loads)
 
@@ -267,6 +279,7 @@ inline ExtractionPlan plan_extraction(const std::vector<LevelDesc>& ev, int batc
         strip_prefix = strip_prefix && sw.doh_strip && e.sigma_size >= 2 && e.sigma_size <= 4 && e.w >= 64 && e.h >= 64 &&
                        (sw.doh_strip == 2 || bpx >= (size_t)1 << 23);
         p.doh_strips = strip_prefix;
+        p.support_unit = mask_support_unit(e);
         plan.n_strip_levels += strip_prefix ? 1 : 0;
         if (i == 0) continue;
 

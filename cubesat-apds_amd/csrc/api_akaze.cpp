@@ -13,7 +13,7 @@ extern "C" {
 // no pass; APDS_TILE_MASK_NONE: none
 static PixelMask tile_mask(int mask_mode, const uint8_t* bgra, int rows, int cols) {
     PixelMask m;
-    if (mask_mode == APDS_TILE_MASK_ALPHA) {
+    if (mask_mode == APDS_TILE_MASK_ALPHA || mask_mode == APDS_TILE_MASK_ALPHA_SUPPORT) {
         m.base = bgra + 3;
         m.pix_stride = 4;
         m.row_stride = (size_t)cols * 4;
@@ -24,8 +24,12 @@ static PixelMask tile_mask(int mask_mode, const uint8_t* bgra, int rows, int col
     return m;
 }
 static void check_mask_mode(int mask_mode) {
-    APDS_REQUIRE(mask_mode == APDS_TILE_MASK_NONE || mask_mode == APDS_TILE_MASK_ALPHA, APDS_ERR_BAD_ARG, "unknown mask_mode");
+    APDS_REQUIRE(mask_mode == APDS_TILE_MASK_NONE || mask_mode == APDS_TILE_MASK_ALPHA || mask_mode == APDS_TILE_MASK_ALPHA_SUPPORT, APDS_ERR_BAD_ARG,
+                 "unknown mask_mode");
 }
+// APDS_TILE_MASK_ALPHA_SUPPORT: the alpha mask reaches over the descriptor's support
+static int tile_mask_support(int mask_mode) { return mask_mode == APDS_TILE_MASK_ALPHA_SUPPORT ? APDS_MASK_SUPPORT_DESCRIPTOR : 0; }
+static void check_mask_support(int mask_support) { APDS_REQUIRE(mask_support >= 0, APDS_ERR_BAD_ARG, "mask_support must be >= 0"); }
 
 // a mask plane of the caller's on the device (rows x cols bytes, any strides)
 static PixelMask plane_mask(const void* mask_dev, size_t row_stride, size_t img_stride, int rows, int cols) {
@@ -43,12 +47,12 @@ static PixelMask plane_mask(const void* mask_dev, size_t row_stride, size_t img_
 
 // device image -> host keypoints + 61-byte descriptors (malloc'ed, the caller frees them with apds_free)
 static void extract_to_host(ThreadCtx& c, hipStream_t s, const uint8_t* dimg, int rows, int cols, int channels, size_t dstride, const PixelMask& pmask,
-                            int max_points, apds_keypoint** kps, uint8_t** desc, int* n) {
+                            int mask_support, int max_points, apds_keypoint** kps, uint8_t** desc, int* n) {
     // strict 3x3 maxima are never adjacent: at most ceil(w/2)*ceil(h/2) per level, and the cap is max_points
     const int capacity = max_points;
     apds_keypoint* dk = c.alloc_n<apds_keypoint>(capacity);
     uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * 64);
-    const int K = akaze_extract_device(dimg, rows, cols, channels, dstride, pmask, max_points, dk, dd, capacity, s);
+    const int K = akaze_extract_device(dimg, rows, cols, channels, dstride, pmask, mask_support, max_points, dk, dd, capacity, s);
     apds_keypoint* hk = static_cast<apds_keypoint*>(std::malloc(std::max<size_t>(1, (size_t)K * sizeof(apds_keypoint))));
     uint8_t* hd = static_cast<uint8_t*>(std::malloc(std::max<size_t>(1, (size_t)K * APDS_DESC_BYTES)));
     if (!hk || !hd) {
@@ -74,10 +78,11 @@ static void extract_to_host(ThreadCtx& c, hipStream_t s, const uint8_t* dimg, in
     *n = K;
 }
 
-static int akaze_extract_host(const uint8_t* img, int rows, int cols, int channels, size_t stride, const uint8_t* mask, size_t mask_stride, int max_points,
-                              apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes) {
+static int akaze_extract_host(const uint8_t* img, int rows, int cols, int channels, size_t stride, const uint8_t* mask, size_t mask_stride, int mask_support,
+                              int max_points, apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes) {
     return guarded([&] {
         APDS_REQUIRE(kps && desc && n && desc_bytes, APDS_ERR_BAD_ARG, "null output");
+        check_mask_support(mask_support);
         *kps = nullptr;
         *desc = nullptr;
         *n = 0;
@@ -99,21 +104,28 @@ static int akaze_extract_host(const uint8_t* img, int rows, int cols, int channe
             dmask = c.alloc_n<uint8_t>((size_t)rows * cols);
             HIP_CHECK(hipMemcpy2DAsync(dmask, cols, mask, mask_stride, cols, rows, hipMemcpyHostToDevice, s));
         }
-        extract_to_host(c, s, dimg, rows, cols, channels, dstride, plane_mask(dmask, cols, 0, rows, cols), max_points, kps, desc, n);
+        extract_to_host(c, s, dimg, rows, cols, channels, dstride, plane_mask(dmask, cols, 0, rows, cols), mask_support, max_points, kps, desc, n);
     });
 }
 
 int apds_akaze_extract(const uint8_t* img, int rows, int cols, int channels, size_t stride, int max_points, apds_keypoint** kps, uint8_t** desc,
                        int* n, int* desc_bytes) {
     APDS_RANGE("apds_akaze_extract");
-    return akaze_extract_host(img, rows, cols, channels, stride, nullptr, 0, max_points, kps, desc, n, desc_bytes);
+    return akaze_extract_host(img, rows, cols, channels, stride, nullptr, 0, 0, max_points, kps, desc, n, desc_bytes);
 }
 
 // cv::Feature2D::detectAndCompute(img, mask, ..): the call above passes Mat::default() (feature_extraction/src/lib.rs:75-79)
 int apds_akaze_extract_masked(const uint8_t* img, int rows, int cols, int channels, size_t stride, const uint8_t* mask, size_t mask_stride, int max_points,
                               apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes) {
     APDS_RANGE("apds_akaze_extract_masked");
-    return akaze_extract_host(img, rows, cols, channels, stride, mask, mask_stride, max_points, kps, desc, n, desc_bytes);
+    return akaze_extract_host(img, rows, cols, channels, stride, mask, mask_stride, 0, max_points, kps, desc, n, desc_bytes);
+}
+
+// the mask consulted on the square of mask_support descriptor units around the keypoint (0: the call above)
+int apds_akaze_extract_masked_support(const uint8_t* img, int rows, int cols, int channels, size_t stride, const uint8_t* mask, size_t mask_stride,
+                                      int mask_support, int max_points, apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes) {
+    APDS_RANGE("apds_akaze_extract_masked_support");
+    return akaze_extract_host(img, rows, cols, channels, stride, mask, mask_stride, mask_support, max_points, kps, desc, n, desc_bytes);
 }
 
 // One tile of the preprocessor in one call (preprocessor/src/main.rs:258-277): the three f32 band windows go up once, band_merger
@@ -142,7 +154,7 @@ int apds_tile_extract_ex(const float* red, const float* green, const float* blue
             HIP_CHECK(hipMemcpy2DAsync(bands + b * px, (size_t)cols * 4, src[b], row_stride * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, s));
         uint8_t* dimg = c.alloc_n<uint8_t>(px * 4);
         band_merger_device(bands, bands + px, bands + 2 * px, px, minmax6, /*bgra=*/1, dimg, s);
-        extract_to_host(c, s, dimg, rows, cols, 4, (size_t)cols * 4, tile_mask(mask_mode, dimg, rows, cols), max_points, kps, desc, n);
+        extract_to_host(c, s, dimg, rows, cols, 4, (size_t)cols * 4, tile_mask(mask_mode, dimg, rows, cols), tile_mask_support(mask_mode), max_points, kps, desc, n);
     });
 }
 
@@ -246,8 +258,8 @@ int apds_tile_extract_batch_ex(const float* const* red, const float* const* gree
         const int capacity = batch_capacity(rows, cols, max_points);
         apds_keypoint* dk = c.alloc_n<apds_keypoint>((size_t)capacity * n_tiles);
         uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * 64 * n_tiles);
-        akaze_extract_batch_device(dimg, n_tiles, px * 4, rows, cols, 4, (size_t)cols * 4, tile_mask(mask_mode, dimg, rows, cols), max_points, dk, dd, capacity,
-                                   counts, s);
+        akaze_extract_batch_device(dimg, n_tiles, px * 4, rows, cols, 4, (size_t)cols * 4, tile_mask(mask_mode, dimg, rows, cols),
+                                   tile_mask_support(mask_mode), max_points, dk, dd, capacity, counts, s);
         batch_results_to_host(c, s, dk, dd, capacity, n_tiles, counts, kps, desc);
     });
 }
@@ -286,7 +298,7 @@ int apds_mosaic_tile_extract_ex(void* mosaic, int x0, int y0, int win_w, int win
         uint8_t* dimg = c.alloc_n<uint8_t>(px * 4);
         mosaic_read_device(m, xy0, 1, win_w, win_h, out_w, out_h, resample, bands, s);
         band_merger_device(bands, bands + px, bands + 2 * px, px, minmax6, /*bgra=*/1, dimg, s);
-        extract_to_host(c, s, dimg, out_h, out_w, 4, (size_t)out_w * 4, tile_mask(mask_mode, dimg, out_h, out_w), max_points, kps, desc, n);
+        extract_to_host(c, s, dimg, out_h, out_w, 4, (size_t)out_w * 4, tile_mask(mask_mode, dimg, out_h, out_w), tile_mask_support(mask_mode), max_points, kps, desc, n);
     });
 }
 
@@ -326,8 +338,8 @@ int apds_mosaic_tile_extract_batch_ex(void* mosaic, const int32_t* xy0, int n_ti
         uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * 64 * n_tiles);
         mosaic_read_device(m, xy0, n_tiles, win_w, win_h, out_w, out_h, resample, bands, s);
         band_merger_device(bands, bands + all, bands + 2 * all, all, minmax6, /*bgra=*/1, dimg, s);
-        akaze_extract_batch_device(dimg, n_tiles, px * 4, out_h, out_w, 4, (size_t)out_w * 4, tile_mask(mask_mode, dimg, out_h, out_w), max_points, dk, dd,
-                                   capacity, counts, s);
+        akaze_extract_batch_device(dimg, n_tiles, px * 4, out_h, out_w, 4, (size_t)out_w * 4, tile_mask(mask_mode, dimg, out_h, out_w),
+                                   tile_mask_support(mask_mode), max_points, dk, dd, capacity, counts, s);
         batch_results_to_host(c, s, dk, dd, capacity, n_tiles, counts, kps, desc);
     });
 }
@@ -341,9 +353,11 @@ int apds_mosaic_tile_extract_batch(void* mosaic, const int32_t* xy0, int n_tiles
 // n_images equal-sized host images in one call: one upload, one batched extraction (every kernel's grid covers all images), one download.
 // Outputs: concatenated keypoints / 61-byte descriptors (image 0's rows first), counts[i] rows per image.
 static int akaze_extract_batch_host(const uint8_t* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride,
-                                    const uint8_t* const* masks, size_t mask_stride, int max_points, apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes) {
+                                    const uint8_t* const* masks, size_t mask_stride, int mask_support, int max_points, apds_keypoint** kps, uint8_t** desc,
+                                    int* counts, int* desc_bytes) {
     return guarded([&] {
         APDS_REQUIRE(kps && desc && counts && desc_bytes, APDS_ERR_BAD_ARG, "null output");
+        check_mask_support(mask_support);
         *kps = nullptr;
         *desc = nullptr;
         *desc_bytes = APDS_DESC_BYTES;
@@ -381,8 +395,8 @@ static int akaze_extract_batch_host(const uint8_t* imgs, int n_images, size_t im
                 else HIP_CHECK(hipMemsetAsync(dmask + i * mpx, 0xFF, mpx, s));
             }
         }
-        akaze_extract_batch_device(dimg, n_images, dimg_bytes, rows, cols, channels, dstride, plane_mask(dmask, cols, mpx, rows, cols), max_points, dk, dd, capacity,
-                                   counts, s);
+        akaze_extract_batch_device(dimg, n_images, dimg_bytes, rows, cols, channels, dstride, plane_mask(dmask, cols, mpx, rows, cols), mask_support, max_points, dk, dd,
+                                   capacity, counts, s);
         batch_results_to_host(c, s, dk, dd, capacity, n_images, counts, kps, desc);
     });
 }
@@ -390,26 +404,43 @@ static int akaze_extract_batch_host(const uint8_t* imgs, int n_images, size_t im
 int apds_akaze_extract_batch(const uint8_t* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride, int max_points,
                              apds_keypoint** kps, uint8_t** desc, int* counts, int* desc_bytes) {
     APDS_RANGE("apds_akaze_extract_batch");
-    return akaze_extract_batch_host(imgs, n_images, image_stride, rows, cols, channels, stride, nullptr, 0, max_points, kps, desc, counts, desc_bytes);
+    return akaze_extract_batch_host(imgs, n_images, image_stride, rows, cols, channels, stride, nullptr, 0, 0, max_points, kps, desc, counts, desc_bytes);
 }
 
 int apds_akaze_extract_batch_masked(const uint8_t* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride,
                                     const uint8_t* const* masks, size_t mask_stride, int max_points, apds_keypoint** kps, uint8_t** desc, int* counts,
                                     int* desc_bytes) {
     APDS_RANGE("apds_akaze_extract_batch_masked");
-    return akaze_extract_batch_host(imgs, n_images, image_stride, rows, cols, channels, stride, masks, mask_stride, max_points, kps, desc, counts, desc_bytes);
+    return akaze_extract_batch_host(imgs, n_images, image_stride, rows, cols, channels, stride, masks, mask_stride, 0, max_points, kps, desc, counts, desc_bytes);
+}
+
+int apds_akaze_extract_batch_masked_support(const uint8_t* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride,
+                                            const uint8_t* const* masks, size_t mask_stride, int mask_support, int max_points, apds_keypoint** kps, uint8_t** desc,
+                                            int* counts, int* desc_bytes) {
+    APDS_RANGE("apds_akaze_extract_batch_masked_support");
+    return akaze_extract_batch_host(imgs, n_images, image_stride, rows, cols, channels, stride, masks, mask_stride, mask_support, max_points, kps, desc, counts,
+                                    desc_bytes);
+}
+
+int apds_dev_akaze_extract_batch_masked_support(const void* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride,
+                                                const void* mask_dev, size_t mask_stride, size_t mask_image_stride, int mask_support, int max_points, void* kps,
+                                                void* desc64, int capacity, int* counts, void* stream) {
+    APDS_RANGE("apds_dev_akaze_extract_batch");
+    return guarded([&] {
+        APDS_REQUIRE(counts && kps && desc64, APDS_ERR_BAD_ARG, "null output");
+        check_mask_support(mask_support);
+        ctx().ws_reset(pick_stream(stream));
+        akaze_extract_batch_device(imgs, n_images, image_stride, rows, cols, channels, stride, plane_mask(mask_dev, mask_stride, mask_image_stride, rows, cols),
+                                   mask_support, max_points, static_cast<apds_keypoint*>(kps), static_cast<uint8_t*>(desc64), capacity, counts,
+                                   pick_stream(stream));
+    });
 }
 
 int apds_dev_akaze_extract_batch_masked(const void* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride, const void* mask_dev,
                                         size_t mask_stride, size_t mask_image_stride, int max_points, void* kps, void* desc64, int capacity, int* counts,
                                         void* stream) {
-    APDS_RANGE("apds_dev_akaze_extract_batch");
-    return guarded([&] {
-        APDS_REQUIRE(counts && kps && desc64, APDS_ERR_BAD_ARG, "null output");
-        ctx().ws_reset(pick_stream(stream));
-        akaze_extract_batch_device(imgs, n_images, image_stride, rows, cols, channels, stride, plane_mask(mask_dev, mask_stride, mask_image_stride, rows, cols),
-                                   max_points, static_cast<apds_keypoint*>(kps), static_cast<uint8_t*>(desc64), capacity, counts, pick_stream(stream));
-    });
+    return apds_dev_akaze_extract_batch_masked_support(imgs, n_images, image_stride, rows, cols, channels, stride, mask_dev, mask_stride, mask_image_stride, 0,
+                                                       max_points, kps, desc64, capacity, counts, stream);
 }
 
 int apds_dev_akaze_extract_batch(const void* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride, int max_points,
@@ -418,14 +449,36 @@ int apds_dev_akaze_extract_batch(const void* imgs, int n_images, size_t image_st
                                                stream);
 }
 
-int apds_dev_akaze_extract_masked(const void* img, int rows, int cols, int channels, size_t stride, const void* mask_dev, size_t mask_stride, int max_points,
-                                  void* kps, void* desc64, int capacity, int* n, void* stream) {
+int apds_dev_akaze_extract_masked_support(const void* img, int rows, int cols, int channels, size_t stride, const void* mask_dev, size_t mask_stride,
+                                          int mask_support, int max_points, void* kps, void* desc64, int capacity, int* n, void* stream) {
     APDS_RANGE("apds_dev_akaze_extract");
     return guarded([&] {
         APDS_REQUIRE(n && kps && desc64, APDS_ERR_BAD_ARG, "null output");
+        check_mask_support(mask_support);
         ctx().ws_reset(pick_stream(stream));
-        *n = akaze_extract_device(img, rows, cols, channels, stride, plane_mask(mask_dev, mask_stride, 0, rows, cols), max_points,
+        *n = akaze_extract_device(img, rows, cols, channels, stride, plane_mask(mask_dev, mask_stride, 0, rows, cols), mask_support, max_points,
                                   static_cast<apds_keypoint*>(kps), static_cast<uint8_t*>(desc64), capacity, pick_stream(stream));
+    });
+}
+
+int apds_dev_akaze_extract_masked(const void* img, int rows, int cols, int channels, size_t stride, const void* mask_dev, size_t mask_stride, int max_points,
+                                  void* kps, void* desc64, int capacity, int* n, void* stream) {
+    return apds_dev_akaze_extract_masked_support(img, rows, cols, channels, stride, mask_dev, mask_stride, 0, max_points, kps, desc64, capacity, n, stream);
+}
+
+// The zero-count summed-area table of a device mask on its own (what the mask support builds in its workspace): out[y][x], (rows + 1) x
+// (cols + 1) u32, = the zero bytes in rows < y and columns < x.
+int apds_dev_mask_zero_sat(const void* mask_dev, int rows, int cols, size_t row_stride, size_t pix_stride, void* out_u32_dev, void* stream) {
+    APDS_RANGE("apds_dev_mask_zero_sat");
+    return guarded([&] {
+        APDS_REQUIRE(mask_dev && out_u32_dev, APDS_ERR_BAD_ARG, "null argument");
+        PixelMask m;
+        m.base = static_cast<const uint8_t*>(mask_dev);
+        m.row_stride = row_stride;
+        m.pix_stride = pix_stride;
+        m.rows = rows;
+        m.cols = cols;
+        mask_zero_sat_device(m, 1, static_cast<uint32_t*>(out_u32_dev), 0, pick_stream(stream));
     });
 }
 

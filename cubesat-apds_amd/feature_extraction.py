@@ -88,10 +88,21 @@ def akaze_keypoint_descriptor_extraction_def(img, max_points=None):
     return ExtractedKeyPoint(k, d)
 
 
-def akaze_keypoint_descriptor_extraction(img, mask=None, max_points=None):
+def _mask_support(mask_support):
+    s = int(mask_support)
+    if s < 0:
+        raise ApdsError(_lib.ERR_BAD_ARG, "mask_support must be >= 0")
+    return s
+
+
+def akaze_keypoint_descriptor_extraction(img, mask=None, max_points=None, mask_support=0):
     """The same call with the mask argument lib.rs:75-79 leaves empty (`&Mat::default()`): detection runs unmasked, then a keypoint goes iff
     mask[int(y + 0.5), int(x + 0.5)] == 0 (f32, truncation; x, y the refined full-resolution position), and max_points cuts what is left.
-    mask: uint8 HxW, non-zero = keep; None = akaze_keypoint_descriptor_extraction_def."""
+    mask: uint8 HxW, non-zero = keep; None = akaze_keypoint_descriptor_extraction_def.
+    mask_support n > 0: the keypoint goes iff ANY mask byte is zero within n * scale * 2^octave pixels of that position on either axis
+    (scale = rint(0.5 * size / 2^octave), the unit of the descriptor's lattice; the square is clipped to the image).
+    _lib.MASK_SUPPORT_DESCRIPTOR (15) covers the descriptor at any orientation."""
+    support = _mask_support(mask_support)
     if mask is None:
         return akaze_keypoint_descriptor_extraction_def(img, max_points)
     img = _image(img)
@@ -99,20 +110,25 @@ def akaze_keypoint_descriptor_extraction(img, mask=None, max_points=None):
     ch = 1 if img.ndim == 2 else img.shape[2]
     kps, desc = C.c_void_p(), C.c_void_p()
     n, nb = C.c_int(0), C.c_int(0)
-    check(lib().apds_akaze_extract_masked(ptr(img), img.shape[0], img.shape[1], ch, img.strides[0], ptr(m), m.strides[0],
-                                          MAX_POINTS if max_points is None else int(max_points),
-                                          C.byref(kps), C.byref(desc), C.byref(n), C.byref(nb)))
+    mp = MAX_POINTS if max_points is None else int(max_points)
+    if support == 0:
+        check(lib().apds_akaze_extract_masked(ptr(img), img.shape[0], img.shape[1], ch, img.strides[0], ptr(m), m.strides[0], mp,
+                                              C.byref(kps), C.byref(desc), C.byref(n), C.byref(nb)))
+    else:
+        check(lib().apds_akaze_extract_masked_support(ptr(img), img.shape[0], img.shape[1], ch, img.strides[0], ptr(m), m.strides[0], support, mp,
+                                                      C.byref(kps), C.byref(desc), C.byref(n), C.byref(nb)))
     k = take(kps, n.value, KEYPOINT_DTYPE)
     d = take(desc, n.value * nb.value, np.uint8).reshape(n.value, nb.value)
     return ExtractedKeyPoint(k, d)
 
 
-def akaze_keypoint_descriptor_extraction_batch(imgs, max_points=None, mask=None):
+def akaze_keypoint_descriptor_extraction_batch(imgs, max_points=None, mask=None, mask_support=0):
     """lib.rs:61-92 for a batch of equal-sized images (array [B, H, W] or [B, H, W, C] uint8, or a list of such images) in ONE library
     call: the batch goes through every kernel's grid together. Returns a list of ExtractedKeyPoint, each exactly what
     akaze_keypoint_descriptor_extraction_def returns for that image. This is how a caller that extracts one tile per task
     (preprocessor/src/main.rs:227-245,277) should hand its tiles over: a single small tile is launch-latency-bound.
-    mask: None, or one entry per image, each None or a mask as akaze_keypoint_descriptor_extraction takes it."""
+    mask: None, or one entry per image, each None or a mask as akaze_keypoint_descriptor_extraction takes it; mask_support: as there."""
+    support = _mask_support(mask_support)
     a = np.ascontiguousarray(np.stack([np.asarray(i) for i in imgs]) if isinstance(imgs, (list, tuple)) else np.asarray(imgs))
     if a.dtype != np.uint8 or a.ndim not in (3, 4) or a.size == 0:
         raise ApdsError(_lib.ERR_ASSERT, "images must be a non-empty uint8 [B, H, W[, C]] array")
@@ -128,8 +144,12 @@ def akaze_keypoint_descriptor_extraction_batch(imgs, max_points=None, mask=None)
             raise ApdsError(_lib.ERR_ASSERT, "one mask (or None) per image")
         planes = [None if m is None else np.ascontiguousarray(_mask_plane(m, h, w)) for m in mask]      # one row stride for all: packed
         mptrs = (C.c_void_p * b)(*[None if m is None else m.ctypes.data for m in planes])
-        check(lib().apds_akaze_extract_batch_masked(ptr(a), b, a.strides[0], h, w, ch, a.strides[1], mptrs, w, mp, C.byref(kps), C.byref(desc), counts,
-                                                    C.byref(nb)))
+        if support == 0:
+            check(lib().apds_akaze_extract_batch_masked(ptr(a), b, a.strides[0], h, w, ch, a.strides[1], mptrs, w, mp, C.byref(kps), C.byref(desc), counts,
+                                                        C.byref(nb)))
+        else:
+            check(lib().apds_akaze_extract_batch_masked_support(ptr(a), b, a.strides[0], h, w, ch, a.strides[1], mptrs, w, support, mp, C.byref(kps),
+                                                                C.byref(desc), counts, C.byref(nb)))
     total = sum(counts)
     k = take(kps, total, KEYPOINT_DTYPE)
     d = take(desc, total * nb.value, np.uint8).reshape(total, nb.value)
@@ -141,6 +161,12 @@ def akaze_keypoint_descriptor_extraction_batch(imgs, max_points=None, mask=None)
 
 
 def _mask_mode(mask_nodata):
+    """mask_nodata of the tile functions: False, True (the alpha is the mask, consulted at the keypoint's pixel) or "support" (the alpha mask
+    with _lib.MASK_SUPPORT_DESCRIPTOR: a keypoint whose descriptor could sample a nodata pixel goes too)"""
+    if isinstance(mask_nodata, str):
+        if mask_nodata != "support":
+            raise ApdsError(_lib.ERR_BAD_ARG, 'mask_nodata must be False, True or "support"')
+        return _lib.TILE_MASK_ALPHA_SUPPORT
     return _lib.TILE_MASK_ALPHA if mask_nodata else _lib.TILE_MASK_NONE
 
 
@@ -148,7 +174,8 @@ def tile_keypoint_descriptor_extraction(red, green, blue, min_max, max_points=No
     """One preprocessor tile (preprocessor/src/main.rs:258-277): to_rgb's band_merger, raster_to_mat and the extraction above in one
     library call — red/green/blue are equal-shape 2-D float32 views (row-strided views into the mosaic are taken as they are), the
     RGBA/BGRA image exists on the device only. Same result as the three separate calls. mask_nodata: the tile's alpha (0 where all three
-    bands are NaN) is the extraction's mask, as akaze_keypoint_descriptor_extraction(tile, mask=tile[..., 3]) would apply it."""
+    bands are NaN) is the extraction's mask, as akaze_keypoint_descriptor_extraction(tile, mask=tile[..., 3]) would apply it; "support": the
+    same with mask_support=_lib.MASK_SUPPORT_DESCRIPTOR (every tile function takes the three values)."""
     bands = [np.asarray(b) for b in (red, green, blue)]
     h, w = bands[0].shape
     if any(b.dtype != np.float32 or b.ndim != 2 or b.shape != (h, w) for b in bands) or h == 0 or w == 0:

@@ -2,7 +2,7 @@
 level of detail of a mosaic is cut into tiles of one fixed pixel size, each tile goes through to_rgb -> raster_to_mat -> AKAZE,
 and its keypoints are stored with their coordinates lifted back to level-0 pixels. The reference writes to Postgres through a
 rayon pool; here the rows go to the GPU-resident KeypointTable (feature_database.py) and an in-memory image table."""
-from . import feature_extraction, homographier
+from . import _lib, feature_extraction, homographier
 from .geotiff_extractor import DeviceMosaic
 
 
@@ -33,7 +33,9 @@ def extract_tile(dataset, tile_size, column, row, lod, fused=True, resample="nea
     resample: how a level > 0 window becomes a tile ("nearest", or "lanczos" as the reference reads it, mod.rs:339). A DeviceMosaic
     dataset is read, resampled and extracted on the device in one call.
     mask_nodata: the tile's alpha, which band_merger sets to 0 where all three bands are NaN (mod.rs:346-378) and the reference never reads
-    again, is the extraction's mask (detectAndCompute's `mask`, empty at lib.rs:75-79): the edges of a nodata area leave no rows."""
+    again, is the extraction's mask (detectAndCompute's `mask`, empty at lib.rs:75-79): the edges of a nodata area leave no rows.
+    "support" beside True / False: the mask reaches over the descriptor's support (mask_support 15), so no stored descriptor has sampled
+    nodata; True consults the keypoint's own pixel alone."""
     span = (tile_size[0] * 2 ** lod, tile_size[1] * 2 ** lod)
     if isinstance(dataset, DeviceMosaic):
         return feature_extraction.mosaic_tile_keypoint_descriptor_extraction(dataset, (column * span[0], row * span[1]), span, tile_size, resample,
@@ -46,7 +48,8 @@ def extract_tile(dataset, tile_size, column, row, lod, fused=True, resample="nea
     tile = dataset.to_rgb((column * span[0], row * span[1]), span, tile_size, **extra)            # main.rs:258-272
     tile_mat = homographier.raster_to_mat(tile, tile_size[0], tile_size[1])                       # main.rs:274
     if mask_nodata:
-        return feature_extraction.akaze_keypoint_descriptor_extraction(tile_mat.mat, tile_mat.mat[..., 3], None)
+        support = _lib.MASK_SUPPORT_DESCRIPTOR if feature_extraction._mask_mode(mask_nodata) == _lib.TILE_MASK_ALPHA_SUPPORT else 0
+        return feature_extraction.akaze_keypoint_descriptor_extraction(tile_mat.mat, tile_mat.mat[..., 3], None, support)
     return feature_extraction.akaze_keypoint_descriptor_extraction_def(tile_mat.mat, None)        # main.rs:277
 
 

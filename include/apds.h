@@ -91,12 +91,29 @@ int apds_akaze_extract_batch(const uint8_t* imgs, int n_images, size_t image_str
  * responses, ties by detection order) comes AFTER the mask. mask: rows x cols u8, mask_stride_bytes between rows, any non-zero value keeps.
  * A NULL mask is the unmasked call; mask_stride_bytes < cols is APDS_ERR_ASSERT (OpenCV asserts mask.size() == image.size()).
  * Batch form: masks = n_images pointers (or NULL: no mask at all), any of them NULL = that image unmasked; one mask_stride_bytes for all.
- * Not eroded by keypoint size or descriptor support: a caller who wants that erodes the mask. */
+ * These two consult the mask at that one pixel, as OpenCV does; the _support forms below widen the test to the keypoint's descriptor support. */
 int apds_akaze_extract_masked(const uint8_t* img, int rows, int cols, int channels, size_t stride_bytes, const uint8_t* mask, size_t mask_stride_bytes,
                               int max_points, apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes);
 int apds_akaze_extract_batch_masked(const uint8_t* imgs, int n_images, size_t image_stride_bytes, int rows, int cols, int channels, size_t stride_bytes,
                                     const uint8_t* const* masks, size_t mask_stride_bytes, int max_points, apds_keypoint** kps, uint8_t** desc, int* counts,
                                     int* desc_bytes);
+/* The masked calls with a mask support: one more argument, int mask_support >= 0 (negative: APDS_ERR_BAD_ARG). A keypoint of level l in
+ * octave o has ratio = 2^o and scale = rint(0.5f * size / ratio) (f32, half to even: the unit in which the descriptor's lattice is laid out,
+ * constant per level), and radius R = mask_support * scale * ratio full-resolution pixels. Its centre is the pixel of the rule above,
+ * cx = (int)(pt.x + 0.5f), cy = (int)(pt.y + 0.5f). It is removed iff at least one mask byte is zero in the square [cx - R, cx + R] x
+ * [cy - R, cy + R] clipped to the image: pixels outside the image are not masked (the descriptor skips its samples there). Everything else
+ * is as above: detection unmasked, the survivors keep order, fields and descriptor bytes, max_points cuts after the mask.
+ * mask_support 0 is exactly the call without _support; a NULL mask is the unmasked call whatever mask_support is.
+ * APDS_MASK_SUPPORT_DESCRIPTOR covers the M-LDB lattice at any orientation: its offsets reach 10 * scale per rotated axis, 10 * sqrt(2) < 15
+ * (the orientation is not yet known where the mask is applied, so the square is the axis-aligned one that holds every rotation).
+ * Cost: the device answers the square from a zero-count summed-area table of the mask, built in the workspace by two launches per call
+ * (4 bytes per pixel and image; one table for a mask that a batch shares); mask_support 0 builds none. */
+#define APDS_MASK_SUPPORT_DESCRIPTOR 15
+int apds_akaze_extract_masked_support(const uint8_t* img, int rows, int cols, int channels, size_t stride_bytes, const uint8_t* mask, size_t mask_stride_bytes,
+                                      int mask_support, int max_points, apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes);
+int apds_akaze_extract_batch_masked_support(const uint8_t* imgs, int n_images, size_t image_stride_bytes, int rows, int cols, int channels, size_t stride_bytes,
+                                            const uint8_t* const* masks, size_t mask_stride_bytes, int mask_support, int max_points, apds_keypoint** kps,
+                                            uint8_t** desc, int* counts, int* desc_bytes);
 
 /* lib.rs:94-114  get_knn_matches(origin_desc, target_desc, k, filter_strength) -> Vector<DMatch>
  * Hamming k-NN of each origin (query) row over the target (train) rows, then keep m[0] iff
@@ -160,9 +177,13 @@ int apds_tile_extract_batch(const float* const* red, const float* const* green, 
  * image's own fourth byte. The alpha rule is band_merger's and unchanged: alpha 0 only where ALL three bands are NaN (a pixel that lost one
  * or two bands keeps alpha 255 and masks nothing). Under APDS_RESAMPLE_LANCZOS a NaN propagates through every tap that touches it, so the
  * masked area is the nodata area widened by the filter footprint (three source pixels times max(1, win / out) on every side). Any other
- * mask_mode is APDS_ERR_BAD_ARG. Results equal apds_akaze_extract_masked on the BGRA tile with mask = its alpha plane. */
+ * mask_mode is APDS_ERR_BAD_ARG. Results equal apds_akaze_extract_masked on the BGRA tile with mask = its alpha plane.
+ * APDS_TILE_MASK_ALPHA_SUPPORT is the alpha mask with the mask support APDS_MASK_SUPPORT_DESCRIPTOR (apds_akaze_extract_masked_support on
+ * the BGRA tile with its alpha plane): a keypoint whose descriptor could sample a nodata pixel is removed, not only one that lies on one.
+ * The modes are two bits: 1 = the alpha is the mask, 2 = with the descriptor support; 2 alone names no mask and stays APDS_ERR_BAD_ARG. */
 #define APDS_TILE_MASK_NONE 0
 #define APDS_TILE_MASK_ALPHA 1
+#define APDS_TILE_MASK_ALPHA_SUPPORT 3
 int apds_tile_extract_ex(const float* red, const float* green, const float* blue, int rows, int cols, size_t row_stride, const double* minmax6,
                          int max_points, int mask_mode, apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes);
 int apds_tile_extract_batch_ex(const float* const* red, const float* const* green, const float* const* blue, int n_tiles, int rows, int cols, size_t row_stride,
@@ -573,6 +594,16 @@ int apds_dev_akaze_extract_masked(const void* img, int rows, int cols, int chann
 int apds_dev_akaze_extract_batch_masked(const void* imgs, int n_images, size_t image_stride_bytes, int rows, int cols, int channels, size_t stride_bytes,
                                         const void* mask_dev, size_t mask_stride_bytes, size_t mask_image_stride_bytes, int max_points, void* kps, void* desc64,
                                         int capacity, int* counts, void* stream);
+/* ... and with a mask support (the rule of apds_akaze_extract_masked_support; 0 = the two calls above, negative: APDS_ERR_BAD_ARG) */
+int apds_dev_akaze_extract_masked_support(const void* img, int rows, int cols, int channels, size_t stride_bytes, const void* mask_dev, size_t mask_stride_bytes,
+                                          int mask_support, int max_points, void* kps, void* desc64, int capacity, int* n, void* stream);
+int apds_dev_akaze_extract_batch_masked_support(const void* imgs, int n_images, size_t image_stride_bytes, int rows, int cols, int channels, size_t stride_bytes,
+                                                const void* mask_dev, size_t mask_stride_bytes, size_t mask_image_stride_bytes, int mask_support, int max_points,
+                                                void* kps, void* desc64, int capacity, int* counts, void* stream);
+/* The table behind the mask support, on its own: out_u32_dev[y][x], (rows + 1) x (cols + 1) u32, = the number of zero mask bytes in rows < y
+ * and columns < x (exact). mask_dev: rows x cols bytes, row_stride_bytes between rows and pix_stride_bytes between the pixels of a row (1: a
+ * plane; 4 with mask_dev = image + 3: the alpha of a BGRA image, read as the aligned 4-byte words that hold the bytes). Sides 1 .. 65535. */
+int apds_dev_mask_zero_sat(const void* mask_dev, int rows, int cols, size_t row_stride_bytes, size_t pix_stride_bytes, void* out_u32_dev, void* stream);
 
 /* gather matched coordinates on the device: pts1/pts2 n_matches x 2 float */
 int apds_dev_points_from_matches(const void* kp1, int n1, const void* kp2, int n2, const void* matches, int n_matches,

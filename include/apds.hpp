@@ -307,14 +307,18 @@ inline Result<ExtractedKeyPoint, Error> akaze_keypoint_descriptor_extraction_def
     return R::Ok(std::move(out));
 }
 /// The same with detectAndCompute's `mask` (lib.rs:75-79 passes Mat::default()): rows x cols u8, non-zero = keep, nullptr = unmasked. A keypoint
-/// goes iff mask[(int)(y + 0.5f)][(int)(x + 0.5f)] == 0 at its refined position; max_points cuts what is left.
+/// goes iff mask[(int)(y + 0.5f)][(int)(x + 0.5f)] == 0 at its refined position; max_points cuts what is left. mask_support > 0: iff any mask
+/// byte is zero within mask_support * scale * 2^octave pixels of that position (apds_akaze_extract_masked_support; APDS_MASK_SUPPORT_DESCRIPTOR
+/// covers the descriptor).
 inline Result<ExtractedKeyPoint, Error> akaze_keypoint_descriptor_extraction(const uint8_t* img, int rows, int cols, int channels, size_t stride_bytes,
-                                                                            const uint8_t* mask, size_t mask_stride_bytes, std::optional<int> max_points) {
+                                                                            const uint8_t* mask, size_t mask_stride_bytes, std::optional<int> max_points,
+                                                                            int mask_support = 0) {
     using R = Result<ExtractedKeyPoint, Error>;
     apds_keypoint* kps = nullptr;
     uint8_t* desc = nullptr;
     int n = 0, nb = 0;
-    const int rc = apds_akaze_extract_masked(img, rows, cols, channels, stride_bytes, mask, mask_stride_bytes, max_points.value_or(MAX_POINTS), &kps, &desc, &n, &nb);
+    const int rc = apds_akaze_extract_masked_support(img, rows, cols, channels, stride_bytes, mask, mask_stride_bytes, mask_support, max_points.value_or(MAX_POINTS),
+                                                     &kps, &desc, &n, &nb);
     if (rc != 0) return R::Err(last_error(rc));
     ExtractedKeyPoint out;
     out.keypoints.assign(kps, kps + n);
