@@ -41,6 +41,7 @@ SYMBOLS = [
     "apds_tile_extract_ex", "apds_tile_extract_batch_ex", "apds_mosaic_tile_extract_ex", "apds_mosaic_tile_extract_batch_ex",
     "apds_akaze_extract_masked_support", "apds_akaze_extract_batch_masked_support", "apds_dev_akaze_extract_masked_support",
     "apds_dev_akaze_extract_batch_masked_support", "apds_dev_mask_zero_sat",
+    "apds_db_insert_dev", "apds_db_insert_batch_dev", "apds_mosaic_tiles_to_db", "apds_db_world_coordinates", "apds_db_table",
 ]
 
 RESAMPLE_NEAREST, RESAMPLE_LANCZOS = 0, 1
@@ -275,6 +276,11 @@ def lib():
             "apds_dev_akaze_extract_masked_support": (i, [vp, i, i, i, sz, vp, sz, i, i, vp, vp, i, ip, vp]),
             "apds_dev_akaze_extract_batch_masked_support": (i, [vp, i, sz, i, i, i, sz, vp, sz, sz, i, i, vp, vp, i, ip, vp]),
             "apds_dev_mask_zero_sat": (i, [vp, i, i, sz, sz, vp, vp]),
+            "apds_db_insert_dev": (i, [vp, vp, vp, i, i, i, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, vp]),
+            "apds_db_insert_batch_dev": (i, [vp, vp, vp, i, i, vp, i, i, vp, C.c_uint64, C.c_uint64, vp]),
+            "apds_mosaic_tiles_to_db": (i, [vp, vp, vp, i, i, i, i, i, i, vp, i, i, i, i, vp, ip]),
+            "apds_db_world_coordinates": (i, [vp, vp, vp, vp, i, i, i, C.POINTER(i64)]),
+            "apds_db_table": (i, [vp, pp, pp, pp, C.POINTER(i64)]),
         }
         for name, (rt, at) in sig.items():
             fn = getattr(L, name)

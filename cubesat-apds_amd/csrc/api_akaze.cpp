@@ -307,6 +307,41 @@ int apds_mosaic_tile_extract(void* mosaic, int x0, int y0, int win_w, int win_h,
     return apds_mosaic_tile_extract_ex(mosaic, x0, y0, win_w, win_h, out_w, out_h, resample, minmax6, max_points, APDS_TILE_MASK_NONE, kps, desc, n, desc_bytes);
 }
 
+// The front of the two calls below: the checks of the batch call, then window read -> band_merger -> batched extraction of n_tiles windows
+// of the resident mosaic on the calling thread's stream, in its (reset) workspace. counts[] is final on return; the rows stay on the device
+// (tile i at i * capacity rows) with the descriptor kernels still queued on `s`.
+struct MosaicBatchRows {
+    apds_keypoint* kps;
+    uint8_t* desc64;
+    int capacity;
+    hipStream_t s;
+};
+static MosaicBatchRows mosaic_tiles_extract_device(ThreadCtx& c, Mosaic* m, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample,
+                                                   const double* minmax6, int max_points, int mask_mode, int* counts) {
+    check_mask_mode(mask_mode);
+    mosaic_check_window(m, 0, xy0, n_tiles, win_w, win_h, out_w, out_h, resample);
+    if (max_points <= 0) max_points = APDS_MAX_POINTS;
+    for (int i = 0; i < n_tiles; i++) counts[i] = 0;
+    double own[6];
+    if (!minmax6) {
+        mosaic_min_max(m, own);
+        minmax6 = own;
+    }
+    c.ws_reset();
+    hipStream_t s = c.stream;
+    const size_t px = (size_t)out_w * out_h, all = px * n_tiles;
+    float* bands = c.alloc_n<float>(3 * all);   // band-major: all tiles' red, then green, then blue
+    uint8_t* dimg = c.alloc_n<uint8_t>(all * 4);
+    const int capacity = batch_capacity(out_h, out_w, max_points);
+    apds_keypoint* dk = c.alloc_n<apds_keypoint>((size_t)capacity * n_tiles);
+    uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * 64 * n_tiles);
+    mosaic_read_device(m, xy0, n_tiles, win_w, win_h, out_w, out_h, resample, bands, s);
+    band_merger_device(bands, bands + all, bands + 2 * all, all, minmax6, /*bgra=*/1, dimg, s);
+    akaze_extract_batch_device(dimg, n_tiles, px * 4, out_h, out_w, 4, (size_t)out_w * 4, tile_mask(mask_mode, dimg, out_h, out_w), tile_mask_support(mask_mode),
+                               max_points, dk, dd, capacity, counts, s);
+    return MosaicBatchRows{dk, dd, capacity, s};
+}
+
 // apds_tile_extract_batch on n_tiles windows of the resident mosaic: ONE resampling launch per pass, ONE band_merger pass and ONE batched
 // extraction serve all tiles.
 int apds_mosaic_tile_extract_batch_ex(void* mosaic, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample,
@@ -317,30 +352,28 @@ int apds_mosaic_tile_extract_batch_ex(void* mosaic, const int32_t* xy0, int n_ti
         *kps = nullptr;
         *desc = nullptr;
         *desc_bytes = APDS_DESC_BYTES;
-        check_mask_mode(mask_mode);
-        Mosaic* m = static_cast<Mosaic*>(mosaic);
-        mosaic_check_window(m, 0, xy0, n_tiles, win_w, win_h, out_w, out_h, resample);
-        if (max_points <= 0) max_points = APDS_MAX_POINTS;
-        for (int i = 0; i < n_tiles; i++) counts[i] = 0;
-        double own[6];
-        if (!minmax6) {
-            mosaic_min_max(m, own);
-            minmax6 = own;
-        }
         ThreadCtx& c = ctx();
-        c.ws_reset();
-        hipStream_t s = c.stream;
-        const size_t px = (size_t)out_w * out_h, all = px * n_tiles;
-        float* bands = c.alloc_n<float>(3 * all);   // band-major: all tiles' red, then green, then blue
-        uint8_t* dimg = c.alloc_n<uint8_t>(all * 4);
-        const int capacity = batch_capacity(out_h, out_w, max_points);
-        apds_keypoint* dk = c.alloc_n<apds_keypoint>((size_t)capacity * n_tiles);
-        uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * 64 * n_tiles);
-        mosaic_read_device(m, xy0, n_tiles, win_w, win_h, out_w, out_h, resample, bands, s);
-        band_merger_device(bands, bands + all, bands + 2 * all, all, minmax6, /*bgra=*/1, dimg, s);
-        akaze_extract_batch_device(dimg, n_tiles, px * 4, out_h, out_w, 4, (size_t)out_w * 4, tile_mask(mask_mode, dimg, out_h, out_w),
-                                   tile_mask_support(mask_mode), max_points, dk, dd, capacity, counts, s);
-        batch_results_to_host(c, s, dk, dd, capacity, n_tiles, counts, kps, desc);
+        const MosaicBatchRows r = mosaic_tiles_extract_device(c, static_cast<Mosaic*>(mosaic), xy0, n_tiles, win_w, win_h, out_w, out_h, resample, minmax6, max_points,
+                                                              mask_mode, counts);
+        batch_results_to_host(c, r.s, r.kps, r.desc64, r.capacity, n_tiles, counts, kps, desc);
+    });
+}
+
+// The DB build of a group of tiles in one call (preprocessor/src/main.rs:197-327): the call above up to the extraction, then the rows go
+// from the extraction's buffers into the keypoint table on the same stream. Only counts[] reaches the host.
+int apds_mosaic_tiles_to_db(void* mosaic, void* db, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample,
+                            const double* minmax6, int max_points, int mask_mode, int first_image_id, int level_of_detail, const uint32_t* columns_rows,
+                            int* counts) {
+    APDS_RANGE("apds_mosaic_tiles_to_db");
+    return guarded([&] {
+        APDS_REQUIRE(mosaic && db && counts && columns_rows, APDS_ERR_BAD_ARG, "null argument");
+        APDS_REQUIRE(level_of_detail >= 0 && level_of_detail < 31, APDS_ERR_BAD_ARG, "bad level of detail");
+        Mosaic* m = static_cast<Mosaic*>(mosaic);
+        APDS_REQUIRE(mosaic_device(m) == table_device(db), APDS_ERR_BAD_ARG, "the mosaic and the keypoint table live on different devices");
+        ThreadCtx& c = ctx();
+        const MosaicBatchRows r = mosaic_tiles_extract_device(c, m, xy0, n_tiles, win_w, win_h, out_w, out_h, resample, minmax6, max_points, mask_mode, counts);
+        table_insert_batch_device(db, r.kps, r.desc64, n_tiles, r.capacity, counts, first_image_id, level_of_detail, columns_rows, (uint64_t)out_w, (uint64_t)out_h,
+                                  r.s);
     });
 }
 

@@ -243,12 +243,10 @@ __device__ __forceinline__ void signed_sincos(double a, double& s, double& c) {
     if (neg) s = -s;
 }
 
-__global__ void world_coordinates_kernel(const double* __restrict__ xy, int n, GeoTransform dgt, GeoTransform inv_egt, int has_elev,
-                                         const double* __restrict__ elev, int ew, int eh, double* __restrict__ xyz, int* __restrict__ missing) {
-    APDS_RAISE_WAVE_PRIORITY();
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double x = xy[2 * i], y = xy[2 * i + 1];
+// One point: out3 = its world point, or three NaNs and `false` when the elevation lookup misses the raster. The one copy of the
+// arithmetic: both kernels below call it.
+__device__ __forceinline__ bool world_point(double x, double y, const GeoTransform& dgt, const GeoTransform& inv_egt, int has_elev,
+                                            const double* __restrict__ elev, int ew, int eh, double* __restrict__ out3) {
     const double gx = dgt.c[0] + x * dgt.c[1] + y * dgt.c[2];
     const double gy = dgt.c[3] + x * dgt.c[4] + y * dgt.c[5];
     double h = 0.0;
@@ -257,10 +255,9 @@ __global__ void world_coordinates_kernel(const double* __restrict__ xy, int n, G
         const double py = inv_egt.c[3] + gx * inv_egt.c[4] + gy * inv_egt.c[5];
         const long long id0 = (long long)(int)round(py) * ew + (long long)(int)round(px);
         if (id0 < 0 || id0 >= (long long)ew * eh) {
-            *missing = 1;
             const double nanv = __longlong_as_double(0x7FF8000000000000ll);
-            xyz[3 * i] = xyz[3 * i + 1] = xyz[3 * i + 2] = nanv;
-            return;
+            out3[0] = out3[1] = out3[2] = nanv;
+            return false;
         }
         h = elev[id0];
     }
@@ -269,9 +266,31 @@ __global__ void world_coordinates_kernel(const double* __restrict__ xy, int n, G
     signed_sincos(gy * deg, sp, cp);
     signed_sincos(gx * deg, sl, cl);
     const double N = a / sqrt(1.0 - es * sp * sp);
-    xyz[3 * i] = (N + h) * cp * cl;
-    xyz[3 * i + 1] = (N + h) * cp * sl;
-    xyz[3 * i + 2] = (N * (1.0 - es) + h) * sp;
+    out3[0] = (N + h) * cp * cl;
+    out3[1] = (N + h) * cp * sl;
+    out3[2] = (N * (1.0 - es) + h) * sp;
+    return true;
+}
+
+__global__ void world_coordinates_kernel(const double* __restrict__ xy, int n, GeoTransform dgt, GeoTransform inv_egt, int has_elev,
+                                         const double* __restrict__ elev, int ew, int eh, double* __restrict__ xyz, int* __restrict__ missing) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (!world_point(xy[2 * i], xy[2 * i + 1], dgt, inv_egt, has_elev, elev, ew, eh, xyz + 3 * (size_t)i)) *missing = 1;
+}
+
+// The same for points kept as two f32 columns (the keypoint table's x and y): (double)x[i], (double)y[i], no xy array in between. The rows
+// that miss are COUNTED: a ballot, then one integer atomic add per wave, so the count does not depend on the order the waves arrive in.
+__global__ __launch_bounds__(256) void world_coordinates_columns_kernel(const float* __restrict__ x, const float* __restrict__ y, int n, GeoTransform dgt,
+                                                                        GeoTransform inv_egt, int has_elev, const double* __restrict__ elev, int ew, int eh,
+                                                                        double* __restrict__ xyz, unsigned int* __restrict__ n_missing) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool miss = false;
+    if (i < n) miss = !world_point((double)x[i], (double)y[i], dgt, inv_egt, has_elev, elev, ew, eh, xyz + 3 * (size_t)i);
+    const unsigned long long b = __ballot(miss);
+    if (b && (threadIdx.x & 63) == 0) atomicAdd(n_missing, (unsigned int)__popcll(b));
 }
 
 bool invert_geotransform(const double* gt, double* out) {   // GDALInvGeoTransform
@@ -312,6 +331,23 @@ int world_coordinates_device(const double* xy, int n, const double* dgt_host, co
     HIP_CHECK(hipMemcpyAsync(&m, missing, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     return m;
+}
+
+// the column form: x, y device f32 columns of n points; returns the number of points whose elevation lookup missed (those are NaN)
+int64_t world_coordinates_columns_device(const float* x, const float* y, int n, const double* dgt_host, const double* egt_host, const double* elev, int ew,
+                                         int eh, double* xyz, hipStream_t s) {
+    GeoTransform d{}, inv{};
+    for (int i = 0; i < 6; i++) d.c[i] = dgt_host[i];
+    if (egt_host) APDS_REQUIRE(invert_geotransform(egt_host, inv.c), APDS_ERR_BAD_ARG, "elevation geotransform is not invertible");
+    if (n <= 0) return 0;
+    unsigned int* missing = ctx().alloc_n<unsigned int>(1);
+    HIP_CHECK(hipMemsetAsync(missing, 0, sizeof(unsigned int), s));
+    hipLaunchKernelGGL(world_coordinates_columns_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, x, y, n, d, inv, egt_host ? 1 : 0, elev, ew, eh, xyz, missing);
+    HIP_CHECK(hipGetLastError());
+    unsigned int m = 0;
+    HIP_CHECK(hipMemcpyAsync(&m, missing, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return (int64_t)m;
 }
 
 }  // namespace apds

@@ -79,12 +79,22 @@ void warp_perspective_any_device(const void* src, int rows, int cols, int channe
                                  hipStream_t s);
 int world_coordinates_device(const double* xy, int n, const double* dgt_host, const double* egt_host, const double* elev, int ew, int eh, double* xyz,
                              hipStream_t s);
+int64_t world_coordinates_columns_device(const float* x, const float* y, int n, const double* dgt_host, const double* egt_host, const double* elev, int ew,
+                                         int eh, double* xyz, hipStream_t s);   // x, y: device f32 columns; returns the number of missed lookups
+
+// keypoint_table.hip: the device a table lives on; n_tiles tiles of an extraction's device output (tile i at i * capacity rows) appended in
+// tile order by one launch on s (checks first, then writes; takes its small tile table from the calling thread's workspace WITHOUT
+// resetting it; synchronises s)
+int table_device(const void* db);
+void table_insert_batch_device(void* db, const void* kps_dev, const void* desc64_dev, int n_tiles, int capacity, const int32_t* counts, int first_image_id,
+                               int lod, const uint32_t* columns_rows, uint64_t tile_w, uint64_t tile_h, hipStream_t s);
 
 // mosaic.hip: the mosaic resident in HBM (apds_mosaic_*). check_window throws what the entry points report for windows of the raster of
 // `level` (0: the base raster); read_device writes out[band][tile][out_h][out_w] f32 (the layout band_merger_device reads a batch in) and
 // returns when the kernels are done: the base-raster windows themselves, or, on a handle with overviews, their image on the level GDAL
 // would serve the read from.
 struct Mosaic;
+int mosaic_device(const Mosaic* m);   // the device the handle's raster lives on
 void mosaic_check_window(const Mosaic* m, int level, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample);
 void mosaic_read_device(const Mosaic* m, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample, float* out, hipStream_t s);
 void mosaic_min_max(Mosaic* m, double* minmax6);   // cached in the handle; resets the calling thread's workspace when it computes

@@ -29,11 +29,37 @@ struct KeypointTable {
     apds_keypoint* view_kps = nullptr;
     int* view_image_id = nullptr;
     uint8_t* view_desc64 = nullptr;
+    // the whole table in the pipeline's layout (apds_db_table): 28-byte keypoints by row, gathered up to row all_kps_rows; the world point
+    // of every row (apds_db_world_coordinates), valid for the first xyz_rows rows (-1: never computed). Both allocated on first use.
+    apds_keypoint* all_kps = nullptr;
+    int64_t all_kps_rows = 0;
+    double* xyz = nullptr;
+    int64_t xyz_rows = -1;
 };
 
+struct TableColumns {
+    float *x, *y, *size, *angle, *response;
+    int *octave, *class_id, *image_id, *lod;
+    uint32_t* desc64;
+};
+
+// The keypoint columns of table row r from one extracted keypoint: the ONE copy of the coordinate lift, whichever side the row comes from.
+// main.rs:299-300: x * 2^lod + (column * tile_w * 2^lod) as f32 (scale = 2^lod; xoff, yoff: the u64 products rounded once to f32)
+__device__ __forceinline__ void store_keypoint_columns(const TableColumns& c, long long r, const apds_keypoint& k, float scale, float xoff, float yoff,
+                                                       int image_id, int lod) {
+    c.x[r] = k.x * scale + xoff;
+    c.y[r] = k.y * scale + yoff;
+    c.size[r] = k.size;
+    c.angle[r] = k.angle;
+    c.response[r] = k.response;
+    c.octave[r] = k.octave;
+    c.class_id[r] = k.class_id;
+    c.image_id[r] = image_id;
+    c.lod[r] = lod;
+}
+
 __global__ void table_insert_kernel(const apds_keypoint* __restrict__ kps, const uint8_t* __restrict__ desc61, int n, int image_id, int lod,
-                                    float scale, float xoff, float yoff, long long base, float* x, float* y, float* size, float* angle,
-                                    float* response, int* octave, int* class_id, int* img, int* lodcol, uint32_t* desc64) {
+                                    float scale, float xoff, float yoff, long long base, TableColumns c) {
     APDS_RAISE_WAVE_PRIORITY();
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (long long)n * 16) return;
@@ -42,20 +68,51 @@ __global__ void table_insert_kernel(const apds_keypoint* __restrict__ kps, const
 #pragma unroll
     for (int b = 0; b < 4; b++)
         if (w * 4 + b < 61) v |= (uint32_t)desc61[(size_t)i * 61 + w * 4 + b] << (8 * b);
-    desc64[(base + i) * 16 + w] = v;
-    if (w == 0) {
-        const apds_keypoint k = kps[i];
-        // main.rs:299-300: x * 2^lod + (column * tile_w * 2^lod) as f32
-        x[base + i] = k.x * scale + xoff;
-        y[base + i] = k.y * scale + yoff;
-        size[base + i] = k.size;
-        angle[base + i] = k.angle;
-        response[base + i] = k.response;
-        octave[base + i] = k.octave;
-        class_id[base + i] = k.class_id;
-        img[base + i] = image_id;
-        lodcol[base + i] = lod;
+    c.desc64[(base + i) * 16 + w] = v;
+    if (w == 0) store_keypoint_columns(c, base + i, kps[i], scale, xoff, yoff, image_id, lod);
+}
+
+// The same rows from the device buffers an extraction has written (28-byte keypoints, 64-byte descriptor rows; tile i at i * capacity
+// rows), every tile of a batch in one launch: 16 lanes per table row, one dword each. tile_offsets[i] = rows of the tiles < i
+// (tile_offsets[n_tiles] = all rows), copied to LDS; a row group finds its tile by binary search (empty tiles repeat an offset: the last
+// tile whose offset is <= the row is the one that holds it). tile_xy_off[i] = that tile's (xoff, yoff). Bytes 61-63 of a source row are
+// not trusted: word 15 keeps byte 60 alone.
+__global__ __launch_bounds__(256) void table_insert_dev_kernel(const apds_keypoint* __restrict__ kps, const uint32_t* __restrict__ desc64_src, int n_tiles,
+                                                               int capacity, const int* __restrict__ tile_offsets, const float2* __restrict__ tile_xy_off,
+                                                               int first_image_id, int lod, float scale, long long base, TableColumns c) {
+    APDS_RAISE_WAVE_PRIORITY();
+    extern __shared__ int offs[];   // n_tiles + 1
+    for (int i = threadIdx.x; i <= n_tiles; i += blockDim.x) offs[i] = tile_offsets[i];
+    __syncthreads();
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)offs[n_tiles] * 16) return;
+    const int r = (int)(t >> 4), w = (int)(t & 15);
+    int lo = 0, hi = n_tiles - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (offs[mid] <= r) lo = mid;
+        else hi = mid - 1;
     }
+    const long long src = (long long)lo * capacity + (r - offs[lo]);
+    uint32_t v = desc64_src[src * 16 + w];
+    if (w == 15) v &= 0xFFu;
+    c.desc64[(base + r) * 16 + w] = v;
+    if (w == 0) {
+        const float2 o = tile_xy_off[lo];
+        store_keypoint_columns(c, base + r, kps[src], scale, o.x, o.y, first_image_id + lo, lod);
+    }
+}
+
+// rows [from, from + n) of the columns as 28-byte keypoints (what the pipeline takes for its train rows)
+__global__ void table_keypoints_kernel(TableColumns c, long long from, int n, apds_keypoint* __restrict__ out) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long r = from + i;
+    apds_keypoint k;
+    k.x = c.x[r]; k.y = c.y[r]; k.size = c.size[r]; k.angle = c.angle[r]; k.response = c.response[r];
+    k.octave = c.octave[r]; k.class_id = c.class_id[r];
+    out[r] = k;
 }
 
 struct SelectArgs {
@@ -185,11 +242,62 @@ void dev_alloc(T*& p, size_t n) {
 void table_free(KeypointTable* t) {
     for (void* p : {(void*)t->x, (void*)t->y, (void*)t->size, (void*)t->angle, (void*)t->response, (void*)t->octave, (void*)t->class_id,
                     (void*)t->image_id, (void*)t->lod, (void*)t->desc64, (void*)t->view_rows, (void*)t->view_kps, (void*)t->view_image_id,
-                    (void*)t->view_desc64})
+                    (void*)t->view_desc64, (void*)t->all_kps, (void*)t->xyz})
         if (p) (void)hipFree(p);
     delete t;
 }
+TableColumns columns_of(KeypointTable* t) {
+    return TableColumns{t->x, t->y, t->size, t->angle, t->response, t->octave, t->class_id, t->image_id, t->lod, reinterpret_cast<uint32_t*>(t->desc64)};
+}
+float lift_offset(uint64_t index, uint64_t tile, int lod) { return (float)(index * tile * (1ull << lod)); }   // (u64 product) as f32
 }  // namespace
+
+namespace apds {
+
+int table_device(const void* db) {
+    APDS_REQUIRE(db, APDS_ERR_BAD_ARG, "null table");
+    return static_cast<const KeypointTable*>(db)->device;
+}
+
+// n_tiles tiles of an extraction's device output appended in tile order by one launch on s; the small tile table comes from the calling
+// thread's workspace (no ws_reset here: the extraction's buffers may live there). Everything is checked before anything is written.
+// Synchronises s.
+void table_insert_batch_device(void* db, const void* kps_dev, const void* desc64_dev, int n_tiles, int capacity, const int32_t* counts, int first_image_id,
+                               int lod, const uint32_t* columns_rows, uint64_t tile_w, uint64_t tile_h, hipStream_t s) {
+    KeypointTable* t = static_cast<KeypointTable*>(db);
+    APDS_REQUIRE(t && lod >= 0 && lod < 31 && capacity >= 0, APDS_ERR_BAD_ARG, "bad argument");
+    APDS_REQUIRE(n_tiles >= 1 && n_tiles <= 4096, APDS_ERR_BAD_ARG, "batch must hold 1 .. 4096 tiles");
+    APDS_REQUIRE(counts && columns_rows, APDS_ERR_BAD_ARG, "null argument");
+    const size_t xy_at = ((size_t)n_tiles + 2) & ~size_t(1);             // an even number of ints: the float2 rows stay 8-byte aligned
+    std::vector<int> table(xy_at + 2 * (size_t)n_tiles);                 // offsets (n_tiles + 1), then (xoff, yoff) per tile as float bits
+    float* xy = reinterpret_cast<float*>(table.data() + xy_at);
+    int64_t total = 0;
+    for (int i = 0; i < n_tiles; i++) {
+        APDS_REQUIRE(counts[i] >= 0 && counts[i] <= capacity, APDS_ERR_BAD_ARG, "a tile's count is negative or exceeds the capacity");
+        total += counts[i];
+    }
+    APDS_REQUIRE(t->n + total <= t->capacity, APDS_ERR_NOMEM, "keypoint table is full");
+    for (int i = 0, off = 0; i < n_tiles; off += counts[i], i++) {
+        table[i] = off;
+        xy[2 * i] = lift_offset(columns_rows[2 * i], tile_w, lod);
+        xy[2 * i + 1] = lift_offset(columns_rows[2 * i + 1], tile_h, lod);
+    }
+    table[n_tiles] = (int)total;
+    if (!total) return;
+    APDS_REQUIRE(kps_dev && desc64_dev, APDS_ERR_BAD_ARG, "null argument");
+    APDS_REQUIRE(reinterpret_cast<uintptr_t>(kps_dev) % 4 == 0 && reinterpret_cast<uintptr_t>(desc64_dev) % 4 == 0, APDS_ERR_BAD_ARG,
+                 "device keypoints and descriptor rows must be 4-byte aligned");
+    int* dtab = ctx().alloc_n<int>(table.size());
+    HIP_CHECK(hipMemcpyAsync(dtab, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(table_insert_dev_kernel, dim3(ceil_div(total * 16, 256)), dim3(256), ((size_t)n_tiles + 1) * sizeof(int), s,
+                       static_cast<const apds_keypoint*>(kps_dev), static_cast<const uint32_t*>(desc64_dev), n_tiles, capacity, (const int*)dtab,
+                       reinterpret_cast<const float2*>(dtab + xy_at), first_image_id, lod, ldexpf(1.0f, lod), (long long)t->n, columns_of(t));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));
+    t->n += total;
+}
+
+}  // namespace apds
 
 extern "C" {
 
@@ -240,14 +348,91 @@ int apds_db_insert_image(void* db, const apds_keypoint* kps, const uint8_t* desc
         HIP_CHECK(hipMemcpyAsync(dk, kps, (size_t)n * sizeof(apds_keypoint), hipMemcpyHostToDevice, s));
         HIP_CHECK(hipMemcpyAsync(dd, desc61, (size_t)n * 61, hipMemcpyHostToDevice, s));
         const float scale = ldexpf(1.0f, lod);                                   // 2_f32.powi(lod)
-        const float xoff = (float)(column * tile_w * (1ull << lod));               // (u64 product) as f32
-        const float yoff = (float)(row * tile_h * (1ull << lod));
+        const float xoff = lift_offset(column, tile_w, lod), yoff = lift_offset(row, tile_h, lod);
         hipLaunchKernelGGL(table_insert_kernel, dim3(ceil_div((long long)n * 16, 256)), dim3(256), 0, s, (const apds_keypoint*)dk, (const uint8_t*)dd, n,
-                           image_id, lod, scale, xoff, yoff, (long long)t->n, t->x, t->y, t->size, t->angle, t->response, t->octave, t->class_id, t->image_id,
-                           t->lod, reinterpret_cast<uint32_t*>(t->desc64));
+                           image_id, lod, scale, xoff, yoff, (long long)t->n, columns_of(t));
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(s));
         t->n += n;
+    });
+}
+
+// the same rows from what apds_dev_akaze_extract has written on the device (no upload, no repack): one tile, then a batch of them
+int apds_db_insert_batch_dev(void* db, const void* kps_dev, const void* desc64_dev, int n_tiles, int capacity, const int32_t* counts, int first_image_id,
+                             int lod, const uint32_t* columns_rows, uint64_t tile_w, uint64_t tile_h, void* stream) {
+    return guarded([&] {
+        hipStream_t s = pick_stream(stream);
+        ctx().ws_reset(s);
+        table_insert_batch_device(db, kps_dev, desc64_dev, n_tiles, capacity, counts, first_image_id, lod, columns_rows, tile_w, tile_h, s);
+    });
+}
+
+int apds_db_insert_dev(void* db, const void* kps_dev, const void* desc64_dev, int n, int image_id, int lod, uint64_t column, uint64_t row, uint64_t tile_w,
+                       uint64_t tile_h, void* stream) {
+    return guarded([&] {
+        APDS_REQUIRE(column <= 0xFFFFFFFFull && row <= 0xFFFFFFFFull, APDS_ERR_BAD_ARG, "tile column / row beyond 32 bits");
+        const int32_t counts[1] = {n};
+        const uint32_t cr[2] = {(uint32_t)column, (uint32_t)row};
+        hipStream_t s = pick_stream(stream);
+        ctx().ws_reset(s);
+        table_insert_batch_device(db, kps_dev, desc64_dev, 1, std::max(n, 0), counts, image_id, lod, cr, tile_w, tile_h, s);
+    });
+}
+
+// The world point of every row (ingest.hip's arithmetic on ((double)x, (double)y)) into the table's xyz column; a row whose elevation
+// lookup misses is three NaNs and is counted in *n_missing.
+int apds_db_world_coordinates(void* db, const double* dataset_gt, const double* elevation_gt, const void* elevation, int ew, int eh, int elevation_on_device,
+                              int64_t* n_missing) {
+    return guarded([&] {
+        KeypointTable* t = static_cast<KeypointTable*>(db);
+        APDS_REQUIRE(t && dataset_gt, APDS_ERR_BAD_ARG, "null argument");
+        APDS_REQUIRE(!elevation_gt || (elevation && ew > 0 && eh > 0), APDS_ERR_BAD_ARG, "elevation geotransform without a raster");
+        if (n_missing) *n_missing = 0;
+        ThreadCtx& c = ctx();
+        APDS_REQUIRE(t->device == c.device, APDS_ERR_BAD_ARG, "the table lives on another device than the calling thread's");
+        c.ws_reset();
+        hipStream_t s = c.stream;
+        if (!t->xyz) dev_alloc(t->xyz, (size_t)t->capacity * 3);
+        const double* del = nullptr;
+        if (elevation_gt) {
+            del = static_cast<const double*>(elevation);
+            if (!elevation_on_device) {
+                double* up = c.alloc_n<double>((size_t)ew * eh);
+                HIP_CHECK(hipMemcpyAsync(up, elevation, (size_t)ew * eh * sizeof(double), hipMemcpyHostToDevice, s));
+                del = up;
+            }
+        }
+        t->xyz_rows = -1;
+        const int64_t miss = world_coordinates_columns_device(t->x, t->y, (int)t->n, dataset_gt, elevation_gt, del, ew, eh, t->xyz, s);
+        t->xyz_rows = t->n;
+        if (n_missing) *n_missing = miss;
+    });
+}
+
+// The whole table as the arguments the pipeline takes: its own descriptor column, 28-byte keypoints by row (gathered here for the rows
+// added since the last call) and the xyz column while it covers every row.
+int apds_db_table(void* db, void** rows64_dev, void** kps_dev, void** xyz_dev, int64_t* n) {
+    return guarded([&] {
+        KeypointTable* t = static_cast<KeypointTable*>(db);
+        APDS_REQUIRE(t, APDS_ERR_BAD_ARG, "null table");
+        if (kps_dev) {
+            ThreadCtx& c = ctx();
+            APDS_REQUIRE(t->device == c.device, APDS_ERR_BAD_ARG, "the table lives on another device than the calling thread's");
+            if (!t->all_kps) dev_alloc(t->all_kps, (size_t)t->capacity);
+            const int64_t fresh = t->n - t->all_kps_rows;
+            if (fresh > 0) {
+                hipStream_t s = c.stream;
+                hipLaunchKernelGGL(table_keypoints_kernel, dim3(ceil_div(fresh, 256)), dim3(256), 0, s, columns_of(t), (long long)t->all_kps_rows, (int)fresh,
+                                   t->all_kps);
+                HIP_CHECK(hipGetLastError());
+                HIP_CHECK(hipStreamSynchronize(s));
+                t->all_kps_rows = t->n;
+            }
+            *kps_dev = t->all_kps;
+        }
+        if (rows64_dev) *rows64_dev = t->desc64;
+        if (xyz_dev) *xyz_dev = (t->xyz && t->xyz_rows == t->n) ? t->xyz : nullptr;
+        if (n) *n = t->n;
     });
 }
 

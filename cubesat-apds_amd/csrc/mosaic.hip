@@ -408,6 +408,11 @@ T* upload(ThreadCtx& c, const std::vector<T>& v, hipStream_t s) {
 
 }  // namespace
 
+int mosaic_device(const Mosaic* m) {
+    APDS_REQUIRE(m, APDS_ERR_BAD_ARG, "null argument");
+    return m->device;
+}
+
 void mosaic_check_window(const Mosaic* m, int level, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample) {
     APDS_REQUIRE(m && xy0, APDS_ERR_BAD_ARG, "null argument");
     APDS_REQUIRE(level >= 0 && level <= m->n_levels(), APDS_ERR_OUT_OF_RANGE, "the mosaic has no such overview level");

@@ -48,6 +48,36 @@ class KeypointTable:
         check(lib().apds_db_insert_image(self._h, ptr(kp), ptr(d), len(kp), int(image_id), int(level_of_detail), int(column), int(row),
                                          int(tile_size[0]), int(tile_size[1])))
 
+    def create_keypoints_device(self, kps_ptr, desc64_ptr, n, image_id, level_of_detail=0, column=0, row=0, tile_size=(0, 0), stream=None):
+        """create_keypoints for rows that are already on the device: kps_ptr / desc64_ptr are what apds_dev_akaze_extract wrote (28-byte
+        keypoints, 64-byte descriptor rows), `stream` the stream it was issued on (None: the calling thread's own). Same stored rows."""
+        check(lib().apds_db_insert_dev(self._h, kps_ptr, desc64_ptr, int(n), int(image_id), int(level_of_detail), int(column), int(row),
+                                       int(tile_size[0]), int(tile_size[1]), stream))
+
+    def world_coordinates(self, elevation_table, elevation_dev_ptr=None):
+        """The world point (ElevationTable.get_world_coordinates_batch's arithmetic on float64(x), float64(y)) of every row, into the
+        table's own xyz column on the device. Returns n_missing: the rows whose elevation lookup missed the raster (three NaNs each; no
+        exception). elevation_dev_ptr: the elevation raster (float64, the shape of elevation_table.elevation) already on the device."""
+        dgt = elevation_table.transforms["dataset"]
+        el = elevation_table.elevation
+        egt = elevation_table.transforms.get("elevation") if el is not None else None
+        miss = C.c_int64(0)
+        if egt is None:
+            check(lib().apds_db_world_coordinates(self._h, ptr(dgt), None, None, 0, 0, 0, C.byref(miss)))
+        elif elevation_dev_ptr is not None:
+            check(lib().apds_db_world_coordinates(self._h, ptr(dgt), ptr(egt), elevation_dev_ptr, el.shape[1], el.shape[0], 1, C.byref(miss)))
+        else:
+            check(lib().apds_db_world_coordinates(self._h, ptr(dgt), ptr(egt), ptr(el), el.shape[1], el.shape[0], 0, C.byref(miss)))
+        return miss.value
+
+    def device_table(self):
+        """(rows64, kps, xyz, n): device pointers of the WHOLE table in the layout a pipeline takes (descriptor rows, 28-byte keypoints,
+        world points; all indexed by table row = id - 1). xyz is None unless world_coordinates() has run since the last insert. The
+        pointers hold until the next insert or close()."""
+        r, k, x, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64(0)
+        check(lib().apds_db_table(self._h, C.byref(r), C.byref(k), C.byref(x), C.byref(n)))
+        return r.value, k.value, x.value, n.value
+
     def _select(self, mode, value, box=(0, 0, 0, 0)):
         n = C.c_int(0)
         check(lib().apds_db_select(self._h, mode, int(value), float(box[0]), float(box[1]), float(box[2]), float(box[3]), C.byref(n)))

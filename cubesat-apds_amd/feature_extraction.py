@@ -267,6 +267,27 @@ def mosaic_tiles_keypoint_descriptor_extraction(mosaic, windows, window_size, si
     return out
 
 
+def mosaic_tiles_to_database(mosaic, table, windows, window_size, size, columns_rows, first_image_id, level_of_detail, resample="nearest", min_max=None,
+                             max_points=None, mask_nodata=False):
+    """The batch above with its rows stored instead of returned (apds_mosaic_tiles_to_db): tile i of `windows` is extracted on the device
+    and appended to `table` (a feature_database.KeypointTable) as image first_image_id + i at tile position columns_rows[i] = (column,
+    row), exactly as table.create_keypoints would store what the call above returns. No keypoint crosses PCIe. Returns the tiles' row
+    counts."""
+    xy = np.ascontiguousarray(np.asarray(list(windows), np.int64).reshape(-1, 2), np.int32)
+    cr = np.ascontiguousarray(np.asarray(list(columns_rows), np.int64).reshape(-1, 2), np.uint32)
+    b = len(xy)
+    if len(cr) != b:
+        raise ApdsError(_lib.ERR_BAD_ARG, "one (column, row) per window")
+    if not b:
+        return []
+    mm = None if min_max is None else min_max.as_array()
+    counts = (C.c_int * b)()
+    check(lib().apds_mosaic_tiles_to_db(mosaic.handle, table._h, ptr(xy), b, int(window_size[0]), int(window_size[1]), int(size[0]), int(size[1]),
+                                        _lib.resample_mode(resample), None if mm is None else ptr(mm), MAX_POINTS if max_points is None else int(max_points),
+                                        _mask_mode(mask_nodata), int(first_image_id), int(level_of_detail), ptr(cr), counts))
+    return list(counts)
+
+
 def _desc(a):
     a = np.ascontiguousarray(a, np.uint8)
     if a.ndim != 2:

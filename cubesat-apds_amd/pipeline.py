@@ -92,6 +92,11 @@ class _DevBytes:
         self.__cuda_array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (int(addr), False), "version": 2, "strides": None}
 
 
+def _table_tensor(addr, nbytes, device, dtype, shape):
+    """A column of a KeypointTable (feature_database.py: device_table()) as a torch tensor on its memory, no copy."""
+    return torch.as_tensor(_DevBytes(addr, nbytes), device=device).view(dtype).view(shape)
+
+
 def device_transport_from_group(dist, group, device):
     """apds_device_transport (include/apds.h) over a torch.distributed process group whose collectives take DEVICE tensors ("nccl" = RCCL):
     the library's exchange buffers are wrapped as tensors in place and the collectives are issued on the stream the library names, so the
@@ -306,13 +311,28 @@ class PoseStage:
     (default EPnP, mod.rs:359); iter_count <= 0 -> 100, reproj_thres <= 0 -> 8.0, confidence outside (0, 1) -> 0.99 (solvePnPRansac's
     defaults)."""
 
-    def __init__(self, db_xyz, camera_intrinsic, origin=None, method=SOLVEPNP_EPNP, iter_count=100, reproj_thres=8.0, confidence=0.99, device="cuda:0"):
+    def __init__(self, db_xyz, camera_intrinsic, origin=None, method=SOLVEPNP_EPNP, iter_count=100, reproj_thres=8.0, confidence=0.99, device="cuda:0",
+                 db_xyz_dev=None):
         xyz = db_xyz.detach().cpu().numpy() if isinstance(db_xyz, torch.Tensor) else np.asarray(db_xyz)
         self.db_xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
         self.origin = np.asarray(self.db_xyz.mean(0) if origin is None else origin, np.float64).reshape(3).copy()
         self.K = np.ascontiguousarray(camera_intrinsic, np.float64).reshape(3, 3)
         self.method, self.iter_count, self.reproj_thres, self.confidence = int(method), int(iter_count), float(reproj_thres), float(confidence)
-        self.db_xyz_dev = torch.from_numpy(self.db_xyz).to(device)     # borrowed by the native pipeline for its whole life
+        # borrowed by the native pipeline for its whole life (db_xyz_dev: the same points already on the device, taken instead of an upload)
+        self.db_xyz_dev = torch.from_numpy(self.db_xyz).to(device) if db_xyz_dev is None else db_xyz_dev
+
+    @classmethod
+    def from_table(cls, table, camera_intrinsic, origin=None, device="cuda:0", **kw):
+        """The pose stage over the world points a KeypointTable holds on the device (table.world_coordinates() must have run since the last
+        insert): the native pipeline reads the table's own xyz column. The stage keeps the table alive; the column holds until the table's
+        next insert. The host copy (solve(), the default origin) is a download of that column."""
+        _, _, xyz, n = table.device_table()
+        if not xyz or n <= 0:
+            raise ValueError("the table has no current world points: call table.world_coordinates(elevation_table) after the last insert")
+        dev = _table_tensor(xyz, n * 24, device, torch.float64, (n, 3))
+        self = cls(dev, camera_intrinsic, origin, device=device, db_xyz_dev=dev, **kw)
+        self._table = table
+        return self
 
     def params(self):
         return _lib.PipelinePoseParams(db_xyz_dev=self.db_xyz_dev.data_ptr(), origin=(C.c_double * 3)(*self.origin), camera_intrinsic=(C.c_double * 9)(*self.K.ravel()),
@@ -419,13 +439,17 @@ class StreamedFramePipeline:
     pointers (train rows, their keypoints, frames), the transport choice for a sharded DB (ShardedMatcher), and results as dicts."""
 
     def __init__(self, db_rows64, db_xy, index_base=0, group=None, max_points=(1 << 18) - 1, device="cuda:0", slots=6, reserve_cus=0,
-                 n_cus=256, meta_group=None, extract_workers=None, transport="rccl", pose=None):
+                 n_cus=256, meta_group=None, extract_workers=None, transport="rccl", pose=None, db_kp=None):
         import os
         self.dev = torch.device(device)
         self.matcher = ShardedMatcher(db_rows64, index_base, group, meta_group=meta_group, transport=transport)
-        self.n_db = db_xy.shape[0]
-        kp = torch.zeros((self.n_db, 7), dtype=torch.float32, device=self.dev)     # 28-byte cv::KeyPoint rows of ALL train rows (x, y used)
-        kp[:, 0:2] = db_xy
+        if db_kp is not None:
+            self.n_db = db_kp.shape[0]     # the 28-byte rows themselves, already on the device (from_table)
+            kp = db_kp
+        else:
+            self.n_db = db_xy.shape[0]
+            kp = torch.zeros((self.n_db, 7), dtype=torch.float32, device=self.dev)     # 28-byte cv::KeyPoint rows of ALL train rows (x, y used)
+            kp[:, 0:2] = db_xy
         self.db_kp = kp
         self.cap = max_points
         self.n_slots = slots
@@ -449,6 +473,20 @@ class StreamedFramePipeline:
             check(lib().apds_stream_create(0, _lib.ptr(mask), words, C.byref(h)))
             self._masked_stream_handle = h
         torch.cuda.synchronize()
+
+    @classmethod
+    def from_table(cls, table, device="cuda:0", **kw):
+        """A pipeline whose database IS a KeypointTable (feature_database.py): the train rows and their keypoints are the table's own device
+        columns (table.device_table()), nothing is downloaded or re-uploaded, and a match's train index is the table row (= id - 1). The
+        pipeline keeps the table alive; nothing may be inserted into it while the pipeline lives. pose=PoseStage.from_table(table, ..) adds
+        the pose stage on the table's world points."""
+        rows64, kps, _, n = table.device_table()
+        if n <= 0:
+            raise ValueError("the table is empty")
+        self = cls(_table_tensor(rows64, n * 64, device, torch.uint8, (n, 64)), None, device=device,
+                   db_kp=_table_tensor(kps, n * 28, device, torch.float32, (n, 7)), **kw)
+        self._table = table
+        return self
 
     # ---- the native handle ------------------------------------------------------------------------------------------------------------
     def _ensure(self, shape, filter_strength, reproj_thr, max_iters, confidence, timing):

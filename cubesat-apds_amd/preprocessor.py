@@ -53,11 +53,15 @@ def extract_tile(dataset, tile_size, column, row, lod, fused=True, resample="nea
     return feature_extraction.akaze_keypoint_descriptor_extraction_def(tile_mat.mat, None)        # main.rs:277
 
 
+def create_tile_image(images, tile_size, column, row, lod):
+    """main.rs:280-293 — the image row of one tile. Returns its id."""
+    span = (tile_size[0] * 2 ** lod, tile_size[1] * 2 ** lod)
+    return images.create_image(lod, column * span[0], column * span[0] + span[0] - 1, row * span[1], row * span[1] + span[1] - 1)
+
+
 def store_tile(table, images, keypoints, tile_size, column, row, lod):
     """main.rs:280-324 — the image row and its keypoints. Returns (image_id, n_keypoints)."""
-    span = (tile_size[0] * 2 ** lod, tile_size[1] * 2 ** lod)
-    image_id = images.create_image(lod, column * span[0], column * span[0] + span[0] - 1,          # main.rs:280-293
-                                   row * span[1], row * span[1] + span[1] - 1)
+    image_id = create_tile_image(images, tile_size, column, row, lod)                              # main.rs:280-293
     # main.rs:296-324: x = x * 2^lod + column * tile_w * 2^lod (same for y), one multi-row INSERT
     table.create_keypoints(keypoints, image_id, lod, column, row, tile_size)
     return image_id, len(keypoints.keypoints)
@@ -68,17 +72,35 @@ def feature_extraction_to_database(table, images, dataset, tile_size, column, ro
     return store_tile(table, images, extract_tile(dataset, tile_size, column, row, lod, fused, resample, mask_nodata), tile_size, column, row, lod)
 
 
-def downscale_from_lod(table, images, dataset, amount_lod, lod, workers=1, fused=True, batch=1, resample="nearest", mask_nodata=False):
+def downscale_from_lod(table, images, dataset, amount_lod, lod, workers=1, fused=True, batch=1, resample="nearest", mask_nodata=False, device_insert=False):
     """main.rs:197-246 — every tile of one level. The reference spawns the tiles on a rayon pool (main.rs:233-243) and image ids
     follow whatever order the inserts reach Postgres in; here the rows are stored in row-major tile order, so ids and table contents
     depend neither on `workers` nor on `batch`. Small tiles are launch-latency-bound on the GPU, so either `batch` tiles go through
     ONE library call (apds_tile_extract_batch: every kernel's grid covers all of them; the preferred form, one host thread) or
     `workers` threads extract tiles concurrently on their own streams. With a DeviceMosaic dataset the batch call is
     apds_mosaic_tile_extract_batch: one resampling launch per pass for the whole group, no band window crosses PCIe.
-    mask_nodata (see extract_tile) reaches all three forms."""
+    mask_nodata (see extract_tile) reaches all three forms.
+    device_insert: every group of max(batch, 1) tiles of a DeviceMosaic goes through ONE call that extracts them and appends their rows to
+    the table on the device (apds_mosaic_tiles_to_db): no keypoint crosses PCIe, one synchronise per group instead of one per tile. Image
+    rows, the returned list and the table are those of the `batch` form."""
+    if device_insert and not isinstance(dataset, DeviceMosaic):
+        raise ValueError("device_insert=True needs a DeviceMosaic dataset: the rows go from the extraction to the table on the device")
     tile_size, columns, rows = tile_grid(dataset.raster_size(), amount_lod, lod)
     cells = [(j, i) for i in range(rows) for j in range(columns)]
     extra = {} if resample == "nearest" else {"resample": resample}
+    if device_insert:
+        span = (tile_size[0] * 2 ** lod, tile_size[1] * 2 ** lod)
+        step = max(int(batch), 1)
+        out = []
+        for k in range(0, len(cells), step):
+            group = cells[k:k + step]
+            ids = [create_tile_image(images, tile_size, j, i, lod) for j, i in group]
+            if ids != list(range(ids[0], ids[0] + len(ids))):
+                raise ValueError("device_insert=True needs an image table that hands out consecutive ids")
+            counts = feature_extraction.mosaic_tiles_to_database(dataset, table, [(j * span[0], i * span[1]) for j, i in group], span, tile_size, group,
+                                                                 ids[0], lod, resample, mask_nodata=mask_nodata)
+            out += list(zip(ids, counts))
+        return out
     if batch > 1:
         span = (tile_size[0] * 2 ** lod, tile_size[1] * 2 ** lod)
         out = []
@@ -143,6 +165,8 @@ def downscale_from_lod(table, images, dataset, amount_lod, lod, workers=1, fused
     return out
 
 
-def process_lod_from_mosaic(table, images, dataset, lod, workers=1, fused=True, batch=1, resample="nearest", mask_nodata=False):
+def process_lod_from_mosaic(table, images, dataset, lod, workers=1, fused=True, batch=1, resample="nearest", mask_nodata=False, device_insert=False):
     """main.rs:175-194 — all levels 0 .. lod-1."""
-    return [downscale_from_lod(table, images, dataset, lod, i, workers, fused, batch, resample, mask_nodata) for i in range(lod)]
+    if device_insert and not isinstance(dataset, DeviceMosaic):
+        raise ValueError("device_insert=True needs a DeviceMosaic dataset: the rows go from the extraction to the table on the device")
+    return [downscale_from_lod(table, images, dataset, lod, i, workers, fused, batch, resample, mask_nodata, device_insert) for i in range(lod)]

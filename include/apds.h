@@ -359,6 +359,43 @@ int apds_db_view(void* db, void** rows64_dev, void** kps_dev, void** row_ids_dev
 int apds_db_view_download(void* db, apds_keypoint* kps, uint8_t* desc61, int32_t* ids, int32_t* image_ids);
 /* knnMatch (any k >= 1 that apds_dev_hamming_topk serves) of host query descriptors against the current view; idx = position in the view (= trainIdx of the Vec the reference would hold) */
 int apds_db_knn_match(void* db, const uint8_t* query_desc, int n_query, int desc_bytes, int k, int32_t* idx, int32_t* dist);
+/* apds_db_insert_image for rows that are already on the device: kps_dev (28-byte keypoints) and desc64_dev (64-byte descriptor rows) are
+ * exactly what apds_dev_akaze_extract writes, n of them; no upload, no repack. The stored rows are apds_db_insert_image's bit for bit:
+ * x = k.x * 2^lod + (float)(column * tile_w * 2^lod) (the u64 product first), the same for y, the other fields copied, bytes 61-63 of
+ * every stored descriptor row zero whatever the source row holds there. `stream` (NULL: the thread's own) must be the stream the
+ * extraction was issued on, or be ordered after it: the extraction returns with its descriptor kernels still queued. Returns when the rows
+ * are in the table (one synchronise). A full table is APDS_ERR_NOMEM with the table unchanged. Inserting - through any of the insert
+ * calls - is single-threaded per table: no two threads may insert into, or insert into and read, one table at the same time. */
+int apds_db_insert_dev(void* db, const void* kps_dev, const void* desc64_dev, int n, int image_id, int level_of_detail, uint64_t column, uint64_t row,
+                       uint64_t tile_w, uint64_t tile_h, void* stream);
+/* The batch form, on what apds_dev_akaze_extract_batch writes: tile i (0 <= i < n_tiles <= 4096) has counts[i] rows at i * capacity rows,
+ * gets image_id = first_image_id + i and the tile position columns_rows = {column0, row0, column1, row1, ...}; its rows follow those of
+ * the tiles before it, so the table is the one n_tiles consecutive apds_db_insert_image calls make. counts and columns_rows are host
+ * arrays. One kernel launch for the whole batch. Everything is checked before anything is written: rows that do not all fit are
+ * APDS_ERR_NOMEM, a negative count or one above capacity APDS_ERR_BAD_ARG, and the table is unchanged in both cases. */
+int apds_db_insert_batch_dev(void* db, const void* kps_dev, const void* desc64_dev, int n_tiles, int capacity, const int32_t* counts, int first_image_id,
+                             int level_of_detail, const uint32_t* columns_rows, uint64_t tile_w, uint64_t tile_h, void* stream);
+/* The DB build of a group of tiles in ONE call (preprocessor/src/main.rs:197-327): apds_mosaic_tile_extract_batch_ex up to the
+ * extraction (same arguments, checks and status codes), then apds_db_insert_batch_dev on the same stream with tile_w = out_w and
+ * tile_h = out_h. No keypoint and no descriptor crosses PCIe: only counts[n_tiles] reaches the host. The mosaic and the table must live on
+ * the same device (else APDS_ERR_BAD_ARG). The table is bit-equal to the batch extraction followed by n_tiles apds_db_insert_image calls. */
+int apds_mosaic_tiles_to_db(void* mosaic, void* db, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample,
+                            const double* minmax6, int max_points, int mask_mode, int first_image_id, int level_of_detail, const uint32_t* columns_rows,
+                            int* counts);
+/* apds_get_world_coordinates for every row currently in the table, where the rows live: the point ((double)x, (double)y) of row i goes
+ * through the same arithmetic into row i of a table-owned column xyz (capacity x 3 doubles, allocated on first use). elevation: eh x ew
+ * doubles, on the host or (elevation_on_device != 0) on the device; elevation_gt NULL = height 0; a singular elevation_gt is
+ * APDS_ERR_BAD_ARG. A row whose lookup misses the raster gets three NaNs and the call still returns APDS_OK: *n_missing (may be NULL) is
+ * the exact number of such rows. */
+int apds_db_world_coordinates(void* db, const double* dataset_gt, const double* elevation_gt, const void* elevation, int ew, int eh,
+                              int elevation_on_device, int64_t* n_missing);
+/* The WHOLE table in the layout the pipeline takes (no selection, no 262143-row limit, insertion order): *rows64_dev = the table's own
+ * descriptor column (not a copy), *kps_dev = a table-owned buffer of 28-byte keypoints with the lifted coordinates, indexed by row
+ * (gathered by one kernel, and only for rows added since the last call), *xyz_dev = the column of apds_db_world_coordinates, or NULL if
+ * it was never computed or rows were added since it was; *n = rows. Any output may be NULL. The pointers hold until the next insert or
+ * apds_db_destroy. They are the arguments of apds_pipeline_create(.., rows64, n, 0, NULL, kps, n, ..) and apds_pipeline_pose_params'
+ * db_xyz_dev; a match's trainIdx is then the table row, i.e. the id - 1 that apds_db_view_download reports. */
+int apds_db_table(void* db, void** rows64_dev, void** kps_dev, void** xyz_dev, int64_t* n);
 
 /* ---- multi-GPU: the descriptor DB row-sharded over the GPUs of one node (BASELINE config 5) -------------------------------
  * No counterpart upstream: the reference matches on one CPU (feature_extraction/src/lib.rs:94-126) against whatever train set

@@ -17,6 +17,14 @@ also the build of the pyramid (host seconds and the kernels' own time on fresh h
 plus 12 per destination pixel written, summed over the steps); last line: one JSON object with everything.
 
     python tools/mosaic_probe.py --size 8192 --reps 2 [--overviews]
+
+With --db-build N it does one other thing instead: the whole table of the mosaic (--levels levels, --batch tiles per call, nearest) is
+built through the two-step path (batch extraction to the host, one apds_db_insert_image per tile) and through the device path
+(apds_mosaic_tiles_to_db per group), alternating in one process: one warm-up of each, then N timed builds of each (host clock around calls
+that end in a device synchronise). Prints every time, the medians and the spread (max - min) of each path, and checks that both paths
+store the same number of rows per image.
+
+    python tools/mosaic_probe.py --size 4096 --levels 3 --batch 16 --db-build 5
 """
 import argparse
 import json
@@ -42,17 +50,53 @@ def synthetic_mosaic(pkg, size):
     return bands
 
 
+def db_build(pkg, args):
+    """the same table through both paths, alternating: seconds per whole build"""
+    ge, pp, fd = pkg.geotiff_extractor, pkg.preprocessor, pkg.feature_database
+    dev = ge.DeviceMosaic(synthetic_mosaic(pkg, args.size))
+    dev.datasets_min_max()
+    times, rows = {"host insert": [], "device insert": []}, {}
+    for rep in range(args.db_build + 1):                                      # rep 0 warms every shape up and is not reported
+        for name, device_insert in (("host insert", False), ("device insert", True)):
+            table, images = fd.KeypointTable(6_000_000), pp.ImageTable()
+            s = time.perf_counter()
+            out = pp.process_lod_from_mosaic(table, images, dev, args.levels, batch=args.batch, device_insert=device_insert)
+            e = time.perf_counter()
+            assert len(table) == sum(n for level in out for _, n in level)
+            rows.setdefault(name, out)
+            assert rows[name] == out and rows["host insert"] == out, "the two paths store different rows per image"
+            if rep:
+                times[name].append(e - s)
+            table.close()
+    tiles = sum(len(level) for level in rows["host insert"])
+    total = sum(n for level in rows["host insert"] for _, n in level)
+    tile, _, _ = pp.tile_grid(dev.raster_size(), args.levels, 0)
+    print(f"DB build of a {args.size} x {args.size} mosaic: {args.levels} levels, {tiles} tiles of {tile[0]} x {tile[1]}, batch {args.batch}, {total} rows; "
+          f"{args.db_build} timed builds of each path after one warm-up, alternating")
+    summary = {}
+    for name, t in times.items():
+        summary[name] = dict(seconds=t, median=float(np.median(t)), spread=float(max(t) - min(t)))
+        print(f"{name:14s}: median {summary[name]['median']:.4f} s, spread (max - min) {summary[name]['spread']:.4f} s  [{' '.join('%.4f' % x for x in t)}]")
+    print(json.dumps(dict(size=args.size, levels=args.levels, batch=args.batch, tiles=tiles, tile=tile[0], rows=total, db_build=summary)))
+    dev.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=8192)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--levels", type=int, default=3)
     ap.add_argument("--overviews", action="store_true", help="also build the overview pyramid and read the levels of detail from it (way d)")
+    ap.add_argument("--db-build", type=int, default=0, metavar="N", help="instead: build the whole table N times through the two-step path and "
+                    "N times through the device path (apds_mosaic_tiles_to_db), alternating, and print both times")
+    ap.add_argument("--batch", type=int, default=16, help="tiles per library call of --db-build")
     args = ap.parse_args()
     import torch  # noqa: F401  (its HIP runtime first, as bench.py does)
     pkg = graft.load_package()
     L = pkg.lib()
     assert L.apds_device_count() > 0, "no HIP device: this probe measures on the GPU"
+    if args.db_build > 0:
+        return db_build(pkg, args)
     ge, pp, fd = pkg.geotiff_extractor, pkg.preprocessor, pkg.feature_database
     t0 = time.perf_counter()
     bands = synthetic_mosaic(pkg, args.size)
