@@ -42,6 +42,7 @@ SYMBOLS = [
     "apds_akaze_extract_masked_support", "apds_akaze_extract_batch_masked_support", "apds_dev_akaze_extract_masked_support",
     "apds_dev_akaze_extract_batch_masked_support", "apds_dev_mask_zero_sat",
     "apds_db_insert_dev", "apds_db_insert_batch_dev", "apds_mosaic_tiles_to_db", "apds_db_world_coordinates", "apds_db_table",
+    "apds_db_view_create", "apds_db_view_destroy", "apds_db_view_select", "apds_db_view_pointers", "apds_pipeline_create_table", "apds_pipeline_submit_select",
 ]
 
 RESAMPLE_NEAREST, RESAMPLE_LANCZOS = 0, 1
@@ -119,6 +120,11 @@ class FramePose(C.Structure):
     """apds_frame_pose"""
     _fields_ = [("frame", C.c_int64), ("status", C.c_int), ("found", C.c_int), ("n_correspondences", C.c_int), ("n_inliers", C.c_int),
                 ("rvec", C.c_double * 3), ("tvec", C.c_double * 3)]
+
+
+class DbSelection(C.Structure):
+    """apds_db_selection: one frame's train-set selection on a table pipeline (apds_db_select's mode, value and bounding box)"""
+    _fields_ = [("mode", C.c_int), ("value", C.c_int), ("x_start", C.c_float), ("y_start", C.c_float), ("x_end", C.c_float), ("y_end", C.c_float)]
 
 
 PIPELINE_NOT_READY = 1
@@ -281,6 +287,12 @@ def lib():
             "apds_mosaic_tiles_to_db": (i, [vp, vp, vp, i, i, i, i, i, i, vp, i, i, i, i, vp, ip]),
             "apds_db_world_coordinates": (i, [vp, vp, vp, vp, i, i, i, C.POINTER(i64)]),
             "apds_db_table": (i, [vp, pp, pp, pp, C.POINTER(i64)]),
+            "apds_db_view_create": (i, [vp, i, pp]),
+            "apds_db_view_destroy": (i, [vp]),
+            "apds_db_view_select": (i, [vp, i, i, f, f, f, f, i, vp, ip]),
+            "apds_db_view_pointers": (i, [vp, pp, pp, pp, pp, pp, ip]),
+            "apds_pipeline_create_table": (i, [pp, vp, i, C.POINTER(PipelineParams)]),
+            "apds_pipeline_submit_select": (i, [vp, vp, sz, i, C.POINTER(DbSelection), C.POINTER(i64)]),
         }
         for name, (rt, at) in sig.items():
             fn = getattr(L, name)

@@ -230,6 +230,245 @@ __global__ void table_gather_kernel(const uint64_t* __restrict__ keys, int m, co
     }
 }
 
+// ---- the view path (apds_db_view_select): the same selection, stream-ordered, on buffers a view object owns ---------------------------
+// One host synchronisation per call (the count of qualifying rows, right after the flag scan: every later grid is sized by it); the
+// radix select keeps its prefix and remaining rank in device memory; the sort does every stride below SORT_B in LDS.
+static constexpr int SORT_B = 2048;             // keys one workgroup sorts / merges in LDS: 16 KB of u64, two per thread of 1024
+static constexpr uint64_t PAD_KEY = ~0ull;      // strictly above every real key (order_key: the row is below 2^31)
+
+struct ViewSelectState {
+    unsigned int hist[256];
+    unsigned long long prefix, mask_hi;   // the bytes of the limit-th key decided so far, and the mask that covers them
+    unsigned int rank, pad;               // rank of that key among the keys that share the prefix
+};
+
+__device__ __forceinline__ bool view_row_selected(const TableColumns& c, long long i, const SelectArgs& a) {
+    if (a.mode == 0) return c.image_id[i] == a.value;
+    if (c.lod[i] != a.value) return false;
+    if (a.mode == 1) return true;
+    const float x = c.x[i], y = c.y[i];
+    return x >= a.x0 && x <= a.x1 && y >= a.y0 && y <= a.y1;
+}
+
+// position of a flagged thread among the flagged threads of its block (TB threads), and the block's count
+__device__ __forceinline__ int view_block_rank(int f, int* block_total) {
+    __shared__ int wsum[TB / 64];
+    const unsigned long long b = __ballot(f);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) wsum[wv] = __popcll(b);
+    __syncthreads();
+    int before = 0, all = 0;
+    for (int k = 0; k < TB / 64; k++) {
+        if (k < wv) before += wsum[k];
+        all += wsum[k];
+    }
+    *block_total = all;
+    return before + __popcll(b & ((1ull << lane) - 1ull));
+}
+
+__global__ __launch_bounds__(TB) void view_count_rows_kernel(TableColumns c, int n, SelectArgs a, int* __restrict__ block_counts) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const int i = blockIdx.x * TB + threadIdx.x;
+    int total;
+    (void)view_block_rank(i < n && view_row_selected(c, i, a), &total);
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
+}
+
+// one block: block_counts[0 .. nblocks) -> exclusive offsets in place, the sum to block_counts[nblocks]
+__global__ __launch_bounds__(1024) void view_offsets_kernel(int* __restrict__ block_counts, int nblocks) {
+    APDS_RAISE_WAVE_PRIORITY();
+    __shared__ int wtot[16];
+    __shared__ int carry;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (int base = 0; base < nblocks; base += 1024) {
+        const int i = base + threadIdx.x;
+        const int v = i < nblocks ? block_counts[i] : 0;
+        int incl = v;
+        for (int off = 1; off < 64; off <<= 1) {
+            const int up = __shfl_up(incl, off);
+            if (lane >= off) incl += up;
+        }
+        if (lane == 63) wtot[wv] = incl;
+        __syncthreads();
+        int before = carry;
+        for (int k = 0; k < wv; k++) before += wtot[k];
+        if (i < nblocks) block_counts[i] = before + incl - v;
+        __syncthreads();
+        if (threadIdx.x == 1023) carry = before + incl;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) block_counts[nblocks] = carry;
+}
+
+__global__ __launch_bounds__(TB) void view_emit_keys_kernel(TableColumns c, int n, SelectArgs a, const int* __restrict__ block_offsets,
+                                                            uint64_t* __restrict__ keys) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const int i = blockIdx.x * TB + threadIdx.x;
+    const int f = i < n && view_row_selected(c, i, a);
+    int total;
+    const int pos = view_block_rank(f, &total);
+    if (f) keys[block_offsets[blockIdx.x] + pos] = order_key(c.response[i], (uint32_t)i);
+}
+
+__global__ __launch_bounds__(256) void view_radix_init_kernel(ViewSelectState* __restrict__ st, unsigned int rank) {
+    st->hist[threadIdx.x] = 0;
+    if (threadIdx.x == 0) st->prefix = 0, st->mask_hi = 0, st->rank = rank, st->pad = 0;
+}
+
+// key_hist_kernel with the prefix read from the state the decide kernel keeps
+__global__ __launch_bounds__(256) void view_radix_hist_kernel(const uint64_t* __restrict__ keys, int m, int shift, ViewSelectState* __restrict__ st) {
+    APDS_RAISE_WAVE_PRIORITY();
+    __shared__ unsigned int s[256];
+    s[threadIdx.x] = 0;
+    const uint64_t prefix = st->prefix, mask_hi = st->mask_hi;
+    __syncthreads();
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) {
+        const uint64_t k = keys[i];
+        if ((k & mask_hi) == prefix) atomicAdd(&s[(k >> shift) & 0xFF], 1u);
+    }
+    __syncthreads();
+    if (s[threadIdx.x]) atomicAdd(&st->hist[threadIdx.x], s[threadIdx.x]);
+}
+
+// one block of 256: the bucket of this byte that holds the wanted rank -> prefix, mask and remaining rank; the histogram is cleared for
+// the next byte. More keys than the rank share the prefix (the host takes this path only when more rows qualify than the limit), so
+// exactly one bucket holds it.
+__global__ __launch_bounds__(256) void view_radix_decide_kernel(ViewSelectState* __restrict__ st, int shift) {
+    __shared__ unsigned int s[256];
+    const unsigned int t = threadIdx.x;
+    const unsigned int h = st->hist[t], rank = st->rank;
+    s[t] = h;
+    __syncthreads();
+    for (unsigned int off = 1; off < 256; off <<= 1) {
+        const unsigned int add = t >= off ? s[t - off] : 0;
+        __syncthreads();
+        s[t] += add;
+        __syncthreads();
+    }
+    const unsigned int excl = s[t] - h;
+    st->hist[t] = 0;
+    if (rank >= excl && rank - excl < h) {
+        st->prefix |= (unsigned long long)t << shift;
+        st->mask_hi |= 0xFFull << shift;
+        st->rank = rank - excl;
+    }
+}
+
+// after the last byte st->prefix is the limit-th key: the keys not above it, counted per block and then compacted in order
+__global__ __launch_bounds__(TB) void view_cut_count_kernel(const uint64_t* __restrict__ keys, int m, const ViewSelectState* __restrict__ st,
+                                                            int* __restrict__ block_counts) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const int i = blockIdx.x * TB + threadIdx.x;
+    int total;
+    (void)view_block_rank(i < m && keys[i] <= st->prefix, &total);
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(TB) void view_cut_compact_kernel(const uint64_t* __restrict__ keys, int m, const ViewSelectState* __restrict__ st,
+                                                              const int* __restrict__ block_offsets, int limit, uint64_t* __restrict__ out) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const int i = blockIdx.x * TB + threadIdx.x;
+    const uint64_t k = i < m ? keys[i] : PAD_KEY;
+    const int f = i < m && k <= st->prefix;
+    int total;
+    const int pos = block_offsets[blockIdx.x] + view_block_rank(f, &total);
+    if (f && pos < limit) out[pos] = k;   // (keys are distinct, so exactly `limit` are kept; the bound guards the buffer all the same)
+}
+
+// Steps j_from, j_from / 2, .., 1 of merge stage k on the SORT_B keys of this block in LDS; s[i] is key base + i of the whole array.
+// Thread t owns the pair (i, i | j) whose lower index has bit j clear. Strides of 32 keys and more are conflict-free ds_read_b64; below
+// that the two halves of a pair interleave and the reads go 2-way.
+__device__ __forceinline__ void lds_bitonic_steps(uint64_t* s, unsigned int base, unsigned int k, unsigned int j_from) {
+    const unsigned int t = threadIdx.x;
+    for (unsigned int j = j_from; j > 0; j >>= 1) {
+        const unsigned int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+        const uint64_t a = s[i], b = s[l];
+        const bool up = ((base + i) & k) == 0;
+        if ((a > b) == up) {
+            s[i] = b;
+            s[l] = a;
+        }
+        __syncthreads();
+    }
+}
+
+// blocks of SORT_B keys sorted in one launch (ascending / descending by the block's place in the bitonic network); keys past m read as
+// padding. src may be dst.
+__global__ __launch_bounds__(SORT_B / 2) void view_block_sort_kernel(const uint64_t* src, int m, uint64_t* dst) {
+    APDS_RAISE_WAVE_PRIORITY();
+    __shared__ uint64_t s[SORT_B];
+    const unsigned int base = blockIdx.x * SORT_B;
+    for (unsigned int e = threadIdx.x; e < SORT_B; e += SORT_B / 2) s[e] = base + e < (unsigned int)m ? src[base + e] : PAD_KEY;
+    __syncthreads();
+    for (unsigned int k = 2; k <= SORT_B; k <<= 1) lds_bitonic_steps(s, base, k, k >> 1);
+    for (unsigned int e = threadIdx.x; e < SORT_B; e += SORT_B / 2) dst[base + e] = s[e];
+}
+
+// every step of merge stage k (> SORT_B) whose stride is below SORT_B, in one launch
+__global__ __launch_bounds__(SORT_B / 2) void view_merge_tail_kernel(uint64_t* __restrict__ keys, unsigned int k) {
+    APDS_RAISE_WAVE_PRIORITY();
+    __shared__ uint64_t s[SORT_B];
+    const unsigned int base = blockIdx.x * SORT_B;
+    for (unsigned int e = threadIdx.x; e < SORT_B; e += SORT_B / 2) s[e] = keys[base + e];
+    __syncthreads();
+    lds_bitonic_steps(s, base, k, SORT_B / 2);
+    for (unsigned int e = threadIdx.x; e < SORT_B; e += SORT_B / 2) keys[base + e] = s[e];
+}
+
+// one step of stride j >= SORT_B: a thread per pair
+__global__ __launch_bounds__(256) void view_merge_step_kernel(uint64_t* __restrict__ keys, unsigned int pairs, unsigned int k, unsigned int j) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const unsigned int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= pairs) return;
+    const unsigned int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+    const uint64_t a = keys[i], b = keys[l];
+    if ((a > b) == ((i & k) == 0)) {
+        keys[i] = b;
+        keys[l] = a;
+    }
+}
+
+// everything a view holds, in one launch: 16 lanes per row, one descriptor dword each (as table_gather_kernel); lane 0 also writes the
+// keypoint, row id and image id, lanes 1..3 one coordinate of the world point each when xyz is asked for
+__global__ __launch_bounds__(256) void view_gather_kernel(const uint64_t* __restrict__ keys, int m, TableColumns c, const double* __restrict__ xyz,
+                                                          int* __restrict__ rows, apds_keypoint* __restrict__ kps, int* __restrict__ out_img,
+                                                          uint32_t* __restrict__ out_desc, double* __restrict__ out_xyz) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long long)m * 16) return;
+    const int i = (int)(t >> 4), w = (int)(t & 15);
+    const uint32_t r = (uint32_t)keys[i];
+    out_desc[(size_t)i * 16 + w] = c.desc64[(size_t)r * 16 + w];
+    if (w == 0) {
+        rows[i] = (int)r;
+        apds_keypoint k;
+        k.x = c.x[r]; k.y = c.y[r]; k.size = c.size[r]; k.angle = c.angle[r]; k.response = c.response[r];
+        k.octave = c.octave[r]; k.class_id = c.class_id[r];
+        kps[i] = k;
+        out_img[i] = c.image_id[r];
+    } else if (w <= 3 && xyz) {
+        out_xyz[(size_t)i * 3 + (w - 1)] = xyz[(size_t)r * 3 + (w - 1)];
+    }
+}
+
+// A view of one table: the outputs of a selection and all the scratch it takes, allocated once (apds_db_view_create).
+struct TableView {
+    KeypointTable* t = nullptr;
+    int limit = 0, n = 0;
+    int64_t sort_cap = 0;   // keys the sort buffer holds: the power of two that holds `limit`, at least SORT_B
+    bool has_xyz = false;
+    int *block_counts = nullptr, *cut_counts = nullptr;   // table capacity / TB + 1 each
+    uint64_t *keys = nullptr, *sorted = nullptr;          // table capacity; sort_cap
+    ViewSelectState* state = nullptr;
+    int* host_count = nullptr;                            // pinned
+    int *rows = nullptr, *image_id = nullptr;
+    apds_keypoint* kps = nullptr;
+    uint8_t* desc64 = nullptr;
+    double* xyz = nullptr;
+};
+
 }  // namespace apds
 
 using namespace apds;
@@ -245,6 +484,13 @@ void table_free(KeypointTable* t) {
                     (void*)t->view_desc64, (void*)t->all_kps, (void*)t->xyz})
         if (p) (void)hipFree(p);
     delete t;
+}
+void view_free(TableView* v) {
+    for (void* p : {(void*)v->block_counts, (void*)v->cut_counts, (void*)v->keys, (void*)v->sorted, (void*)v->state, (void*)v->rows, (void*)v->image_id,
+                    (void*)v->kps, (void*)v->desc64, (void*)v->xyz})
+        if (p) (void)hipFree(p);
+    if (v->host_count) (void)hipHostFree(v->host_count);
+    delete v;
 }
 TableColumns columns_of(KeypointTable* t) {
     return TableColumns{t->x, t->y, t->size, t->angle, t->response, t->octave, t->class_id, t->image_id, t->lod, reinterpret_cast<uint32_t*>(t->desc64)};
@@ -575,6 +821,114 @@ int apds_db_view_download(void* db, apds_keypoint* kps, uint8_t* desc61, int32_t
         HIP_CHECK(hipStreamSynchronize(s));
         if (ids)
             for (int i = 0; i < m; i++) ids[i] = rows[i] + 1;
+    });
+}
+
+// ---- view objects: keypointdb.rs:50-90 once per frame, on the caller's stream ------------------------------------------------------
+int apds_db_view_create(void* db, int capacity, void** view) {
+    return guarded([&] {
+        KeypointTable* t = static_cast<KeypointTable*>(db);
+        APDS_REQUIRE(t && view, APDS_ERR_BAD_ARG, "null argument");
+        *view = nullptr;
+        APDS_REQUIRE(t->device == ctx().device, APDS_ERR_BAD_ARG, "the table lives on another device than the calling thread's");
+        TableView* v = new TableView();
+        v->t = t;
+        v->limit = (int)(capacity <= 0 ? std::min<int64_t>(APDS_MAX_POINTS, t->capacity) : std::min<int64_t>(capacity, APDS_MAX_POINTS));
+        v->sort_cap = SORT_B;
+        while (v->sort_cap < v->limit) v->sort_cap <<= 1;
+        const size_t nblocks = (size_t)ceil_div(t->capacity, TB) + 1, lim = (size_t)v->limit;
+        try {
+            dev_alloc(v->block_counts, nblocks); dev_alloc(v->cut_counts, nblocks);
+            dev_alloc(v->keys, (size_t)t->capacity); dev_alloc(v->sorted, (size_t)v->sort_cap);
+            dev_alloc(v->state, 1);
+            dev_alloc(v->rows, lim); dev_alloc(v->image_id, lim); dev_alloc(v->kps, lim); dev_alloc(v->desc64, lim * 64); dev_alloc(v->xyz, lim * 3);
+            HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&v->host_count), sizeof(int), hipHostMallocDefault));
+        } catch (...) {
+            view_free(v);
+            throw;
+        }
+        *view = v;
+    });
+}
+
+int apds_db_view_destroy(void* view) {
+    return guarded([&] {
+        if (view) view_free(static_cast<TableView*>(view));
+    });
+}
+
+// apds_db_select's rows into the view, everything on `stream` (NULL: the calling thread's). The one host synchronisation is the count
+// of qualifying rows; the kernels that cut, sort and gather are queued behind it and the call returns: *n_out is final, the view's
+// buffers are complete once the stream has run (any later work on the same stream sees them).
+int apds_db_view_select(void* view, int mode, int value, float x_start, float y_start, float x_end, float y_end, int with_xyz, void* stream, int* n_out) {
+    return guarded([&] {
+        TableView* v = static_cast<TableView*>(view);
+        APDS_REQUIRE(v && n_out && mode >= 0 && mode <= 2, APDS_ERR_BAD_ARG, "bad argument");
+        KeypointTable* t = v->t;
+        *n_out = 0;
+        APDS_REQUIRE(!with_xyz || (t->xyz && t->xyz_rows == t->n), APDS_ERR_BAD_ARG,
+                     "the table's world points are absent or older than its rows (apds_db_world_coordinates)");
+        APDS_REQUIRE(t->device == ctx().device, APDS_ERR_BAD_ARG, "the table lives on another device than the calling thread's");
+        hipStream_t s = pick_stream(stream);
+        v->n = 0;
+        v->has_xyz = false;
+        const int n = (int)t->n;
+        if (!n) return;
+        const SelectArgs a{mode, value, floorf(x_start), floorf(y_start), ceilf(x_end), ceilf(y_end)};
+        const TableColumns c = columns_of(t);
+        const int nb = ceil_div(n, TB);
+        hipLaunchKernelGGL(view_count_rows_kernel, dim3(nb), dim3(TB), 0, s, c, n, a, v->block_counts);
+        hipLaunchKernelGGL(view_offsets_kernel, dim3(1), dim3(1024), 0, s, v->block_counts, nb);
+        HIP_CHECK(hipMemcpyAsync(v->host_count, v->block_counts + nb, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        int m = *v->host_count;
+        if (!m) return;
+        hipLaunchKernelGGL(view_emit_keys_kernel, dim3(nb), dim3(TB), 0, s, c, n, a, (const int*)v->block_counts, v->keys);
+        const uint64_t* unsorted = v->keys;
+        if (m > v->limit) {
+            // radix select of the limit-th smallest key, most significant byte first; each byte's bucket is decided on the device
+            hipLaunchKernelGGL(view_radix_init_kernel, dim3(1), dim3(256), 0, s, v->state, (unsigned int)(v->limit - 1));
+            for (int shift = 56; shift >= 0; shift -= 8) {
+                hipLaunchKernelGGL(view_radix_hist_kernel, dim3(256), dim3(256), 0, s, (const uint64_t*)v->keys, m, shift, v->state);
+                hipLaunchKernelGGL(view_radix_decide_kernel, dim3(1), dim3(256), 0, s, v->state, shift);
+            }
+            const int mb = ceil_div(m, TB);
+            hipLaunchKernelGGL(view_cut_count_kernel, dim3(mb), dim3(TB), 0, s, (const uint64_t*)v->keys, m, (const ViewSelectState*)v->state, v->cut_counts);
+            hipLaunchKernelGGL(view_offsets_kernel, dim3(1), dim3(1024), 0, s, v->cut_counts, mb);
+            hipLaunchKernelGGL(view_cut_compact_kernel, dim3(mb), dim3(TB), 0, s, (const uint64_t*)v->keys, m, (const ViewSelectState*)v->state,
+                               (const int*)v->cut_counts, v->limit, v->sorted);
+            unsorted = v->sorted;
+            m = v->limit;
+        }
+        // bitonic sort of the m surviving keys, padded to p2 (a power of two, at least one block) with keys above every real one
+        unsigned int p2 = SORT_B;
+        while (p2 < (unsigned int)m) p2 <<= 1;
+        hipLaunchKernelGGL(view_block_sort_kernel, dim3(p2 / SORT_B), dim3(SORT_B / 2), 0, s, unsorted, m, v->sorted);
+        for (unsigned int k = 2 * SORT_B; k <= p2; k <<= 1) {
+            for (unsigned int j = k >> 1; j >= (unsigned int)SORT_B; j >>= 1)
+                hipLaunchKernelGGL(view_merge_step_kernel, dim3(p2 / 2 / 256), dim3(256), 0, s, v->sorted, p2 / 2, k, j);
+            hipLaunchKernelGGL(view_merge_tail_kernel, dim3(p2 / SORT_B), dim3(SORT_B / 2), 0, s, v->sorted, k);
+        }
+        hipLaunchKernelGGL(view_gather_kernel, dim3(ceil_div((long long)m * 16, 256)), dim3(256), 0, s, (const uint64_t*)v->sorted, m, c,
+                           (const double*)(with_xyz ? t->xyz : nullptr), v->rows, v->kps, v->image_id, reinterpret_cast<uint32_t*>(v->desc64), v->xyz);
+        HIP_CHECK(hipGetLastError());
+        v->n = m;
+        v->has_xyz = with_xyz != 0;
+        *n_out = m;
+    });
+}
+
+// device pointers of the view's last selection (*xyz_dev: NULL unless it ran with_xyz)
+int apds_db_view_pointers(const void* view, void** rows64_dev, void** kps_dev, void** row_ids_dev, void** image_ids_dev, void** xyz_dev, int* n) {
+    return guarded([&] {
+        const TableView* v = static_cast<const TableView*>(view);
+        APDS_REQUIRE(v, APDS_ERR_BAD_ARG, "null view");
+        if (rows64_dev) *rows64_dev = v->desc64;
+        if (kps_dev) *kps_dev = v->kps;
+        if (row_ids_dev) *row_ids_dev = v->rows;
+        if (image_ids_dev) *image_ids_dev = v->image_id;
+        if (xyz_dev) *xyz_dev = v->has_xyz ? v->xyz : nullptr;
+        if (n) *n = v->n;
     });
 }
 

@@ -11,6 +11,9 @@
 //   homography worker (1)    frame i-1: ratio filter, point gather, RANSAC (its host round trips hide behind the other two stages)
 //   pose worker (opt-in, 1)  frame i-2: world-point gather, PnP RANSAC (apds_pipeline_enable_pose; overlaps the next frame's homography)
 //
+// A table pipeline (apds_pipeline_create_table) selects each frame's train set from a keypoint table first (keypointdb.rs:50-90): the match
+// worker runs the slot's view select on the match stream in front of the scan, and the later stages read the view by position.
+//
 // Every worker owns a HIP stream and a device workspace (the per-thread context every entry point uses), stages hand frames over
 // through HIP events, results leave in frame order. The reference only chains these steps inside unit tests
 // (feature_extraction/src/lib.rs:197-249) and never calls find_homography_mat on the result; this is the composed path the
@@ -90,6 +93,14 @@ struct Slot {
     hipEvent_t ev_mstart = nullptr, ev_mend = nullptr;   // (timing enabled) the match stream's idle gaps: starvation watch
     void* topk_state = nullptr;   // split scan (one GPU)
     void* shard_slot = nullptr;   // exchange slot (sharded DB)
+    // a table pipeline (apds_pipeline_create_table): this slot's view of the table, the frame's selection and what it gave. The later
+    // stages read the train side from here (the view's pointers never change; its contents hold until the slot's next frame).
+    void* view = nullptr;
+    apds_db_selection sel{};
+    const void* view_rows64 = nullptr;
+    const apds_keypoint* view_kps = nullptr;
+    const void* view_xyz = nullptr;
+    int n_view = 0;
     int owner = 0;
     // the job
     const void* src = nullptr;
@@ -117,6 +128,7 @@ struct Pipeline {
     int world = 1;
     const apds_keypoint* db_kps = nullptr;
     int64_t n_db_total = 0;
+    void* table = nullptr;   // the train set is selected per frame from this keypoint table (borrowed)
     int cap = 0, E = 2;
     bool split = true, adaptive_cap = true, own_match_stream = true;
     double extract_delay_s = 0;
@@ -289,7 +301,28 @@ struct Pipeline {
             Slot* s = nullptr;
             if (!q_ext[(size_t)e]->pop(s)) break;
             const int K = s->K;
-            if (K > 0 && split) {
+            if (table) {
+                // the frame's train set first: the select needs nothing from the extraction. Its one synchronisation waits for the previous
+                // frame's scan on this stream; the cut, sort and gather it queues run in front of this frame's scan.
+                s->n_view = 0;
+                PIPE_OK(apds_db_view_select(s->view, s->sel.mode, s->sel.value, s->sel.x_start, s->sel.y_start, s->sel.x_end, s->sel.y_end, pose_on ? 1 : 0,
+                                            st_match, &s->n_view));
+                void* xyz = nullptr;
+                PIPE_OK(apds_db_view_pointers(s->view, nullptr, nullptr, nullptr, nullptr, &xyz, nullptr));
+                s->view_xyz = xyz;
+                HIP_CHECK(hipStreamWaitEvent(st_match, s->ev_extract, 0));
+                HIP_CHECK(hipEventRecord(s->ev_mstart, st_match));
+                if (s->n_view < 2) {   // what a train set of that size is to apds_pipeline_create
+                    if (s->status == APDS_OK) {
+                        s->status = APDS_ERR_ASSERT;
+                        s->error = "the frame's selection has fewer than two rows: a train set of at least two rows is required";
+                    }
+                } else if (K > 0) {
+                    PIPE_OK(apds_dev_hamming_topk(s->desc, K, s->view_rows64, s->n_view, 0, 2, s->keys, st_match));
+                }
+                HIP_CHECK(hipEventRecord(s->ev_match, st_match));
+                HIP_CHECK(hipEventRecord(s->ev_mend, st_match));
+            } else if (K > 0 && split) {
                 HIP_CHECK(hipStreamWaitEvent(st_pre, s->ev_extract, 0));   // threshold pre-pass: beside the previous frame's main scan
                 PIPE_OK(apds_dev_topk_prepass(s->topk_state, s->desc, K, db_rows, n_rows, index_base, 2, st_pre));
                 HIP_CHECK(hipEventRecord(s->ev_pre, st_pre));
@@ -415,11 +448,14 @@ struct Pipeline {
             try {
                 HIP_CHECK(hipStreamWaitEvent(st, s->ev_match, 0));
                 int M = 0;
-                if (s->K > 0) PIPE_OK(apds_dev_ratio_filter(s->keys, s->K, 2, p.filter_strength, s->matches, &M, st));
+                const bool matched = s->K > 0 && !(table && s->n_view < 2);
+                const apds_keypoint* train_kps = table ? s->view_kps : db_kps;
+                const int n_train = table ? s->n_view : (int)n_db_total;
+                if (matched) PIPE_OK(apds_dev_ratio_filter(s->keys, s->K, 2, p.filter_strength, s->matches, &M, st));
                 r.n_matches = M;
                 if (M >= 4) {
                     // query_idx -> this frame's keypoints, train_idx -> the DB rows' keypoints (the intended gather: lib.rs:161-180 has two bugs)
-                    PIPE_OK(apds_dev_points_from_matches(s->kps, s->K, db_kps, (int)n_db_total, s->matches, M, 0, s->p1, s->p2, st));
+                    PIPE_OK(apds_dev_points_from_matches(s->kps, s->K, train_kps, n_train, s->matches, M, 0, s->p1, s->p2, st));
                     const int rc = apds_dev_find_homography(s->p1, s->p2, M, p.homography_method, p.reproj_threshold, p.max_iters, p.confidence, r.H, s->mask, st);
                     if (rc == APDS_OK) {
                         r.homography_found = 1;
@@ -462,7 +498,7 @@ struct Pipeline {
                 fp.n_correspondences = M;
                 try {
                     HIP_CHECK(hipStreamWaitEvent(st, s->ev_homography, 0));
-                    PIPE_OK(apds_dev_pnp_correspondences(s->kps, s->K, pose.db_xyz_dev, n_db_total, pose.origin, s->matches, M, s->pose_img, s->pose_obj, st));
+                    PIPE_OK(apds_dev_pnp_correspondences(s->kps, s->K, table ? s->view_xyz : pose.db_xyz_dev, table ? (int64_t)s->n_view : n_db_total, pose.origin, s->matches, M, s->pose_img, s->pose_obj, st));
                     // fewer than four pairs: the one-call entry's APDS_ERR_ASSERT, without device work
                     fp.status = apds_dev_pnp_solver_ransac(s->pose_obj, s->pose_img, M, pose.camera_intrinsic, pose.iter_count, pose.reproj_thres, pose.confidence,
                                                           pose.method, fp.rvec, fp.tvec, nullptr, &fp.n_inliers, &fp.found, st);
@@ -508,6 +544,7 @@ void destroy_pipeline(Pipeline* P) {
             if (ev) (void)hipEventDestroy(ev);
         if (s->topk_state) topk_split_destroy(s->topk_state);
         if (s->shard_slot && P->shard) (void)apds_shard_slot_destroy(P->shard, s->shard_slot);
+        if (s->view) (void)apds_db_view_destroy(s->view);
     }
     if (P->db_expanded) hm_train_destroy(P->db_expanded);
     P->db_expanded = nullptr;
@@ -529,19 +566,28 @@ Pipeline* pipe_handle(void* h) {
 
 extern "C" {
 
-int apds_pipeline_create(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint32_t index_base, void* shard, const void* db_kps_dev, int64_t n_db_total,
-                         const apds_pipeline_params* params) {
+}  // extern "C"
+
+namespace {
+
+// table != null: the train set is a per-frame view of that keypoint table (view_capacity rows at most); the rows arguments are unused
+int create_pipeline(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint32_t index_base, void* shard, const void* db_kps_dev, int64_t n_db_total,
+                    void* table, int view_capacity, const apds_pipeline_params* params) {
     return guarded([&] {
         APDS_REQUIRE(pipe && params, APDS_ERR_BAD_ARG, "null argument");
         *pipe = nullptr;
         const apds_pipeline_params& in = *params;
         APDS_REQUIRE(in.rows > 0 && in.cols > 0 && (in.channels == 1 || in.channels == 3 || in.channels == 4), APDS_ERR_ASSERT, "bad frame geometry");
-        APDS_REQUIRE(shard || (db_rows64_dev && n_rows >= 2), APDS_ERR_ASSERT, "a train set of at least two rows (or a shard handle) is required");
-        APDS_REQUIRE(db_kps_dev && n_db_total > 0 && n_db_total < (1ll << 31), APDS_ERR_ASSERT, "the train rows' keypoints are required (n_db_total x 28 bytes)");
+        if (!table) {
+            APDS_REQUIRE(shard || (db_rows64_dev && n_rows >= 2), APDS_ERR_ASSERT, "a train set of at least two rows (or a shard handle) is required");
+            APDS_REQUIRE(db_kps_dev && n_db_total > 0 && n_db_total < (1ll << 31), APDS_ERR_ASSERT, "the train rows' keypoints are required (n_db_total x 28 bytes)");
+        }
         ThreadCtx& c = ctx();
+        APDS_REQUIRE(!table || table_device(table) == c.device, APDS_ERR_BAD_ARG, "the table lives on another device than the calling thread's");
         std::unique_ptr<Pipeline, void (*)(Pipeline*)> P(new Pipeline(), destroy_pipeline);
         P->p = in;
         P->device = c.device;
+        P->table = table;
         P->db_rows = db_rows64_dev;
         P->n_rows = n_rows;
         P->index_base = index_base;
@@ -565,7 +611,8 @@ int apds_pipeline_create(void** pipe, const void* db_rows64_dev, int64_t n_rows,
         // three streams for the pre-pass, main scan and merge of consecutive frames: the vector-ALU matcher's pipeline (its pre-pass and record
         // merge are 0.8 ms of small kernels per frame). The matrix-core matcher has one main launch and two tiny ones: on one stream 131.6
         // frames/s, split over three 126.8 (profiles/r04/ab_bench_env.txt); APDS_MATCH_SPLIT=2 forces the split for it as well.
-        P->split = P->world == 1 && !shard && (cfg.match_mfma ? cfg.pipe_match_split == 2 : cfg.pipe_match_split != 0);
+        // (a table pipeline matches each frame against another view: one stream, the one-call matcher, no expanded copy of a resident train set)
+        P->split = P->world == 1 && !shard && !table && (cfg.match_mfma ? cfg.pipe_match_split == 2 : cfg.pipe_match_split != 0);
         // (the starvation watch caps hamming_topk_kernel's occupancy: the matrix-core matcher has no such knob and is not watched)
         P->adaptive_cap = cfg.pipe_adaptive_cap != 0 && P->split && in.match_lds_cap == 0 && !cfg.match_mfma;
         P->extract_delay_s = in.debug_extract_delay_ms > 0 ? in.debug_extract_delay_ms * 1e-3 : 0.0;
@@ -587,7 +634,7 @@ int apds_pipeline_create(void** pipe, const void* db_rows64_dev, int64_t n_rows,
             HIP_CHECK(hipStreamCreateWithPriority(&P->st_gather, hipStreamNonBlocking, hp));
             HIP_CHECK(hipStreamCreateWithPriority(&P->st_counts, hipStreamNonBlocking, hp));
         }
-        if (P->world == 1 && !shard && cfg.match_mfma) P->db_expanded = hm_train_create(P->db_rows, P->n_rows, P->st_match);
+        if (P->world == 1 && !shard && !table && cfg.match_mfma) P->db_expanded = hm_train_create(P->db_rows, P->n_rows, P->st_match);
         const size_t cap = (size_t)P->cap;
         for (int i = 0; i < n_slots; i++) {
             auto s = std::make_unique<Slot>();
@@ -610,6 +657,18 @@ int apds_pipeline_create(void** pipe, const void* db_rows64_dev, int64_t n_rows,
                 const int rc = apds_shard_slot_create(shard, P->cap, 2, &s->shard_slot);
                 if (rc != APDS_OK) fail(rc, apds_last_error());
             }
+            if (table) {
+                int rc = apds_db_view_create(table, view_capacity, &s->view);
+                void *rows64 = nullptr, *kps = nullptr;
+                if (rc == APDS_OK) rc = apds_db_view_pointers(s->view, &rows64, &kps, nullptr, nullptr, nullptr, nullptr);
+                if (rc != APDS_OK) {
+                    const std::string why = apds_last_error();
+                    P->slots.push_back(std::move(s));   // (destroy releases what this slot already holds)
+                    fail(rc, why);
+                }
+                s->view_rows64 = rows64;
+                s->view_kps = static_cast<const apds_keypoint*>(kps);
+            }
             P->slots.push_back(std::move(s));
         }
         for (int e = 0; e < P->E; e++) {
@@ -629,9 +688,13 @@ int apds_pipeline_create(void** pipe, const void* db_rows64_dev, int64_t n_rows,
     });
 }
 
-int apds_pipeline_submit(void* pipe, const void* frame, size_t stride_bytes, int on_device, int64_t* frame_id) {
+int submit_frame(void* pipe, const void* frame, size_t stride_bytes, int on_device, const apds_db_selection* sel, bool with_selection, int64_t* frame_id) {
     return guarded([&] {
         Pipeline* P = pipe_handle(pipe);
+        APDS_REQUIRE(with_selection == (P->table != nullptr), APDS_ERR_BAD_ARG,
+                     with_selection ? "this pipeline has a fixed train set: use apds_pipeline_submit"
+                                    : "this pipeline selects its train set per frame: use apds_pipeline_submit_select");
+        APDS_REQUIRE(!with_selection || (sel && sel->mode >= 0 && sel->mode <= 2), APDS_ERR_BAD_ARG, "a selection with mode 0, 1 or 2 is required");
         APDS_REQUIRE(frame, APDS_ERR_BAD_ARG, "null frame");
         APDS_REQUIRE(stride_bytes >= (size_t)P->p.cols * (size_t)P->p.channels, APDS_ERR_ASSERT, "row stride shorter than a row");
         std::lock_guard<std::mutex> one(P->submit_m);
@@ -651,6 +714,7 @@ int apds_pipeline_submit(void* pipe, const void* frame, size_t stride_bytes, int
         s->stride = stride_bytes;
         s->on_device = on_device != 0;
         s->index = index;
+        if (sel) s->sel = *sel;
         {
             std::lock_guard<std::mutex> g(P->m);
             P->next_submit = index + 1;
@@ -658,6 +722,28 @@ int apds_pipeline_submit(void* pipe, const void* frame, size_t stride_bytes, int
         if (frame_id) *frame_id = index;
         P->q_jobs[e]->push(s);
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+int apds_pipeline_create(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint32_t index_base, void* shard, const void* db_kps_dev, int64_t n_db_total,
+                         const apds_pipeline_params* params) {
+    return create_pipeline(pipe, db_rows64_dev, n_rows, index_base, shard, db_kps_dev, n_db_total, nullptr, 0, params);
+}
+
+int apds_pipeline_create_table(void** pipe, void* db, int view_capacity, const apds_pipeline_params* params) {
+    if (!db) return guarded([] { fail(APDS_ERR_BAD_ARG, "null table"); });
+    return create_pipeline(pipe, nullptr, 0, 0, nullptr, nullptr, 0, db, view_capacity, params);
+}
+
+int apds_pipeline_submit(void* pipe, const void* frame, size_t stride_bytes, int on_device, int64_t* frame_id) {
+    return submit_frame(pipe, frame, stride_bytes, on_device, nullptr, false, frame_id);
+}
+
+int apds_pipeline_submit_select(void* pipe, const void* frame, size_t stride_bytes, int on_device, const apds_db_selection* sel, int64_t* frame_id) {
+    return submit_frame(pipe, frame, stride_bytes, on_device, sel, true, frame_id);
 }
 
 int apds_pipeline_poll(void* pipe, apds_frame_result* result, int wait) { return apds_pipeline_poll_pose(pipe, result, nullptr, wait); }
@@ -698,7 +784,10 @@ int apds_pipeline_enable_pose(void* pipe, const apds_pipeline_pose_params* pose)
     return guarded([&] {
         // the parameters first: every argument error is found before the handle is touched
         APDS_REQUIRE(pose, APDS_ERR_BAD_ARG, "null pose parameters");
-        APDS_REQUIRE(pose->db_xyz_dev, APDS_ERR_BAD_ARG, "the DB rows' world points are required (n_db_total x 3 doubles)");
+        Pipeline* Q = pipe ? static_cast<Pipeline*>(pipe) : nullptr;
+        const bool per_frame = Q && Q->table;
+        APDS_REQUIRE(per_frame || pose->db_xyz_dev, APDS_ERR_BAD_ARG, "the DB rows' world points are required (n_db_total x 3 doubles)");
+        APDS_REQUIRE(!per_frame || !pose->db_xyz_dev, APDS_ERR_BAD_ARG, "a table pipeline takes the world points from the table: db_xyz_dev must be NULL");
         const double* K = pose->camera_intrinsic;
         APDS_REQUIRE(std::isfinite(K[0]) && std::isfinite(K[4]) && K[0] > 0 && K[4] > 0, APDS_ERR_BAD_ARG, "the focal lengths must be finite and positive");
         APDS_REQUIRE(pose->method >= APDS_SOLVEPNP_ITERATIVE && pose->method <= APDS_SOLVEPNP_SQPNP, APDS_ERR_NOT_IMPLEMENTED,
@@ -710,6 +799,12 @@ int apds_pipeline_enable_pose(void* pipe, const apds_pipeline_pose_params* pose)
             if (P->failed) fail(P->fail_code, P->fail_msg);
             APDS_REQUIRE(P->next_submit == 0, APDS_ERR_BAD_ARG, "the pose stage is enabled before the first submit");
             APDS_REQUIRE(!P->pose_on, APDS_ERR_BAD_ARG, "the pose stage is already enabled");
+        }
+        if (P->table) {   // the views gather the table's xyz column: it has to cover every row now (the table is frozen from here on)
+            void* xyz = nullptr;
+            const int rc = apds_db_table(P->table, nullptr, nullptr, &xyz, nullptr);
+            if (rc != APDS_OK) fail(rc, apds_last_error());
+            APDS_REQUIRE(xyz, APDS_ERR_BAD_ARG, "the table's world points are absent or older than its rows (apds_db_world_coordinates)");
         }
         P->pose = *pose;
         if (P->pose.iter_count <= 0) P->pose.iter_count = 100;

@@ -108,6 +108,11 @@ class KeypointTable:
         check(lib().apds_db_view(self._h, C.byref(r), C.byref(k), C.byref(i), C.byref(g), C.byref(n)))
         return r.value, k.value, i.value, g.value, n.value
 
+    def view(self, capacity=None):
+        """A TableView of this table: a selection object of its own (buffers and scratch allocated here), for reads that repeat per
+        frame on a stream of the caller's. capacity None: min(262143, the table's capacity) rows."""
+        return TableView(self, capacity)
+
     def knn_match_view(self, query_desc, k=2):
         """BFMatcher.knnMatch of host query descriptors against the last selection, which stays resident on the device."""
         q = np.ascontiguousarray(query_desc, np.uint8)
@@ -115,6 +120,54 @@ class KeypointTable:
         dist = np.zeros((q.shape[0], k), np.int32)
         check(lib().apds_db_knn_match(self._h, ptr(q), q.shape[0], q.shape[1], int(k), ptr(idx), ptr(dist)))
         return idx, dist
+
+
+class TableView:
+    """keypointdb.rs:50-90 as a per-frame read: the selection of KeypointTable.read_keypoints_from_* (same rows, same order: response
+    descending, ties by table row, at most `capacity` rows), left on the device, on the caller's stream, with one host synchronisation.
+    Any number of views of one table select concurrently from different threads on different streams; none touches the table's own
+    last selection. The table must outlive the view and receive no inserts while a select is in flight."""
+
+    def __init__(self, table, capacity=None):
+        self._table = table     # keeps the table alive
+        self._h = C.c_void_p()
+        check(lib().apds_db_view_create(table._h, int(capacity) if capacity else 0, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().apds_db_view_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _select(self, mode, value, box, with_xyz, stream):
+        n = C.c_int(0)
+        check(lib().apds_db_view_select(self._h, mode, int(value), float(box[0]), float(box[1]), float(box[2]), float(box[3]), 1 if with_xyz else 0,
+                                        stream, C.byref(n)))
+        return n.value
+
+    def read_keypoints_from_image_id(self, image_id, with_xyz=False, stream=None):
+        """keypointdb.rs:38-48 -> the number of rows now in the view"""
+        return self._select(0, image_id, (0, 0, 0, 0), with_xyz, stream)
+
+    def read_keypoints_from_lod(self, level_of_detail, with_xyz=False, stream=None):
+        """keypointdb.rs:50-65"""
+        return self._select(1, level_of_detail, (0, 0, 0, 0), with_xyz, stream)
+
+    def read_keypoints_from_coordinates(self, x_start, y_start, x_end, y_end, level_of_detail, with_xyz=False, stream=None):
+        """keypointdb.rs:67-90"""
+        return self._select(2, level_of_detail, (x_start, y_start, x_end, y_end), with_xyz, stream)
+
+    def device_pointers(self):
+        """(rows64, keypoints, row_ids, image_ids, xyz, n): device pointers of the last selection; xyz is None unless it ran with_xyz.
+        Complete once the stream the selection ran on has finished."""
+        r, k, i, g, x, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+        check(lib().apds_db_view_pointers(self._h, C.byref(r), C.byref(k), C.byref(i), C.byref(g), C.byref(x), C.byref(n)))
+        return r.value, k.value, i.value, g.value, x.value, n.value
 
 
 class ElevationTable:

@@ -439,11 +439,15 @@ class StreamedFramePipeline:
     pointers (train rows, their keypoints, frames), the transport choice for a sharded DB (ShardedMatcher), and results as dicts."""
 
     def __init__(self, db_rows64, db_xy, index_base=0, group=None, max_points=(1 << 18) - 1, device="cuda:0", slots=6, reserve_cus=0,
-                 n_cus=256, meta_group=None, extract_workers=None, transport="rccl", pose=None, db_kp=None):
+                 n_cus=256, meta_group=None, extract_workers=None, transport="rccl", pose=None, db_kp=None, per_frame_table=None, view_capacity=None):
         import os
         self.dev = torch.device(device)
-        self.matcher = ShardedMatcher(db_rows64, index_base, group, meta_group=meta_group, transport=transport)
-        if db_kp is not None:
+        self.per_frame_table = per_frame_table     # a KeypointTable: the train set is selected from it per frame (from_table)
+        self.view_capacity = int(view_capacity) if view_capacity else 0
+        self.matcher = None if per_frame_table is not None else ShardedMatcher(db_rows64, index_base, group, meta_group=meta_group, transport=transport)
+        if per_frame_table is not None:
+            self.n_db, kp = 0, None
+        elif db_kp is not None:
             self.n_db = db_kp.shape[0]     # the 28-byte rows themselves, already on the device (from_table)
             kp = db_kp
         else:
@@ -475,11 +479,17 @@ class StreamedFramePipeline:
         torch.cuda.synchronize()
 
     @classmethod
-    def from_table(cls, table, device="cuda:0", **kw):
+    def from_table(cls, table, device="cuda:0", per_frame_view=False, view_capacity=None, **kw):
         """A pipeline whose database IS a KeypointTable (feature_database.py): the train rows and their keypoints are the table's own device
         columns (table.device_table()), nothing is downloaded or re-uploaded, and a match's train index is the table row (= id - 1). The
         pipeline keeps the table alive; nothing may be inserted into it while the pipeline lives. pose=PoseStage.from_table(table, ..) adds
-        the pose stage on the table's world points."""
+        the pose stage on the table's world points.
+        per_frame_view=True: every frame is matched against the rows ITS selection returns (keypointdb.rs:50-90, at most view_capacity
+        rows, default 262143) instead of the whole table: run(frames, count, selections=[...]) / submit_select(). One GPU."""
+        if per_frame_view:
+            self = cls(None, None, device=device, per_frame_table=table, view_capacity=view_capacity, **kw)
+            self._table = table
+            return self
         rows64, kps, _, n = table.device_table()
         if n <= 0:
             raise ValueError("the table is empty")
@@ -504,10 +514,15 @@ class StreamedFramePipeline:
         h = C.c_void_p()
         m = self.matcher
         check(lib().apds_set_device(self.dev.index or 0))
-        check(lib().apds_pipeline_create(C.byref(h), m.rows.data_ptr(), int(m.rows.shape[0]), m.index_base, m.handle, self.db_kp.data_ptr(), self.n_db, C.byref(p)))
+        if self.per_frame_table is not None:
+            check(lib().apds_pipeline_create_table(C.byref(h), self.per_frame_table._h, self.view_capacity, C.byref(p)))
+        else:
+            check(lib().apds_pipeline_create(C.byref(h), m.rows.data_ptr(), int(m.rows.shape[0]), m.index_base, m.handle, self.db_kp.data_ptr(), self.n_db, C.byref(p)))
         self._pipe, self._key = h, key
         if self.pose is not None:
             pp = self.pose.params()
+            if self.per_frame_table is not None:
+                pp.db_xyz_dev = None     # the views gather the table's own world points
             check(lib().apds_pipeline_enable_pose(h, C.byref(pp)))
 
     def enable_pose(self, pose):
@@ -557,9 +572,35 @@ class StreamedFramePipeline:
         check(lib().apds_pipeline_stats(self._pipe, C.byref(st), 1 if reset else 0))
         return st
 
-    def run(self, frames, count, filter_strength=0.8, reproj_thr=3.0, max_iters=2000, confidence=0.995, timing=False):
-        """Push `count` frames (cycled from `frames`) through the pipeline. Returns (results in frame order, timers)."""
+    @staticmethod
+    def selection(mode, value, box=(0, 0, 0, 0)):
+        """apds_db_selection: mode 0 image id, 1 level of detail, 2 level of detail + bounding box (x_start, y_start, x_end, y_end)"""
+        return _lib.DbSelection(mode=int(mode), value=int(value), x_start=float(box[0]), y_start=float(box[1]), x_end=float(box[2]), y_end=float(box[3]))
+
+    def submit_select(self, frame, sel):
+        """Hand one frame and its train-set selection (selection(..)) to a per-frame-view pipeline (prepare() first); returns the frame number.
+        The frame must stay alive until its result is polled."""
+        ptr, stride, on_dev = self.frame_args(frame)
+        fid = C.c_int64(0)
+        check(lib().apds_pipeline_submit_select(self._pipe, ptr, stride, on_dev, C.byref(sel), C.byref(fid)))
+        return fid.value
+
+    def poll(self, wait=True):
+        """The next result in submission order as a dict (None: wait=False and it is not finished, or nothing is in flight). A frame that
+        failed is reported through its "status", not raised."""
+        res = _lib.FrameResult()
+        fp = _lib.FramePose() if self.pose is not None else None
+        rc = lib().apds_pipeline_poll_pose(self._pipe, C.byref(res), C.byref(fp) if fp is not None else None, 1 if wait else 0)
+        if rc < 0:
+            check(rc)
+        return self.result_dict(res, fp) if rc == 0 else None
+
+    def run(self, frames, count, filter_strength=0.8, reproj_thr=3.0, max_iters=2000, confidence=0.995, timing=False, selections=None):
+        """Push `count` frames (cycled from `frames`) through the pipeline. Returns (results in frame order, timers). selections (a
+        per-frame-view pipeline): the frames' train-set selections, cycled like the frames."""
         L = lib()
+        if (selections is not None) != (self.per_frame_table is not None):
+            raise ValueError("selections go with a pipeline made by from_table(per_frame_view=True), and only with it")
         self._ensure(frames[0].shape, filter_strength, reproj_thr, max_iters, confidence, timing)
         if timing:
             self.stats(reset=True)
@@ -570,7 +611,10 @@ class StreamedFramePipeline:
         results = []
         for i in range(count):
             ptr, stride, on_dev = args[i % len(args)]
-            check(L.apds_pipeline_submit(self._pipe, ptr, stride, on_dev, None))
+            if selections is not None:
+                check(L.apds_pipeline_submit_select(self._pipe, ptr, stride, on_dev, C.byref(selections[i % len(selections)]), None))
+            else:
+                check(L.apds_pipeline_submit(self._pipe, ptr, stride, on_dev, None))
             while True:       # take what is finished, so the result queue stays short on long runs
                 rc = L.apds_pipeline_poll_pose(self._pipe, C.byref(res), fpp, 0)
                 if rc != 0:

@@ -396,6 +396,30 @@ int apds_db_world_coordinates(void* db, const double* dataset_gt, const double* 
  * apds_db_destroy. They are the arguments of apds_pipeline_create(.., rows64, n, 0, NULL, kps, n, ..) and apds_pipeline_pose_params'
  * db_xyz_dev; a match's trainIdx is then the table row, i.e. the id - 1 that apds_db_view_download reports. */
 int apds_db_table(void* db, void** rows64_dev, void** kps_dev, void** xyz_dev, int64_t* n);
+/* View objects: the read of keypointdb.rs:50-90 (read_keypoints_from_lod / read_keypoints_from_coordinates: the rows of one level of
+ * detail, optionally inside a bounding box, ORDER BY response DESC LIMIT 262143) as something a caller repeats for every frame. A view
+ * owns its result buffers and every byte of scratch a selection takes, allocated at create from the table's capacity and the view's,
+ * so any number of views of one table select at the same time from different threads on different streams, and nothing grows with
+ * the number of calls. A view never touches the table's own "current view" (apds_db_select, apds_db_view, apds_db_knn_match).
+ * capacity <= 0: min(262143, table capacity) rows; else min(capacity, 262143). The view borrows the table: destroy it first. The
+ * table must not receive inserts while a select of any of its views is in flight. */
+int apds_db_view_create(void* db, int capacity, void** view);
+int apds_db_view_destroy(void* view);
+/* apds_db_select's selection (same modes, same floor / ceil of the box, same order: response descending with -0.0 tied to +0.0, then
+ * table row ascending - SQL leaves ties in response unspecified, here they fall to row order), cut at the view's capacity, into the
+ * view. With equal limits the rows, keypoints, row ids and image ids are apds_db_select's bit for bit. with_xyz != 0 also gathers
+ * the table's world points (apds_db_world_coordinates; three doubles per row); APDS_ERR_BAD_ARG if that column was never computed or
+ * rows were added since. Everything runs on `stream` (NULL: the calling thread's own). The call synchronises the stream ONCE, for the
+ * number of qualifying rows, queues the cut, the sort and the gather behind it and returns: *n_out is final, the view's buffers are
+ * complete when the stream has run, so work queued later on the same stream (or ordered behind it by an event) reads them safely.
+ * One select at a time per view. */
+int apds_db_view_select(void* view, int mode, int value, float x_start, float y_start, float x_end, float y_end, int with_xyz, void* stream,
+                        int* n_out);
+/* Device pointers of the view's last selection: n x 64-byte descriptor rows (a ready train set; trainIdx = position in the view),
+ * n x 28-byte keypoints, table row ids, image ids, and n x 3 doubles (*xyz_dev NULL unless that selection ran with_xyz). Any output may
+ * be NULL. The pointers hold until apds_db_view_destroy; their contents until the next select. */
+int apds_db_view_pointers(const void* view, void** rows64_dev, void** kps_dev, void** row_ids_dev, void** image_ids_dev, void** xyz_dev,
+                          int* n);
 
 /* ---- multi-GPU: the descriptor DB row-sharded over the GPUs of one node (BASELINE config 5) -------------------------------
  * No counterpart upstream: the reference matches on one CPU (feature_extraction/src/lib.rs:94-126) against whatever train set
@@ -558,6 +582,22 @@ int apds_pipeline_enable_pose(void* pipe, const apds_pipeline_pose_params* pose)
 /* apds_pipeline_poll with the frame's pose: *pose (may be NULL) is filled when pose is enabled, zeroed (status APDS_OK, found 0) otherwise.
  * apds_pipeline_poll is this call with pose = NULL. */
 int apds_pipeline_poll_pose(void* pipe, apds_frame_result* result, apds_frame_pose* pose, int wait);
+/* A pipeline whose train set is selected per frame, the reference's own access path (keypointdb.rs:50-90: a frame is matched against
+ * the rows its read returns, never against the whole table). One GPU. Every slot owns a view of `db` (apds_db_view_create with
+ * view_capacity; six slots of full-size views are about 200 MB); the match worker runs the frame's selection on the match stream in
+ * front of the scan, matches the frame against the view's rows, and the ratio filter, matched points, homography and (if enabled) pose
+ * read the view's keypoints and world points by view position. Train indices never leave the library. The table is borrowed until
+ * apds_pipeline_destroy and must not receive inserts meanwhile. apds_pipeline_enable_pose on such a pipeline takes db_xyz_dev == NULL
+ * (anything else is APDS_ERR_BAD_ARG) and requires the table's world points to be current (APDS_ERR_BAD_ARG otherwise).
+ * A frame whose view has fewer than two rows gets the status the one-call matcher gives for such a train set (APDS_ERR_ASSERT), no
+ * matches and no homography; the pipeline goes on. apds_pipeline_submit on a table pipeline and apds_pipeline_submit_select on any
+ * other are APDS_ERR_BAD_ARG; so are a NULL sel and a mode outside 0..2, before any device work. */
+typedef struct apds_db_selection {
+    int mode, value;                         /* apds_db_select's: 0 image id, 1 level of detail, 2 level of detail and bounding box */
+    float x_start, y_start, x_end, y_end;    /* mode 2: floor(start) <= v <= ceil(end) */
+} apds_db_selection;
+int apds_pipeline_create_table(void** pipe, void* db, int view_capacity, const apds_pipeline_params* params);
+int apds_pipeline_submit_select(void* pipe, const void* frame, size_t stride_bytes, int on_device, const apds_db_selection* sel, int64_t* frame_id);
 
 /* ---- device-resident API ------------------------------------------------------------------- */
 /* All pointers below are HIP device pointers. stream: hipStream_t or NULL (the thread's own stream).

@@ -4,7 +4,7 @@
 //! chains `akaze_keypoint_descriptor_extraction_def` -> `get_knn_matches` -> `get_points_from_matches` only inside unit tests
 //! (feature_extraction/src/lib.rs:197-249) and calls extraction from a rayon pool without a lock (preprocessor/src/main.rs:227-245); this
 //! is that chain for a stream of frames, one `submit` and one `poll` per frame. NOT compiled in the build container (no Rust toolchain).
-use apds_sys::{apds_frame_pose, apds_frame_result, apds_pipeline_counters, apds_pipeline_params, apds_pipeline_pose_params, APDS_PIPELINE_NOT_READY,
+use apds_sys::{apds_db_selection, apds_frame_pose, apds_frame_result, apds_pipeline_counters, apds_pipeline_params, apds_pipeline_pose_params, APDS_PIPELINE_NOT_READY,
                APDS_SOLVEPNP_EPNP};
 use std::ffi::CStr;
 use std::os::raw::c_void;
@@ -72,6 +72,41 @@ impl FramePipeline {
     pub fn submit(&self, pixels: &[u8]) -> Result<i64, String> {
         let mut id = -1i64;
         let rc = unsafe { apds_sys::apds_pipeline_submit(self.pipe, pixels.as_ptr() as *const c_void, self.stride, 0, &mut id) };
+        if rc != 0 {
+            return Err(err(rc));
+        }
+        Ok(id)
+    }
+
+    /// A pipeline whose train set is selected per frame from a keypoint table (`db`: an `apds_db_create` handle, borrowed until the
+    /// pipeline is dropped and frozen meanwhile): the reference's access path, keypointdb.rs:50-90. Frames go in through `submit_select`.
+    /// `view_capacity` <= 0: 262143 rows (keypointdb.rs:12).
+    pub fn new_table(gpu: i32, rows: i32, cols: i32, channels: i32, db: *mut c_void, view_capacity: i32, filter_strength: f32, method: i32,
+                     reproj_threshold: f64) -> Result<Self, String> {
+        let params = apds_pipeline_params {
+            rows, cols, channels, max_points: 0, n_slots: 0, extract_workers: 0, filter_strength, homography_method: method, reproj_threshold,
+            max_iters: 0, confidence: 0.0, timing: 0, match_lds_cap: 0, match_stream: ptr::null_mut(), debug_extract_delay_ms: 0.0,
+        };
+        let mut pipe = ptr::null_mut();
+        unsafe {
+            let rc = apds_sys::apds_set_device(gpu);
+            if rc != 0 {
+                return Err(err(rc));
+            }
+            let rc = apds_sys::apds_pipeline_create_table(&mut pipe, db, view_capacity, &params);
+            if rc != 0 {
+                return Err(err(rc));
+            }
+        }
+        Ok(FramePipeline { pipe, stride: (cols * channels) as usize })
+    }
+
+    /// `submit` on a `new_table` pipeline: the frame is matched against the rows `read_keypoints_from_coordinates(x_start, y_start, x_end,
+    /// y_end, level_of_detail)` returns (keypointdb.rs:67-90: floor(start) <= v <= ceil(end), ORDER BY response DESC LIMIT 262143).
+    pub fn submit_select(&self, pixels: &[u8], x_start: f32, y_start: f32, x_end: f32, y_end: f32, level_of_detail: i32) -> Result<i64, String> {
+        let sel = apds_db_selection { mode: 2, value: level_of_detail, x_start, y_start, x_end, y_end };
+        let mut id = -1i64;
+        let rc = unsafe { apds_sys::apds_pipeline_submit_select(self.pipe, pixels.as_ptr() as *const c_void, self.stride, 0, &sel, &mut id) };
         if rc != 0 {
             return Err(err(rc));
         }

@@ -19,8 +19,8 @@ BASE = {"void": "c_void", "char": "c_char", "int": "c_int", "float": "f32", "dou
         "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64", "apds_keypoint": "apds_keypoint", "apds_dmatch": "apds_dmatch",
         "apds_comm_id": "apds_comm_id", "apds_host_transport": "apds_host_transport", "apds_pipeline_params": "apds_pipeline_params",
         "apds_frame_result": "apds_frame_result", "apds_pipeline_counters": "apds_pipeline_counters", "apds_device_transport": "apds_device_transport",
-        "apds_pipeline_pose_params": "apds_pipeline_pose_params", "apds_frame_pose": "apds_frame_pose"}
-POD_STRUCTS = ["apds_pipeline_params", "apds_frame_result", "apds_pipeline_counters", "apds_pipeline_pose_params", "apds_frame_pose"]     # plain-data structs translated field by field
+        "apds_pipeline_pose_params": "apds_pipeline_pose_params", "apds_frame_pose": "apds_frame_pose", "apds_db_selection": "apds_db_selection"}
+POD_STRUCTS = ["apds_pipeline_params", "apds_frame_result", "apds_pipeline_counters", "apds_pipeline_pose_params", "apds_frame_pose", "apds_db_selection"]     # plain-data structs translated field by field
 RESERVED = {"type", "match", "ref", "box", "move", "in", "fn", "loop", "mod", "use", "where", "impl", "self", "super", "crate", "dyn", "as"}
 
 
