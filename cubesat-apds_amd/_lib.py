@@ -17,6 +17,9 @@ assert KEYPOINT_DTYPE.itemsize == 28 and DMATCH_DTYPE.itemsize == 16
 
 ERR_INTERNAL, ERR_NOMEM, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_OUT_OF_RANGE, ERR_ASSERT, ERR_EMPTY = -2, -4, -5, -216, -211, -215, -1000
 ERR_NOT_IMPLEMENTED = -213
+PIPELINE_MATCH_RATIO, PIPELINE_MATCH_CROSSCHECK = 0, 1   # apds_pipeline_set_matcher
+PIPELINE_MATCHERS = {"ratio": PIPELINE_MATCH_RATIO, "crosscheck": PIPELINE_MATCH_CROSSCHECK}
+ERR_NOT_IMPLEMENTED = -213
 
 # every symbol include/apds.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -43,6 +46,7 @@ SYMBOLS = [
     "apds_dev_akaze_extract_batch_masked_support", "apds_dev_mask_zero_sat",
     "apds_db_insert_dev", "apds_db_insert_batch_dev", "apds_mosaic_tiles_to_db", "apds_db_world_coordinates", "apds_db_table",
     "apds_db_view_create", "apds_db_view_destroy", "apds_db_view_select", "apds_db_view_pointers", "apds_pipeline_create_table", "apds_pipeline_submit_select",
+    "apds_dev_crosscheck_match", "apds_pipeline_set_matcher",
 ]
 
 RESAMPLE_NEAREST, RESAMPLE_LANCZOS = 0, 1
@@ -293,6 +297,8 @@ def lib():
             "apds_db_view_pointers": (i, [vp, pp, pp, pp, pp, pp, ip]),
             "apds_pipeline_create_table": (i, [pp, vp, i, C.POINTER(PipelineParams)]),
             "apds_pipeline_submit_select": (i, [vp, vp, sz, i, C.POINTER(DbSelection), C.POINTER(i64)]),
+            "apds_dev_crosscheck_match": (i, [vp, i, vp, i64, u32, vp, ip, vp]),
+            "apds_pipeline_set_matcher": (i, [vp, i]),
         }
         for name, (rt, at) in sig.items():
             fn = getattr(L, name)

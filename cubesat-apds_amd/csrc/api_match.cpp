@@ -269,6 +269,27 @@ int apds_dev_cross_check(const void* train_best, int64_t n_train, int nq, void* 
     });
 }
 
+// apds_get_bruteforce_matches on device rows: the roles-swapped top-1 (every train row's nearest query, ties to the lower query), then per
+// query the closest train row that chose it (ties to the lower train row), in query order. The streamed pipeline's cross-check mode runs
+// the same two steps on two stage threads (csrc/pipeline.cpp).
+int apds_dev_crosscheck_match(const void* q, int nq, const void* t, int64_t nt, uint32_t index_base, void* out_matches, int* n_matches, void* stream) {
+    APDS_RANGE("apds_dev_crosscheck_match");
+    return guarded([&] {
+        APDS_REQUIRE(n_matches, APDS_ERR_BAD_ARG, "null output");
+        *n_matches = 0;
+        APDS_REQUIRE(nq >= 0 && nt >= 0, APDS_ERR_ASSERT, "negative row count");
+        APDS_REQUIRE(nt <= (int64_t)INT_MAX, APDS_ERR_ASSERT, "the train rows are the searching side of the swapped scan: at most INT_MAX of them");
+        if (nq == 0 || nt == 0) return;
+        APDS_REQUIRE(q && t && out_matches, APDS_ERR_BAD_ARG, "null argument");
+        ThreadCtx& c = ctx();
+        c.ws_reset();
+        hipStream_t s = pick_stream(stream);
+        uint64_t* tbest = c.alloc_n<uint64_t>((size_t)nt);
+        hamming_topk_device(t, (int)nt, q, nq, 0, 1, tbest, s);
+        *n_matches = cross_check_base_device(tbest, nt, nq, index_base, static_cast<apds_dmatch*>(out_matches), s);
+    });
+}
+
 int apds_dev_points_from_matches(const void* kp1, int n1, const void* kp2, int n2, const void* m, int nm, int bug_compatible, void* pts1,
                                  void* pts2, void* stream) {
     return guarded([&] {

@@ -733,4 +733,52 @@ void hamming_mfma_topk_train_device(const void* q, int nq, const void* train, ui
     hm_topk_expanded(q, nq, t->rows, t->pc, t->n, index_base, k, out, s);
 }
 
+// ---- the roles-swapped scan of the cross-check (get_bruteforce_matches, lib.rs:116-126) against a train set expanded once ----
+// Every TRAIN row looks for its nearest query: the searching side - the register columns of hamming_mfma_kernel - is the resident train
+// set, the streamed side the frame's rows. The kernel never asks which side is which: a product is (tile nibble) x (column nibble), the
+// accumulator is preset from the TILE rows' biased popcounts, and hm_distance adds the COLUMN row's plain popcount. So the resident
+// expansion (nibble 1.0, made for the tile side) serves as the column operand as it is, the frame's rows are expanded per frame with the
+// other nibble (-2.0: every product is still 0 or -2) and THEIR popcounts carry the bias:
+//     acc = popcount(f) + 1024 - 2 popcount(f AND t),   distance = popcount(t) + acc - 1024 = hamming(f, t)
+// - the same integers, the same exactness argument as the forward form (file header), no row of the train set expanded again. What the
+// column side needs beside the operands is the train rows' popcounts WITHOUT the bias (hm_train_plain_popcounts_device: once per train
+// set). Keys: (distance << 32 | frame row); equal distances keep the lower frame row, as the forward form keeps the lower train row.
+__global__ void hm_plain_popcounts_kernel(const float* __restrict__ biased, long long n, float* __restrict__ plain) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) plain[i] = biased[i] - (float)HM_BIAS;   // (integers below 2^11: exact)
+}
+
+// out: n floats (n = the train set's rows) = popcount of every row, what hm_scan_device takes as qpc when the train set is the column side
+void hm_train_plain_popcounts_device(const void* train, float* out, hipStream_t s) {
+    const HmTrain* t = static_cast<const HmTrain*>(train);
+    APDS_REQUIRE(t && out, APDS_ERR_ASSERT, "an expanded train set and an output are required");
+    hipLaunchKernelGGL(hm_plain_popcounts_kernel, dim3((unsigned)ceil_div(t->n, 256ll)), dim3(256), 0, s, (const float*)t->pc, (long long)t->n, out);
+    HIP_CHECK(hipGetLastError());
+}
+
+// train_best[r] = (distance << 32 | nearest of the n rows) for every row r of the expanded train set; n >= 1 rows of 64 bytes on the device.
+// Scratch (the n rows' operands, the split lists) is the calling thread's workspace.
+void hamming_mfma_swapped_top1_device(const void* rows64, int n, const void* train, const float* train_plain_pc, uint64_t* train_best, hipStream_t s) {
+    const HmTrain* t = static_cast<const HmTrain*>(train);
+    APDS_REQUIRE(t && train_plain_pc && rows64 && train_best && n > 0, APDS_ERR_ASSERT, "the swapped scan needs an expanded train set, its plain popcounts and rows");
+    ThreadCtx& c = ctx();
+    const long long n_pad = hm_padded_rows(n);
+    uint4* f4 = static_cast<uint4*>(c.alloc((size_t)n_pad * 256));
+    float* fp = c.alloc_n<float>((size_t)n_pad);
+    {
+        KernelTimer timer("hamming_topk_sample", s);   // (the counters' name for what runs in front of the main match kernel)
+        hipLaunchKernelGGL(hm_expand_rows_kernel, dim3((unsigned)ceil_div((long long)n * 16, 256ll)), dim3(256), 0, s, static_cast<const uint32_t*>(rows64), (long long)n, 0xCu,
+                           HM_BIAS, f4, fp);
+        if (n_pad > n) hipLaunchKernelGGL(hm_pad_rows_kernel, dim3(1), dim3(128), 0, s, f4, fp, (long long)n, n_pad);
+    }
+    const int nc = (int)t->n;   // (hm_train_create: below 2^31)
+    const HmPlan p = hm_plan(nc, n, 2);
+    uint64_t* top2 = c.alloc_n<uint64_t>((size_t)nc * 2);
+    uint64_t* parts = p.splits == 1 ? top2 : c.alloc_n<uint64_t>((size_t)p.splits * nc * 2);
+    hm_scan_device(t->rows, train_plain_pc, nc, f4, fp, n, p, 0, parts, s, nullptr, /*timed=*/true, 2);
+    if (p.splits > 1) merge_topk_device(parts, p.splits, nc, 2, top2, s);
+    take_first_columns_device(top2, nc, 2, 1, train_best, s);
+    HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace apds

@@ -47,11 +47,16 @@ long long hm_sample_rows(long long nt);
 void* hm_train_create(const void* rows64, long long n, hipStream_t s);
 void hm_train_destroy(void* train);
 void hamming_mfma_topk_train_device(const void* q, int nq, const void* train, uint32_t index_base, int k, uint64_t* out, hipStream_t s);
+// the cross-check's roles-swapped top-1 with an expanded train set as the searching side: train_best[row] = (distance << 32 | nearest of the
+// n rows); train_plain_pc: hm_train_plain_popcounts_device's output (the train rows' popcounts without the bias, made once per train set)
+void hm_train_plain_popcounts_device(const void* train, float* out, hipStream_t s);
+void hamming_mfma_swapped_top1_device(const void* rows64, int n, const void* train, const float* train_plain_pc, uint64_t* train_best, hipStream_t s);
 
 // match_filter.hip: ratio test, cross-check, ordered compaction
 int* scan_flags_device(const uint8_t* flags, int n, int** total_dev, hipStream_t s);
 int ratio_filter_device(const uint64_t* keys, int nq, int k, float fs, apds_dmatch* out, hipStream_t s);
 int cross_check_device(const uint64_t* train_best, long long n_train, int nq, apds_dmatch* out, hipStream_t s);
+int cross_check_base_device(const uint64_t* train_best, long long n_train, int nq, uint32_t index_base, apds_dmatch* out, hipStream_t s);   // train_idx = row + index_base
 
 // valu_peak.hip
 double valu_popcount_peak_device();

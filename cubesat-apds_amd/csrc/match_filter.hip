@@ -149,4 +149,44 @@ int cross_check_device(const uint64_t* train_best, long long n_train, int nq, ap
     return emit_flagged_device(best, nq, 1, flags, out, s);
 }
 
+// ---- the cross-check with an index base (apds_dev_crosscheck_match, the pipeline's cross-check mode) ----
+// The scatter, the flags and the scan are cross_check_device's; the emit adds index_base to the train row (a shard's or a batch's global
+// row, as the keys of apds_dev_hamming_topk carry it). best_per_query[q] = (distance << 32 | train row), EMPTY where nobody chose q.
+__global__ __launch_bounds__(SCAN_BLOCK) void emit_crosscheck_matches_kernel(const uint64_t* __restrict__ best_per_query, int nq, uint32_t index_base,
+                                                                             const uint8_t* __restrict__ flags, const int* __restrict__ block_offsets,
+                                                                             apds_dmatch* __restrict__ out) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const int i = blockIdx.x * SCAN_BLOCK + threadIdx.x;
+    const int f = i < nq ? (flags[i] != 0) : 0;
+    const int pos = block_exclusive_pos(f, block_offsets[blockIdx.x]);
+    if (f) {
+        const uint64_t k0 = best_per_query[i];
+        apds_dmatch m;
+        m.query_idx = i;
+        m.train_idx = (int32_t)((uint32_t)k0 + index_base);
+        m.img_idx = 0;
+        m.distance = (float)(uint32_t)(k0 >> 32);
+        out[pos] = m;
+    }
+}
+
+int cross_check_base_device(const uint64_t* train_best, long long n_train, int nq, uint32_t index_base, apds_dmatch* out, hipStream_t s) {
+    if (nq <= 0 || n_train <= 0) return 0;
+    ThreadCtx& c = ctx();
+    uint64_t* best = c.alloc_n<uint64_t>(nq);
+    HIP_CHECK(hipMemsetAsync(best, 0xFF, (size_t)nq * 8, s));
+    hipLaunchKernelGGL(crosscheck_scatter_kernel, dim3(ceil_div(n_train, 256)), dim3(256), 0, s, train_best, n_train,
+                       reinterpret_cast<unsigned long long*>(best));
+    uint8_t* flags = c.alloc_n<uint8_t>(nq);
+    hipLaunchKernelGGL(nonempty_flag_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, s, best, nq, flags);
+    int* total_dev = nullptr;
+    int* offs = scan_flags_device(flags, nq, &total_dev, s);
+    hipLaunchKernelGGL(emit_crosscheck_matches_kernel, dim3(ceil_div(nq, SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, s, best, nq, index_base, flags, offs, out);
+    HIP_CHECK(hipGetLastError());
+    int total = 0;
+    HIP_CHECK(hipMemcpyAsync(&total, total_dev, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return total;
+}
+
 }  // namespace apds

@@ -14,11 +14,17 @@
 // A table pipeline (apds_pipeline_create_table) selects each frame's train set from a keypoint table first (keypointdb.rs:50-90): the match
 // worker runs the slot's view select on the match stream in front of the scan, and the later stages read the view by position.
 //
+// The matcher is selectable before the first submit (apds_pipeline_set_matcher): the cross-check (get_bruteforce_matches, lib.rs:116-126)
+// replaces the forward top-2 scan by ONE roles-swapped top-1 scan per frame - every train row's nearest query, into the slot's train_best;
+// with the matrix-core matcher the resident expanded copy of the DB is its searching side as it is - and the ratio filter by the
+// cross-check's scatter / flags / ordered compaction; everything behind the matches is unchanged.
+//
 // Every worker owns a HIP stream and a device workspace (the per-thread context every entry point uses), stages hand frames over
 // through HIP events, results leave in frame order. The reference only chains these steps inside unit tests
 // (feature_extraction/src/lib.rs:197-249) and never calls find_homography_mat on the result; this is the composed path the
 // north-star metric (frames/s) is measured on. The Python class cubesat-apds_amd/pipeline.py:StreamedFramePipeline is a front of this.
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <condition_variable>
 #include <cstring>
@@ -92,6 +98,7 @@ struct Slot {
     hipEvent_t ev_extract = nullptr, ev_pre = nullptr, ev_scan = nullptr, ev_match = nullptr;
     hipEvent_t ev_mstart = nullptr, ev_mend = nullptr;   // (timing enabled) the match stream's idle gaps: starvation watch
     void* topk_state = nullptr;   // split scan (one GPU)
+    uint64_t* train_best = nullptr;   // cross-check mode (apds_pipeline_set_matcher): every train row's nearest query of this slot's frame
     void* shard_slot = nullptr;   // exchange slot (sharded DB)
     // a table pipeline (apds_pipeline_create_table): this slot's view of the table, the frame's selection and what it gave. The later
     // stages read the train side from here (the view's pointers never change; its contents hold until the slot's next frame).
@@ -141,6 +148,9 @@ struct Pipeline {
     hipStream_t st_extract[8] = {}, st_match = nullptr, st_pre = nullptr, st_merge = nullptr, st_homography = nullptr, st_gather = nullptr, st_counts = nullptr;
     hipStream_t st_pose = nullptr;
     std::atomic<bool> pose_on{false};   // set once, before the first submit
+    std::atomic<int> matcher{APDS_PIPELINE_MATCH_RATIO};   // set before the first submit (apds_pipeline_set_matcher)
+    float* db_plain_pc = nullptr;   // cross-check mode on the expanded copy: the train rows' popcounts as the swapped scan's column side takes them
+    int view_capacity = 0;
     apds_pipeline_pose_params pose{};
 
     std::mutex m;   // results, counters, errors
@@ -291,6 +301,9 @@ struct Pipeline {
         int e = 0;
         int64_t seen = 0;
         while (q_any.pop(e)) {
+            // cross-check mode: one roles-swapped top-1 per frame (every train row's nearest query) on the single-stream branch; the split
+            // scan, the threshold pre-pass and the starvation watch belong to the ratio matcher
+            const bool crosscheck = matcher == APDS_PIPELINE_MATCH_CROSSCHECK;
             if (e < 0) {
                 harvest({"hamming_topk", "hamming_topk_sample"});
                 continue;
@@ -317,12 +330,14 @@ struct Pipeline {
                         s->status = APDS_ERR_ASSERT;
                         s->error = "the frame's selection has fewer than two rows: a train set of at least two rows is required";
                     }
+                } else if (K > 0 && crosscheck) {
+                    PIPE_OK(apds_dev_hamming_topk(s->view_rows64, s->n_view, s->desc, K, 0, 1, s->train_best, st_match));
                 } else if (K > 0) {
                     PIPE_OK(apds_dev_hamming_topk(s->desc, K, s->view_rows64, s->n_view, 0, 2, s->keys, st_match));
                 }
                 HIP_CHECK(hipEventRecord(s->ev_match, st_match));
                 HIP_CHECK(hipEventRecord(s->ev_mend, st_match));
-            } else if (K > 0 && split) {
+            } else if (K > 0 && split && !crosscheck) {
                 HIP_CHECK(hipStreamWaitEvent(st_pre, s->ev_extract, 0));   // threshold pre-pass: beside the previous frame's main scan
                 PIPE_OK(apds_dev_topk_prepass(s->topk_state, s->desc, K, db_rows, n_rows, index_base, 2, st_pre));
                 HIP_CHECK(hipEventRecord(s->ev_pre, st_pre));
@@ -337,7 +352,14 @@ struct Pipeline {
             } else {
                 HIP_CHECK(hipStreamWaitEvent(st_match, s->ev_extract, 0));
                 HIP_CHECK(hipEventRecord(s->ev_mstart, st_match));
-                if (K > 0 && db_expanded) {   // the matrix-core matcher on the DB's expanded copy
+                if (K > 0 && crosscheck && db_expanded) {   // the resident expanded copy as the searching side: only the frame's rows are expanded
+                    PIPE_OK(guarded([&] {
+                        ctx().ws_reset();
+                        hamming_mfma_swapped_top1_device(s->desc, K, db_expanded, db_plain_pc, s->train_best, st_match);
+                    }));
+                } else if (K > 0 && crosscheck) {   // (vector-ALU matcher: the swapped scan directly)
+                    PIPE_OK(apds_dev_hamming_topk(db_rows, (int)n_rows, s->desc, K, 0, 1, s->train_best, st_match));
+                } else if (K > 0 && db_expanded) {   // the matrix-core matcher on the DB's expanded copy
                     PIPE_OK(guarded([&] {
                         ctx().ws_reset();   // (as every entry point does: the scan's scratch is this thread's workspace from its start; one stream orders the frames)
                         hamming_mfma_topk_train_device(s->desc, K, db_expanded, index_base, 2, static_cast<uint64_t*>(s->keys), st_match);
@@ -348,7 +370,7 @@ struct Pipeline {
                 HIP_CHECK(hipEventRecord(s->ev_match, st_match));
                 HIP_CHECK(hipEventRecord(s->ev_mend, st_match));
             }
-            if (watch) {
+            if (watch && !crosscheck) {
                 if (prev && seen >= 4) pending.emplace_back(prev, s);   // the first frames are the pipeline filling up
                 while (!pending.empty() && hipEventQuery(pending.front().second->ev_mstart) == hipSuccess) {
                     float g = -1;
@@ -451,7 +473,15 @@ struct Pipeline {
                 const bool matched = s->K > 0 && !(table && s->n_view < 2);
                 const apds_keypoint* train_kps = table ? s->view_kps : db_kps;
                 const int n_train = table ? s->n_view : (int)n_db_total;
-                if (matched) PIPE_OK(apds_dev_ratio_filter(s->keys, s->K, 2, p.filter_strength, s->matches, &M, st));
+                if (matched && matcher == APDS_PIPELINE_MATCH_CROSSCHECK) {
+                    // per query the closest train row that chose it, in query order; train_idx = row + index_base (a view: its position)
+                    PIPE_OK(guarded([&] {
+                        ctx().ws_reset();
+                        M = cross_check_base_device(s->train_best, table ? (long long)s->n_view : (long long)n_rows, s->K, table ? 0u : index_base, s->matches, st);
+                    }));
+                } else if (matched) {
+                    PIPE_OK(apds_dev_ratio_filter(s->keys, s->K, 2, p.filter_strength, s->matches, &M, st));
+                }
                 r.n_matches = M;
                 if (M >= 4) {
                     // query_idx -> this frame's keypoints, train_idx -> the DB rows' keypoints (the intended gather: lib.rs:161-180 has two bugs)
@@ -538,7 +568,7 @@ void destroy_pipeline(Pipeline* P) {
     for (auto& up : P->slots) {
         Slot* s = up.get();
         for (void* ptr : {(void*)s->kps, (void*)s->desc, (void*)s->keys, (void*)s->matches, (void*)s->p1, (void*)s->p2, (void*)s->mask, (void*)s->frame_dev,
-                          (void*)s->pose_img, (void*)s->pose_obj})
+                          (void*)s->pose_img, (void*)s->pose_obj, (void*)s->train_best})
             if (ptr) (void)hipFree(ptr);
         for (hipEvent_t ev : {s->ev_extract, s->ev_pre, s->ev_scan, s->ev_match, s->ev_mstart, s->ev_mend, s->ev_homography})
             if (ev) (void)hipEventDestroy(ev);
@@ -548,6 +578,8 @@ void destroy_pipeline(Pipeline* P) {
     }
     if (P->db_expanded) hm_train_destroy(P->db_expanded);
     P->db_expanded = nullptr;
+    if (P->db_plain_pc) (void)hipFree(P->db_plain_pc);
+    P->db_plain_pc = nullptr;
     if (!P->own_match_stream) P->st_match = nullptr;
     for (hipStream_t st : {P->st_match, P->st_pre, P->st_merge, P->st_homography, P->st_gather, P->st_counts, P->st_pose})
         if (st) (void)hipStreamDestroy(st);
@@ -588,6 +620,7 @@ int create_pipeline(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint
         P->p = in;
         P->device = c.device;
         P->table = table;
+        P->view_capacity = view_capacity;
         P->db_rows = db_rows64_dev;
         P->n_rows = n_rows;
         P->index_base = index_base;
@@ -824,6 +857,41 @@ int apds_pipeline_enable_pose(void* pipe, const apds_pipeline_pose_params* pose)
         P->pose_on = true;
         Pipeline* raw = P;
         P->threads.emplace_back([raw] { raw->worker("pose", [&] { raw->pose_worker(); }); });
+    });
+}
+
+int apds_pipeline_set_matcher(void* pipe, int matcher) {
+    return guarded([&] {
+        // the three contract checks first, before any device work
+        APDS_REQUIRE(matcher == APDS_PIPELINE_MATCH_RATIO || matcher == APDS_PIPELINE_MATCH_CROSSCHECK, APDS_ERR_BAD_ARG,
+                     "matcher: APDS_PIPELINE_MATCH_RATIO (0) or APDS_PIPELINE_MATCH_CROSSCHECK (1)");
+        Pipeline* P = pipe_handle(pipe);
+        APDS_REQUIRE(matcher == APDS_PIPELINE_MATCH_RATIO || !(P->shard || P->world > 1), APDS_ERR_NOT_IMPLEMENTED,
+                     "the cross-check over a row-sharded train set (the per-query minimum across shards) is not built");
+        std::lock_guard<std::mutex> one(P->submit_m);
+        {
+            std::lock_guard<std::mutex> g(P->m);
+            if (P->failed) fail(P->fail_code, P->fail_msg);
+            APDS_REQUIRE(P->next_submit == 0, APDS_ERR_BAD_ARG, "the matcher is chosen before the first submit");
+        }
+        if (matcher == APDS_PIPELINE_MATCH_CROSSCHECK) {
+            // every slot's train_best: one key per train row (a table pipeline: per row a view can hold); the swapped scan's searching side
+            // counts its rows in an int
+            APDS_REQUIRE(P->table || P->n_rows <= (int64_t)INT_MAX, APDS_ERR_ASSERT, "the train rows are the searching side of the swapped scan: at most INT_MAX of them");
+            const size_t rows = P->table ? (size_t)(P->view_capacity > 0 ? std::min(P->view_capacity, APDS_MAX_POINTS) : APDS_MAX_POINTS) : (size_t)P->n_rows;
+            int previous = -1;
+            if (hipGetDevice(&previous) != hipSuccess) previous = -1;
+            HIP_CHECK(hipSetDevice(P->device));
+            for (auto& s : P->slots)
+                if (!s->train_best) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->train_best), rows * sizeof(uint64_t)));
+            if (P->db_expanded && !P->db_plain_pc) {
+                HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&P->db_plain_pc), (size_t)P->n_rows * sizeof(float)));
+                hm_train_plain_popcounts_device(P->db_expanded, P->db_plain_pc, P->st_match);
+                HIP_CHECK(hipStreamSynchronize(P->st_match));
+            }
+            if (previous >= 0 && previous != P->device) (void)hipSetDevice(previous);
+        }
+        P->matcher = matcher;
     });
 }
 

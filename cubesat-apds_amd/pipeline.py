@@ -299,6 +299,26 @@ class ShardedMatcher:
         return dst
 
 
+def _matcher_code(matcher):
+    """"ratio" | "crosscheck" -> APDS_PIPELINE_MATCH_*"""
+    try:
+        return _lib.PIPELINE_MATCHERS[matcher]
+    except (KeyError, TypeError):
+        raise ValueError('matcher: "ratio" (get_knn_matches, lib.rs:94-114) or "crosscheck" (get_bruteforce_matches, lib.rs:116-126)') from None
+
+
+def dev_crosscheck_match(q_rows64, t_rows64, index_base=0, out=None):
+    """apds_dev_crosscheck_match on the CURRENT stream: get_bruteforce_matches (BFMatcher crossCheck = true, lib.rs:116-126) of device rows
+    [Q, 64] u8 against [N, 64] u8. Returns the matches as a [M, 4] int32 device tensor (16-byte cv::DMatch rows: query, train + index_base,
+    image, distance as f32 bits) in query order - a view of `out` ([>= Q, 4] int32) when given."""
+    nq, nt = int(q_rows64.shape[0]), int(t_rows64.shape[0])
+    dst = out if out is not None else torch.empty((max(nq, 1), 4), dtype=torch.int32, device=q_rows64.device)
+    n = C.c_int(0)
+    check(lib().apds_dev_crosscheck_match(q_rows64.data_ptr() if nq else None, nq, t_rows64.data_ptr() if nt else None, nt, int(index_base), dst.data_ptr(),
+                                          C.byref(n), torch_stream()))
+    return dst[:n.value]
+
+
 SOLVEPNP_EPNP = 1
 
 
@@ -378,12 +398,16 @@ class FramePipeline:
         self.p2 = torch.empty((self.cap, 2), dtype=torch.float32, device=self.dev)
         self.mask = torch.empty(self.cap, dtype=torch.uint8, device=self.dev)
 
-    def step(self, frame, filter_strength=0.8, reproj_thr=3.0, max_iters=2000, confidence=0.995, pose=None):
+    def step(self, frame, filter_strength=0.8, reproj_thr=3.0, max_iters=2000, confidence=0.995, pose=None, matcher="ratio"):
         """frame: [H, W, C] u8 device tensor. Returns dict(n_keypoints, n_matches, H (3x3 numpy) or None, n_inliers), and with a PoseStage
         `pose` also "pose": the frame's matches downloaded, the pairs built on the host and solved by apds_pnp_solver_ransac (the
-        established path the streamed pose stage is compared against)."""
+        established path the streamed pose stage is compared against). matcher "crosscheck": get_bruteforce_matches instead of the ratio
+        matcher (one GPU; filter_strength is then unused)."""
+        code = _matcher_code(matcher)
+        if code == _lib.PIPELINE_MATCH_CROSSCHECK and self.matcher.handle is not None:
+            raise _lib.ApdsError(_lib.ERR_NOT_IMPLEMENTED, "the cross-check over a row-sharded train set is not built")
         with torch.cuda.stream(self.stream):
-            out = self._step(frame, filter_strength, reproj_thr, max_iters, confidence)
+            out = self._step(frame, filter_strength, reproj_thr, max_iters, confidence, code)
             if pose is not None:
                 M = out["n_matches"]
                 m = self.matches[:M].cpu().numpy()
@@ -391,7 +415,7 @@ class FramePipeline:
                 out["pose"] = pose.solve(kp[m[:, 0], 0:2], m[:, 1])
             return out
 
-    def _step(self, frame, filter_strength, reproj_thr, max_iters, confidence):
+    def _step(self, frame, filter_strength, reproj_thr, max_iters, confidence, matcher=_lib.PIPELINE_MATCH_RATIO):
         L = lib()
         h, w = frame.shape[0], frame.shape[1]
         ch = 1 if frame.dim() == 2 else frame.shape[2]
@@ -400,12 +424,17 @@ class FramePipeline:
                                        C.byref(n), torch_stream()))
         K = n.value
         out = dict(n_keypoints=K, n_matches=0, H=None, n_inliers=0)
-        keys = self.matcher.knn(self.desc[:K], 2)
-        if K == 0:
-            return out
-        nm = C.c_int(0)
-        check(L.apds_dev_ratio_filter(keys.data_ptr(), K, 2, float(filter_strength), self.matches.data_ptr(), C.byref(nm), torch_stream()))
-        M = nm.value
+        if matcher == _lib.PIPELINE_MATCH_CROSSCHECK:
+            if K == 0:
+                return out
+            M = int(dev_crosscheck_match(self.desc[:K], self.matcher.rows, self.matcher.index_base, out=self.matches).shape[0])
+        else:
+            keys = self.matcher.knn(self.desc[:K], 2)
+            if K == 0:
+                return out
+            nm = C.c_int(0)
+            check(L.apds_dev_ratio_filter(keys.data_ptr(), K, 2, float(filter_strength), self.matches.data_ptr(), C.byref(nm), torch_stream()))
+            M = nm.value
         out["n_matches"] = M
         if M < 4:
             return out
@@ -439,8 +468,10 @@ class StreamedFramePipeline:
     pointers (train rows, their keypoints, frames), the transport choice for a sharded DB (ShardedMatcher), and results as dicts."""
 
     def __init__(self, db_rows64, db_xy, index_base=0, group=None, max_points=(1 << 18) - 1, device="cuda:0", slots=6, reserve_cus=0,
-                 n_cus=256, meta_group=None, extract_workers=None, transport="rccl", pose=None, db_kp=None, per_frame_table=None, view_capacity=None):
+                 n_cus=256, meta_group=None, extract_workers=None, transport="rccl", pose=None, db_kp=None, per_frame_table=None, view_capacity=None,
+                 matcher="ratio"):
         import os
+        self.matcher_mode = _matcher_code(matcher)   # "ratio" | "crosscheck" (apds_pipeline_set_matcher; one GPU and per-frame-view pipelines)
         self.dev = torch.device(device)
         self.per_frame_table = per_frame_table     # a KeypointTable: the train set is selected from it per frame (from_table)
         self.view_capacity = int(view_capacity) if view_capacity else 0
@@ -519,6 +550,13 @@ class StreamedFramePipeline:
         else:
             check(lib().apds_pipeline_create(C.byref(h), m.rows.data_ptr(), int(m.rows.shape[0]), m.index_base, m.handle, self.db_kp.data_ptr(), self.n_db, C.byref(p)))
         self._pipe, self._key = h, key
+        if self.matcher_mode != _lib.PIPELINE_MATCH_RATIO:     # (a pipeline that never asks runs the ratio matcher)
+            rc = lib().apds_pipeline_set_matcher(h, self.matcher_mode)
+            if rc != 0:
+                why = lib().apds_last_error().decode("utf-8", "replace")
+                self._pipe = None
+                lib().apds_pipeline_destroy(h)
+                raise _lib.ApdsError(rc, why)
         if self.pose is not None:
             pp = self.pose.params()
             if self.per_frame_table is not None:

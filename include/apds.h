@@ -598,6 +598,18 @@ typedef struct apds_db_selection {
 } apds_db_selection;
 int apds_pipeline_create_table(void** pipe, void* db, int view_capacity, const apds_pipeline_params* params);
 int apds_pipeline_submit_select(void* pipe, const void* frame, size_t stride_bytes, int on_device, const apds_db_selection* sel, int64_t* frame_id);
+/* The pipeline's matcher (opt-in; a pipeline that never calls this runs the ratio matcher as before). APDS_PIPELINE_MATCH_CROSSCHECK: the
+ * reference's second matcher, get_bruteforce_matches (lib.rs:116-126) - per frame ONE roles-swapped top-1 scan (the train rows search the
+ * frame's descriptors; the forward k = 2 scan is not launched), and the homography stage builds its matches with the cross-check instead
+ * of the ratio test: the matches of apds_dev_crosscheck_match on (frame descriptors, train set), so n_matches, the homography and the pose
+ * stage work on them. filter_strength is ignored. With the matrix-core matcher the resident expanded copy of the train rows serves the
+ * swapped scan as it is (only the frame's rows are expanded per frame). Every slot gets a buffer of one u64 per train row (per view row
+ * on a table pipeline) here; nothing grows with the number of frames.
+ * Before the first submit (else APDS_ERR_BAD_ARG); any other value APDS_ERR_BAD_ARG; APDS_PIPELINE_MATCH_CROSSCHECK on a pipeline over a
+ * shard handle APDS_ERR_NOT_IMPLEMENTED - all three before any device work. One GPU and table pipelines. */
+#define APDS_PIPELINE_MATCH_RATIO 0
+#define APDS_PIPELINE_MATCH_CROSSCHECK 1
+int apds_pipeline_set_matcher(void* pipe, int matcher);
 
 /* ---- device-resident API ------------------------------------------------------------------- */
 /* All pointers below are HIP device pointers. stream: hipStream_t or NULL (the thread's own stream).
@@ -654,6 +666,13 @@ int apds_dev_ratio_filter(const void* keys, int n_query, int k, float filter_str
 /* Cross-check: given for every train row its best query key (from apds_dev_hamming_topk with roles swapped, k=1),
  * produce matches in query order. */
 int apds_dev_cross_check(const void* train_best_keys, int64_t n_train, int n_query, void* out_matches, int* n_matches, void* stream);
+/* apds_get_bruteforce_matches on device rows (BFMatcher(NORM_HAMMING, crossCheck = true), lib.rs:116-126) in one call: every train row
+ * finds its nearest query (ties to the lower query index), every query keeps the closest train row that chose it (ties to the lower
+ * train index), queries nobody chose are dropped. out_matches: room for n_query 16-byte matches, written in query order with
+ * train_idx = row + index_base; *n_matches (host) = their count. An empty side gives zero matches and APDS_OK; n_train above INT_MAX is
+ * APDS_ERR_ASSERT (the train rows are the searching side of the scan). Synchronises the stream once, for the count. */
+int apds_dev_crosscheck_match(const void* query_rows64, int n_query, const void* train_rows64, int64_t n_train, uint32_t index_base, void* out_matches,
+                              int* n_matches, void* stream);
 
 /* AKAZE on a device image. Results stay on the device: kps (capacity x 28 B), desc64 (capacity x 64 B).
  * Returns the keypoint count in *n (host). capacity >= min(max_points, APDS_MAX_POINTS). */

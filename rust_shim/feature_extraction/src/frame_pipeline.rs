@@ -36,6 +36,14 @@ pub struct FramePose {
     pub tvec: [f64; 3],
 }
 
+/// `apds_pipeline_set_matcher`'s values (`APDS_PIPELINE_MATCH_RATIO`, `APDS_PIPELINE_MATCH_CROSSCHECK`)
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+#[repr(i32)]
+pub enum Matcher {
+    Ratio = 0,
+    CrossCheck = 1,
+}
+
 pub struct FramePipeline {
     pipe: *mut c_void,
     stride: usize,
@@ -145,6 +153,18 @@ impl FramePipeline {
             db_xyz_dev, origin, camera_intrinsic, method: method.unwrap_or(APDS_SOLVEPNP_EPNP), iter_count, reproj_thres, confidence,
         };
         let rc = unsafe { apds_sys::apds_pipeline_enable_pose(self.pipe, &params) };
+        if rc != 0 {
+            return Err(err(rc));
+        }
+        Ok(())
+    }
+
+    /// Chooses the pipeline's matcher; before the first `submit`. `Matcher::Ratio` (the default of a pipeline that never calls this) is
+    /// `get_knn_matches` with k = 2 and the Lowe ratio (lib.rs:94-114); `Matcher::CrossCheck` is `get_bruteforce_matches` (lib.rs:116-126,
+    /// `BFMatcher(NORM_HAMMING, crossCheck = true)`): `filter_strength` is then ignored, and the homography and the pose stage work on the
+    /// cross-checked matches. Not built over a shard handle (`APDS_ERR_NOT_IMPLEMENTED`).
+    pub fn set_matcher(&self, matcher: Matcher) -> Result<(), String> {
+        let rc = unsafe { apds_sys::apds_pipeline_set_matcher(self.pipe, matcher as i32) };
         if rc != 0 {
             return Err(err(rc));
         }
