@@ -43,9 +43,10 @@ int apds_dev_find_homography(const void* src, const void* dst, int n, int method
                              void* mask_dev, void* stream) {
     APDS_RANGE("apds_dev_find_homography");
     return guarded([&] {
-        ctx().ws_reset();
+        hipStream_t s = pick_stream(stream);
+        ctx().ws_reset(s);
         const int found = find_homography_device(static_cast<const float*>(src), static_cast<const float*>(dst), n, method, thr, max_iters, confidence, H,
-                                                 static_cast<uint8_t*>(mask_dev), pick_stream(stream));
+                                                 static_cast<uint8_t*>(mask_dev), s);
         if (!found) fail(APDS_ERR_EMPTY, "no homography found (empty model)");
     });
 }

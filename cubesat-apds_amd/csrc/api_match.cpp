@@ -185,8 +185,8 @@ int apds_dev_hamming_topk(const void* q, int nq, const void* t, int64_t nt, uint
     APDS_RANGE("apds_dev_hamming_topk");
     return guarded([&] {
         APDS_REQUIRE(nq >= 0 && nt >= 0, APDS_ERR_ASSERT, "negative row count");
-        ctx().ws_reset();
-        hamming_topk_device(q, nq, t, nt, index_base, k, static_cast<uint64_t*>(out_keys), pick_stream(stream));
+        QueuedWorkspaceCall call(pick_stream(stream));
+        hamming_topk_device(q, nq, t, nt, index_base, k, static_cast<uint64_t*>(out_keys), call.s);
     });
 }
 
@@ -194,8 +194,8 @@ int apds_dev_hamming_topk_backend(const void* q, int nq, const void* t, int64_t 
     APDS_RANGE("apds_dev_hamming_topk_backend");
     return guarded([&] {
         APDS_REQUIRE(nq >= 0 && nt >= 0, APDS_ERR_ASSERT, "negative row count");
-        ctx().ws_reset();
-        hamming_topk_device(q, nq, t, nt, index_base, k, static_cast<uint64_t*>(out_keys), pick_stream(stream), backend);
+        QueuedWorkspaceCall call(pick_stream(stream));
+        hamming_topk_device(q, nq, t, nt, index_base, k, static_cast<uint64_t*>(out_keys), call.s, backend);
     });
 }
 
@@ -256,16 +256,18 @@ int apds_dev_ratio_filter(const void* keys, int nq, int k, float fs, void* out_m
     return guarded([&] {
         APDS_REQUIRE(k >= 2, APDS_ERR_OUT_OF_RANGE, "ratio test needs two neighbours");
         APDS_REQUIRE(n_matches, APDS_ERR_BAD_ARG, "null output");
-        ctx().ws_reset();
-        *n_matches = ratio_filter_device(static_cast<const uint64_t*>(keys), nq, k, fs, static_cast<apds_dmatch*>(out_matches), pick_stream(stream));
+        hipStream_t s = pick_stream(stream);
+        ctx().ws_reset(s);
+        *n_matches = ratio_filter_device(static_cast<const uint64_t*>(keys), nq, k, fs, static_cast<apds_dmatch*>(out_matches), s);
     });
 }
 
 int apds_dev_cross_check(const void* train_best, int64_t n_train, int nq, void* out_matches, int* n_matches, void* stream) {
     return guarded([&] {
         APDS_REQUIRE(n_matches, APDS_ERR_BAD_ARG, "null output");
-        ctx().ws_reset();
-        *n_matches = cross_check_device(static_cast<const uint64_t*>(train_best), n_train, nq, static_cast<apds_dmatch*>(out_matches), pick_stream(stream));
+        hipStream_t s = pick_stream(stream);
+        ctx().ws_reset(s);
+        *n_matches = cross_check_device(static_cast<const uint64_t*>(train_best), n_train, nq, static_cast<apds_dmatch*>(out_matches), s);
     });
 }
 
@@ -282,8 +284,8 @@ int apds_dev_crosscheck_match(const void* q, int nq, const void* t, int64_t nt, 
         if (nq == 0 || nt == 0) return;
         APDS_REQUIRE(q && t && out_matches, APDS_ERR_BAD_ARG, "null argument");
         ThreadCtx& c = ctx();
-        c.ws_reset();
         hipStream_t s = pick_stream(stream);
+        c.ws_reset(s);
         uint64_t* tbest = c.alloc_n<uint64_t>((size_t)nt);
         hamming_topk_device(t, (int)nt, q, nq, 0, 1, tbest, s);
         *n_matches = cross_check_base_device(tbest, nt, nq, index_base, static_cast<apds_dmatch*>(out_matches), s);
@@ -295,8 +297,8 @@ int apds_dev_points_from_matches(const void* kp1, int n1, const void* kp2, int n
     return guarded([&] {
         if (nm <= 0) return;
         ThreadCtx& c = ctx();
-        c.ws_reset();
         hipStream_t s = pick_stream(stream);
+        c.ws_reset(s);
         int* err = c.alloc_n<int>(1);
         HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int), s));
         points_from_matches_device(static_cast<const apds_keypoint*>(kp1), n1, static_cast<const apds_keypoint*>(kp2), n2,

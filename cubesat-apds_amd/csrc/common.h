@@ -82,17 +82,22 @@ struct ThreadCtx {
     void drop_side();
     hipEvent_t fork_event(size_t i);            // i-th reusable event (no timing)
 
-    // A call that hands its result count to the host before its last kernels are done (akaze: the count is final ~0.3 ms before the
-    // descriptors) leaves a TAIL on its stream: the workspace it used is still being read. The next call of this thread re-uses that memory,
-    // so ws_reset() waits for the tail first - unless the next call goes to the same stream, whose order already protects it.
+    // A call that returns with kernels queued that use the workspace (the asynchronous apds_dev_* matchers; akaze, whose count is final
+    // ~0.3 ms before the descriptors) leaves a TAIL on its stream: the workspace is still being read and written. The next call of this
+    // thread re-uses that memory from offset 0, so ws_reset() orders the coming call's stream behind the tail (hipStreamWaitEvent: the host
+    // does not block) - unless the call goes to the same stream, whose order already protects it. The rule, and every entry's class:
+    // DESIGN.md section 1 "Workspace and streams".
     hipEvent_t tail_event = nullptr, count_event = nullptr;
     hipStream_t tail_stream = nullptr;
     bool tail_pending = false;
     void mark_tail(hipStream_t s);   // everything queued on s so far is this thread's tail
+    void mark_tail_noexcept(hipStream_t s) noexcept;   // the same for destructors: synchronises s where the event cannot be recorded
 
     void ensure();
     void* alloc(size_t bytes);   // valid until the next ws_reset()
-    void ws_reset(hipStream_t for_stream = nullptr);   // frees all but one slab sized to the high-water mark; for_stream: the stream the coming call uses, if known
+    // frees all but one slab sized to the high-water mark; for_stream: the stream ALL of the coming call's workspace users go to (null: the
+    // thread's own stream, where the host-pointer entries run)
+    void ws_reset(hipStream_t for_stream = nullptr);
     template <class T>
     T* alloc_n(size_t n) { return static_cast<T*>(alloc(n * sizeof(T))); }
 };
@@ -110,6 +115,18 @@ void cache_side_stream(int device, hipStream_t st);
 unsigned stream_event_flags();   // flags for events that only order GPU streams of one device
 
 inline hipStream_t pick_stream(void* s) { return s ? static_cast<hipStream_t>(s) : ctx().stream; }
+
+// The frame of an entry that RETURNS WITH KERNELS QUEUED on s that use the thread's workspace: the workspace is reset with s ordered behind
+// the thread's previous tail, and what the entry has queued when it leaves - with a result or with an error - is the thread's new tail
+// (one event record per call). Entries that synchronise s before they return need ws_reset(s) only.
+struct QueuedWorkspaceCall {
+    ThreadCtx& c;
+    hipStream_t s;
+    explicit QueuedWorkspaceCall(hipStream_t st) : c(ctx()), s(st) { c.ws_reset(s); }
+    ~QueuedWorkspaceCall() { c.mark_tail_noexcept(s); }
+    QueuedWorkspaceCall(const QueuedWorkspaceCall&) = delete;
+    QueuedWorkspaceCall& operator=(const QueuedWorkspaceCall&) = delete;
+};
 
 // RAII: time one named kernel with hipEvents on the stream it is launched on (only when enabled).
 struct KernelTimer {

@@ -329,8 +329,8 @@ int apds_dev_l2_topk_ex(const void* q, int nq, const void* t, int64_t nt, int di
     return guarded([&] {
         APDS_REQUIRE(nq >= 0 && nt >= 0, APDS_ERR_ASSERT, "negative row count");
         APDS_REQUIRE(mode == APDS_L2_EXACT || mode == APDS_L2_SCREEN, APDS_ERR_BAD_ARG, "mode must be APDS_L2_EXACT or APDS_L2_SCREEN");
-        ctx().ws_reset();
-        hipStream_t s = pick_stream(stream);
+        QueuedWorkspaceCall call(pick_stream(stream));   // (the screen's re-rank and the exact kernel are queued on return)
+        hipStream_t s = call.s;
         if (mode_used) *mode_used = APDS_L2_EXACT;
         if (candidates_per_query) *candidates_per_query = 0;
         if (mode == APDS_L2_SCREEN && l2_topk_screen_device(static_cast<const float*>(q), nq, static_cast<const float*>(t), nt, dim, index_base, k,
@@ -338,7 +338,7 @@ int apds_dev_l2_topk_ex(const void* q, int nq, const void* t, int64_t nt, int di
             if (mode_used) *mode_used = APDS_L2_SCREEN;
             return;
         }
-        ctx().ws_reset();   // the screen does not apply (shape, alignment, candidate overflow): the exact kernel
+        ctx().ws_reset(s);   // the screen does not apply (shape, alignment, candidate overflow): the exact kernel
         l2_topk_device(static_cast<const float*>(q), nq, static_cast<const float*>(t), nt, dim, index_base, k, static_cast<uint64_t*>(out_keys), s);
     });
 }
@@ -346,9 +346,8 @@ int apds_dev_l2_topk_ex(const void* q, int nq, const void* t, int64_t nt, int di
 int apds_dev_l2_topk(const void* q, int nq, const void* t, int64_t nt, int dim, uint32_t index_base, int k, void* out_keys, void* stream) {
     return guarded([&] {
         APDS_REQUIRE(nq >= 0 && nt >= 0, APDS_ERR_ASSERT, "negative row count");
-        ctx().ws_reset();
-        l2_topk_device(static_cast<const float*>(q), nq, static_cast<const float*>(t), nt, dim, index_base, k, static_cast<uint64_t*>(out_keys),
-                       pick_stream(stream));
+        QueuedWorkspaceCall call(pick_stream(stream));
+        l2_topk_device(static_cast<const float*>(q), nq, static_cast<const float*>(t), nt, dim, index_base, k, static_cast<uint64_t*>(out_keys), call.s);
     });
 }
 

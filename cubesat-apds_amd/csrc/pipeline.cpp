@@ -354,14 +354,14 @@ struct Pipeline {
                 HIP_CHECK(hipEventRecord(s->ev_mstart, st_match));
                 if (K > 0 && crosscheck && db_expanded) {   // the resident expanded copy as the searching side: only the frame's rows are expanded
                     PIPE_OK(guarded([&] {
-                        ctx().ws_reset();
+                        QueuedWorkspaceCall call(st_match);
                         hamming_mfma_swapped_top1_device(s->desc, K, db_expanded, db_plain_pc, s->train_best, st_match);
                     }));
                 } else if (K > 0 && crosscheck) {   // (vector-ALU matcher: the swapped scan directly)
                     PIPE_OK(apds_dev_hamming_topk(db_rows, (int)n_rows, s->desc, K, 0, 1, s->train_best, st_match));
                 } else if (K > 0 && db_expanded) {   // the matrix-core matcher on the DB's expanded copy
                     PIPE_OK(guarded([&] {
-                        ctx().ws_reset();   // (as every entry point does: the scan's scratch is this thread's workspace from its start; one stream orders the frames)
+                        QueuedWorkspaceCall call(st_match);   // (as apds_dev_hamming_topk does: the scan's scratch is this thread's workspace, and it is queued on return)
                         hamming_mfma_topk_train_device(s->desc, K, db_expanded, index_base, 2, static_cast<uint64_t*>(s->keys), st_match);
                     }));
                 } else if (K > 0) {
@@ -476,7 +476,7 @@ struct Pipeline {
                 if (matched && matcher == APDS_PIPELINE_MATCH_CROSSCHECK) {
                     // per query the closest train row that chose it, in query order; train_idx = row + index_base (a view: its position)
                     PIPE_OK(guarded([&] {
-                        ctx().ws_reset();
+                        ctx().ws_reset(st);
                         M = cross_check_base_device(s->train_best, table ? (long long)s->n_view : (long long)n_rows, s->K, table ? 0u : index_base, s->matches, st);
                     }));
                 } else if (matched) {

@@ -274,11 +274,26 @@ void ThreadCtx::mark_tail(hipStream_t s) {
     tail_pending = true;
 }
 
-void ThreadCtx::ws_reset(hipStream_t for_stream) {
-    if (tail_pending && !(for_stream && for_stream == tail_stream)) {   // (same stream: its order protects the workspace, the tail stays pending for others)
-        HIP_CHECK(hipEventSynchronize(tail_event));
-        tail_pending = false;
+void ThreadCtx::mark_tail_noexcept(hipStream_t s) noexcept {
+    if ((tail_event || hipEventCreateWithFlags(&tail_event, hipEventDisableTiming) == hipSuccess) && hipEventRecord(tail_event, s) == hipSuccess) {
+        tail_stream = s;
+        tail_pending = true;
+        return;
     }
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(s);   // no event: nothing of the call stays queued instead
+    (void)hipGetLastError();
+}
+
+void ThreadCtx::ws_reset(hipStream_t for_stream) {
+    if (!for_stream) for_stream = stream;   // (the host-pointer entries: all their work goes to the thread's own stream)
+    // same stream: its order protects the workspace. Another one: it waits for the tail on the device, the host does not; the tail stays
+    // pending for a third stream until the coming call leaves its own (a call that leaves none has synchronised for_stream, and the tail with it).
+    // tail_pending is deliberately never cleared here: once a tail has completed, a later change of stream costs one wait on a completed
+    // event (no device work, no host block), which is cheaper than asking the event. Not covered: an entry of the synchronising class that
+    // throws between queueing work and its synchronisation leaves that work unordered against the thread's next call on another stream
+    // (only QueuedWorkspaceCall marks a tail on the error path); such errors are HIP failures, after which the workspace's contents are moot.
+    if (tail_pending && for_stream != tail_stream) HIP_CHECK(hipStreamWaitEvent(for_stream, tail_event, 0));
     if (slabs.size() > 1) {
         // one slab for everything the last call asked for (+ 1/16), not the sum of the slabs it happened to open
         const size_t total = call_bytes + call_bytes / 16 + (size_t(1) << 20);

@@ -73,7 +73,7 @@ struct HipDevice final : Device {
     void topk(const void* q, int nq, const void* rows, int64_t n_rows, uint32_t base, int k, void* out, void* s) override {
         // the scan's scratch is the calling thread's workspace, from its start: scans issued by one thread must be ordered on the GPU
         // (one stream, or events), exactly as for apds_dev_hamming_topk
-        ctx().ws_reset();
+        QueuedWorkspaceCall call(st(s));   // (returns with the scan queued: the thread's tail)
         if (k <= std::max(2, config().match_mfma_kmax) && config().match_mfma && nq > 0 && n_rows > 0) {   // (APDS_MATCH_MFMA_KMAX: hamming_topk_device's routing)
             void* train = nullptr;
             {

@@ -615,7 +615,12 @@ int apds_pipeline_set_matcher(void* pipe, int matcher);
 /* All pointers below are HIP device pointers. stream: hipStream_t or NULL (the thread's own stream).
  * Calls are asynchronous on that stream unless they return a count to the host; apds_dev_akaze_extract(_batch) returns as soon as the
  * count is known, with the orientation / descriptor kernels still queued on the stream: consumers order themselves on that stream (or an
- * event recorded on it), as with any asynchronous call. */
+ * event recorded on it), as with any asynchronous call.
+ * Scratch: the matchers, the filters, the estimators and the extraction keep their scratch in the CALLING THREAD's workspace, which every
+ * such call re-uses from its start. One host thread may nevertheless issue them on different streams without synchronising in between:
+ * a call that returns with work queued leaves an event behind it, and the thread's next call makes its own stream wait for that event on
+ * the device when it is another stream (no host block; nothing at all while the thread stays on one stream). The outputs are not covered:
+ * they are the caller's buffers, ordered by the caller. A stream must outlive the work queued on it. */
 
 /* Pack n rows of desc_bytes (<= 64) bytes into 64-byte rows (zero padded). */
 int apds_dev_pack_descriptors(const void* src_rows, int64_t n, int desc_bytes, int64_t src_stride, void* dst_rows64, void* stream);

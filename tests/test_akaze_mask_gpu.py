@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import akaze_mask_cases as mc
+from stream_handover import hand_over
 
 pytestmark = pytest.mark.gpu
 
@@ -65,6 +66,7 @@ def _dev_single(gpu_pkg, dev, tile, mask=None, max_points=4096, capacity=4096):
     desc = torch.zeros((capacity, 64), dtype=torch.uint8, device=d)
     n = C.c_int(-1)
     ch = 1 if tile.ndim == 2 else tile.shape[2]
+    hand_over()
     rc = L.apds_dev_akaze_extract_masked(t.data_ptr(), tile.shape[0], tile.shape[1], ch, tile.shape[1] * ch, mptr, mstride, max_points, kps.data_ptr(),
                                          desc.data_ptr(), capacity, C.byref(n), None)
     torch.cuda.synchronize()
@@ -175,6 +177,7 @@ def test_strided_mask(gpu_pkg, dev, case):
     t = torch.from_numpy(np.array(tile)).to(d)
     out_k = torch.zeros((64, 7), dtype=torch.float32, device=d)
     out_d = torch.zeros((64, 64), dtype=torch.uint8, device=d)
+    hand_over()
     rc = L.apds_dev_akaze_extract_masked(t.data_ptr(), H, W, 4, W * 4, m.data_ptr(), W - 1, 64, out_k.data_ptr(), out_d.data_ptr(), 64, C.byref(n), None)
     assert rc == gpu_pkg._lib.ERR_ASSERT
 
@@ -239,6 +242,7 @@ def test_batch_masks(gpu_pkg, dev, case):
     kps = torch.zeros((3, cap, 7), dtype=torch.float32, device=d)
     desc = torch.zeros((3, cap, 64), dtype=torch.uint8, device=d)
     counts = (C.c_int * 3)()
+    hand_over()
     check(L.apds_dev_akaze_extract_batch_masked(t.data_ptr(), 3, H * W * 4, H, W, 4, W * 4, tm.data_ptr(), W, 0, cap, kps.data_ptr(), desc.data_ptr(), cap, counts,
                                                 None))
     torch.cuda.synchronize()

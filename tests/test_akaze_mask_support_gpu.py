@@ -18,6 +18,7 @@ import pytest
 
 import akaze_mask_cases as mc
 import akaze_mask_support_cases as sc
+from stream_handover import hand_over
 
 pytestmark = pytest.mark.gpu
 
@@ -67,6 +68,7 @@ def _sat(dev, plane_bytes, first, rows, cols, row_stride, pix_stride):
     src = torch.from_numpy(plane_bytes).to(d)
     n = (rows + 1) * (cols + 1)
     out = torch.full((n + 128,), 0x5A5A5A5A, dtype=torch.int32, device=d)
+    hand_over()
     check(L.apds_dev_mask_zero_sat(src.data_ptr() + first, rows, cols, row_stride, pix_stride, out.data_ptr() + 64 * 4, None))
     torch.cuda.synchronize()
     got = out.cpu().numpy().view(np.uint32)
@@ -137,6 +139,7 @@ def _dev_single(gpu_pkg, dev, tile, mask, support, max_points=4096, capacity=409
     desc = torch.zeros((capacity, 64), dtype=torch.uint8, device=d)
     n = C.c_int(-1)
     ch = 1 if tile.ndim == 2 else tile.shape[2]
+    hand_over()
     check(L.apds_dev_akaze_extract_masked_support(t.data_ptr(), tile.shape[0], tile.shape[1], ch, tile.shape[1] * ch, None if m is None else m.data_ptr(),
                                                   tile.shape[1], support, max_points, kps.data_ptr(), desc.data_ptr(), capacity, C.byref(n), None))
     torch.cuda.synchronize()
@@ -244,6 +247,7 @@ def test_batches(gpu_pkg, dev, case):
     counts = (C.c_int * 3)()
     # device: one mask shared by all images (image stride 0: one table)
     tm = torch.from_numpy(hole).to(d)
+    hand_over()
     check(L.apds_dev_akaze_extract_batch_masked_support(t.data_ptr(), 3, H * W * 4, H, W, 4, W * 4, tm.data_ptr(), W, 0, 15, cap, kps.data_ptr(), desc.data_ptr(),
                                                         cap, counts, None))
     torch.cuda.synchronize()

@@ -5,6 +5,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from stream_handover import hand_over
+
 pytestmark = pytest.mark.gpu
 
 
@@ -21,6 +23,7 @@ def test_pack_descriptors_strided_rows(gpu_pkg, dev):
         src = rng.integers(0, 256, (n, stride), dtype=np.uint8)
         t = torch.from_numpy(src).to(d)
         out = torch.full((n, 64), 0xAB, dtype=torch.uint8, device=d)
+        hand_over()
         check(L.apds_dev_pack_descriptors(t.data_ptr(), n, nbytes, stride, out.data_ptr(), None))
         torch.cuda.synchronize()
         got = out.cpu().numpy()
@@ -61,6 +64,7 @@ def test_band_merger_on_device_equals_host_entry(gpu_pkg, dev):
         check(L.apds_band_merger(bands[0].ctypes.data, bands[1].ctypes.data, bands[2].ctypes.data, n, mm.ctypes.data, bgra, host.ctypes.data))
         tb = [torch.from_numpy(b).to(d) for b in bands]
         out = torch.zeros((n, 4), dtype=torch.uint8, device=d)
+        hand_over()
         check(L.apds_dev_band_merger(tb[0].data_ptr(), tb[1].data_ptr(), tb[2].data_ptr(), n, mm.ctypes.data, bgra, out.data_ptr(), None))
         torch.cuda.synchronize()
         assert np.array_equal(out.cpu().numpy(), host)
@@ -75,10 +79,12 @@ def test_batched_device_extraction_equals_single_calls(gpu_pkg, dev):
     kps = torch.zeros((B, cap, 7), dtype=torch.float32, device=d)
     desc = torch.zeros((B, cap, 64), dtype=torch.uint8, device=d)
     counts = (C.c_int * B)()
+    hand_over()
     check(L.apds_dev_akaze_extract_batch(t.data_ptr(), B, T * T * 4, T, T, 4, T * 4, cap, kps.data_ptr(), desc.data_ptr(), cap, counts, None))
     torch.cuda.synchronize()
     k1 = torch.zeros((cap, 7), dtype=torch.float32, device=d)
     d1 = torch.zeros((cap, 64), dtype=torch.uint8, device=d)
+    hand_over()
     for i in range(B):
         n = C.c_int(0)
         check(L.apds_dev_akaze_extract(t[i].data_ptr(), T, T, 4, T * 4, cap, k1.data_ptr(), d1.data_ptr(), cap, C.byref(n), None))
@@ -137,6 +143,7 @@ def test_merge_topk_equals_sorted_concatenation(dev, k, parts):
     assert (keys[:, 17] == empty).all() and (keys[:, :, k - 1] == empty).any() and len(real) > nq   # one query without rows, short lists, rows
     tp = torch.from_numpy(keys.view(np.int64)).to(d)
     out = torch.zeros((nq, k), dtype=torch.int64, device=d)
+    hand_over()
     check(L.apds_dev_merge_topk(tp.data_ptr(), parts, nq, k, out.data_ptr(), None))
     torch.cuda.synchronize()
     assert np.array_equal(out.cpu().numpy().view(np.uint64), want)
