@@ -47,6 +47,7 @@ SYMBOLS = [
     "apds_db_insert_dev", "apds_db_insert_batch_dev", "apds_mosaic_tiles_to_db", "apds_db_world_coordinates", "apds_db_table",
     "apds_db_view_create", "apds_db_view_destroy", "apds_db_view_select", "apds_db_view_pointers", "apds_pipeline_create_table", "apds_pipeline_submit_select",
     "apds_dev_crosscheck_match", "apds_pipeline_set_matcher",
+    "apds_db_ids", "apds_db_read_keypoint_from_id", "apds_db_delete_where", "apds_db_delete_ids",
 ]
 
 RESAMPLE_NEAREST, RESAMPLE_LANCZOS = 0, 1
@@ -299,6 +300,10 @@ def lib():
             "apds_pipeline_submit_select": (i, [vp, vp, sz, i, C.POINTER(DbSelection), C.POINTER(i64)]),
             "apds_dev_crosscheck_match": (i, [vp, i, vp, i64, u32, vp, ip, vp]),
             "apds_pipeline_set_matcher": (i, [vp, i]),
+            "apds_db_ids": (i, [vp, pp]),
+            "apds_db_read_keypoint_from_id": (i, [vp, i, vp, vp, ip, C.POINTER(i64)]),
+            "apds_db_delete_where": (i, [vp, i, i, f, f, f, f, C.POINTER(i64)]),
+            "apds_db_delete_ids": (i, [vp, vp, i, C.POINTER(i64)]),
         }
         for name, (rt, at) in sig.items():
             fn = getattr(L, name)

@@ -9,8 +9,10 @@
 // Selection = predicate flags -> ordered compaction of u64 keys (~response_bits << 32 | row) -> radix select of the
 // LIMIT-th key when more rows qualify -> bitonic sort of the survivors -> row gather. Ties in response are ordered by
 // insertion order (row id), which SQL leaves unspecified.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 
 #include "kernels.h"
 #include "topk_keys.h"
@@ -23,6 +25,9 @@ struct KeypointTable {
     float *x = nullptr, *y = nullptr, *size = nullptr, *angle = nullptr, *response = nullptr;
     int *octave = nullptr, *class_id = nullptr, *image_id = nullptr, *lod = nullptr;
     uint8_t* desc64 = nullptr;
+    // the reference's SERIAL column: the id of every row, and the next id to give. Ids are never reused, so they ascend with the row.
+    int* id = nullptr;
+    int64_t next_id = 1;
     // last selection (device)
     int64_t view_n = 0, view_cap = 0;
     int* view_rows = nullptr;
@@ -35,18 +40,22 @@ struct KeypointTable {
     int64_t all_kps_rows = 0;
     double* xyz = nullptr;
     int64_t xyz_rows = -1;
+    // staging buffer of a delete's compaction (one chunk of rows, every moved column), allocated on the first delete that moves a row
+    uint32_t* stage = nullptr;
+    int stage_rows = 0;
 };
 
 struct TableColumns {
     float *x, *y, *size, *angle, *response;
     int *octave, *class_id, *image_id, *lod;
     uint32_t* desc64;
+    int* id;
 };
 
 // The keypoint columns of table row r from one extracted keypoint: the ONE copy of the coordinate lift, whichever side the row comes from.
 // main.rs:299-300: x * 2^lod + (column * tile_w * 2^lod) as f32 (scale = 2^lod; xoff, yoff: the u64 products rounded once to f32)
 __device__ __forceinline__ void store_keypoint_columns(const TableColumns& c, long long r, const apds_keypoint& k, float scale, float xoff, float yoff,
-                                                       int image_id, int lod) {
+                                                       int image_id, int lod, int id) {
     c.x[r] = k.x * scale + xoff;
     c.y[r] = k.y * scale + yoff;
     c.size[r] = k.size;
@@ -56,10 +65,11 @@ __device__ __forceinline__ void store_keypoint_columns(const TableColumns& c, lo
     c.class_id[r] = k.class_id;
     c.image_id[r] = image_id;
     c.lod[r] = lod;
+    c.id[r] = id;
 }
 
 __global__ void table_insert_kernel(const apds_keypoint* __restrict__ kps, const uint8_t* __restrict__ desc61, int n, int image_id, int lod,
-                                    float scale, float xoff, float yoff, long long base, TableColumns c) {
+                                    float scale, float xoff, float yoff, long long base, int first_id, TableColumns c) {
     APDS_RAISE_WAVE_PRIORITY();
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (long long)n * 16) return;
@@ -69,7 +79,7 @@ __global__ void table_insert_kernel(const apds_keypoint* __restrict__ kps, const
     for (int b = 0; b < 4; b++)
         if (w * 4 + b < 61) v |= (uint32_t)desc61[(size_t)i * 61 + w * 4 + b] << (8 * b);
     c.desc64[(base + i) * 16 + w] = v;
-    if (w == 0) store_keypoint_columns(c, base + i, kps[i], scale, xoff, yoff, image_id, lod);
+    if (w == 0) store_keypoint_columns(c, base + i, kps[i], scale, xoff, yoff, image_id, lod, first_id + i);
 }
 
 // The same rows from the device buffers an extraction has written (28-byte keypoints, 64-byte descriptor rows; tile i at i * capacity
@@ -79,7 +89,7 @@ __global__ void table_insert_kernel(const apds_keypoint* __restrict__ kps, const
 // not trusted: word 15 keeps byte 60 alone.
 __global__ __launch_bounds__(256) void table_insert_dev_kernel(const apds_keypoint* __restrict__ kps, const uint32_t* __restrict__ desc64_src, int n_tiles,
                                                                int capacity, const int* __restrict__ tile_offsets, const float2* __restrict__ tile_xy_off,
-                                                               int first_image_id, int lod, float scale, long long base, TableColumns c) {
+                                                               int first_image_id, int lod, float scale, long long base, int first_id, TableColumns c) {
     APDS_RAISE_WAVE_PRIORITY();
     extern __shared__ int offs[];   // n_tiles + 1
     for (int i = threadIdx.x; i <= n_tiles; i += blockDim.x) offs[i] = tile_offsets[i];
@@ -99,7 +109,7 @@ __global__ __launch_bounds__(256) void table_insert_dev_kernel(const apds_keypoi
     c.desc64[(base + r) * 16 + w] = v;
     if (w == 0) {
         const float2 o = tile_xy_off[lo];
-        store_keypoint_columns(c, base + r, kps[src], scale, o.x, o.y, first_image_id + lo, lod);
+        store_keypoint_columns(c, base + r, kps[src], scale, o.x, o.y, first_image_id + lo, lod, first_id + r);
     }
 }
 
@@ -453,6 +463,156 @@ __global__ __launch_bounds__(256) void view_gather_kernel(const uint64_t* __rest
     }
 }
 
+// ---- ids and deletes (keypointdb.rs:28-36, 92-97): stable ordered compaction of the whole table under a delete predicate ---------------
+// Victim flags and per-block victim counts -> view_offsets_kernel -> the survivors move down in row order, chunk by chunk: a chunk's
+// survivors are gathered into the table's staging buffer by one launch and copied to their destination by the next one (DESIGN §7c-4
+// has the argument why no launch reads what another workgroup of the same launch writes).
+
+// the row that holds `id`, or -1: ids ascend strictly with the row
+__device__ __forceinline__ long long find_id_row(const int* __restrict__ ids, long long n, int id) {
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (ids[mid] < id) lo = mid + 1;
+        else hi = mid;
+    }
+    return (lo < n && ids[lo] == id) ? lo : -1;
+}
+
+__global__ void table_ids_of_rows_kernel(const int* __restrict__ ids, const int* __restrict__ rows, int m, int* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < m) out[i] = ids[rows[i]];
+}
+
+struct FoundRow {
+    long long row;   // -1: no row has the id
+    apds_keypoint kp;
+    int image_id;
+    uint32_t desc[16];
+};
+
+// one wave: lane 0 searches the id column, 16 lanes copy the descriptor row
+__global__ __launch_bounds__(64) void table_read_id_kernel(TableColumns c, long long n, int id, FoundRow* __restrict__ out) {
+    __shared__ long long found;
+    if (threadIdx.x == 0) found = find_id_row(c.id, n, id);
+    __syncthreads();
+    const long long r = found;
+    if (threadIdx.x == 0) out->row = r;
+    if (r < 0) return;
+    if (threadIdx.x < 16) out->desc[threadIdx.x] = c.desc64[r * 16 + threadIdx.x];
+    if (threadIdx.x == 0) {
+        apds_keypoint k;
+        k.x = c.x[r]; k.y = c.y[r]; k.size = c.size[r]; k.angle = c.angle[r]; k.response = c.response[r];
+        k.octave = c.octave[r]; k.class_id = c.class_id[r];
+        out->kp = k;
+        out->image_id = c.image_id[r];
+    }
+}
+
+// a thread per entry of the caller's list: the row of that id, if any, is flagged (a duplicate flags it again, an unknown id nothing)
+__global__ void delete_mark_ids_kernel(const int* __restrict__ ids, long long n, const int* __restrict__ list, int m, uint8_t* __restrict__ flags) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const long long r = find_id_row(ids, n, list[j]);
+    if (r >= 0) flags[r] = 1;
+}
+
+static constexpr int DELETE_MODE_FLAGGED = 3;   // SelectArgs.mode of a delete whose victim flags are already written (the id list)
+
+// victims per block of TB rows and the first victim row of the table (*first_row starts at INT_MAX); modes 0..2 evaluate the select
+// path's predicate and write the flags the gather reads
+__global__ __launch_bounds__(TB) void delete_count_kernel(TableColumns c, int n, SelectArgs a, uint8_t* __restrict__ flags, int* __restrict__ block_counts,
+                                                          int* __restrict__ first_row) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const long long i = (long long)blockIdx.x * TB + threadIdx.x;
+    int f = 0;
+    if (i < n) {
+        if (a.mode == DELETE_MODE_FLAGGED) f = flags[i] != 0;
+        else flags[i] = f = view_row_selected(c, i, a);
+    }
+    int total;
+    const int pos = view_block_rank(f, &total);
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
+    if (f && pos == 0) atomicMin(first_row, (int)i);
+}
+
+static constexpr int DELETE_CHUNK_ROWS = 1 << 20;   // rows one gather / scatter pair moves: a multiple of TB
+static constexpr int MOVE_COLUMNS = 10;             // x, y, size, angle, response, octave, class_id, image_id, lod, id: one dword each
+static constexpr int STAGE_ROW_DWORDS = MOVE_COLUMNS + 16 + 6;   // + the descriptor row + the world point: 128 bytes
+
+struct MoveColumns {
+    uint32_t* col[MOVE_COLUMNS];
+    uint32_t* desc;   // 16 dwords per row
+    uint32_t* xyz;    // 6 dwords per row, or null (no valid world points: nothing to move)
+};
+// the staging buffer: MOVE_COLUMNS planes of `rows` dwords, then rows x 16 descriptor dwords, then rows x 6 world point dwords
+struct StageColumns {
+    uint32_t* base;
+    int rows;
+    __device__ __forceinline__ uint32_t* col(int k) const { return base + (size_t)k * rows; }
+    __device__ __forceinline__ uint32_t* desc() const { return base + (size_t)MOVE_COLUMNS * rows; }
+    __device__ __forceinline__ uint32_t* xyz() const { return base + (size_t)(MOVE_COLUMNS + 16) * rows; }
+};
+
+// Chunk = blocks [block0, block0 + gridDim.x) of TB rows. Its survivors go to consecutive staging slots in row order: slot = survivors of
+// the chunk before the row. Rows below first_row (all survivors, the first slots of the first chunk) stay where they are: not read here,
+// their slots not written, and skipped by the scatter. Reads the table, writes the staging buffer only.
+__global__ __launch_bounds__(TB) void delete_gather_kernel(MoveColumns m, int n, const uint8_t* __restrict__ flags, const int* __restrict__ victim_offsets,
+                                                           int block0, int first_row, StageColumns st) {
+    APDS_RAISE_WAVE_PRIORITY();
+    __shared__ unsigned short src_of[TB];   // the thread (row of the block) of the block's pos-th survivor
+    const int b = block0 + blockIdx.x;
+    const long long r0 = (long long)b * TB, r = r0 + threadIdx.x;
+    const int f = r < n && !flags[r];
+    int total;
+    const int pos = view_block_rank(f, &total);
+    const size_t before = (size_t)blockIdx.x * TB - (size_t)(victim_offsets[b] - victim_offsets[block0]);
+    const int skip = (int)std::min<long long>(std::max<long long>(first_row - r0, 0), TB);
+    if (f) {
+        src_of[pos] = (unsigned short)threadIdx.x;
+        if (pos >= skip) {
+#pragma unroll
+            for (int k = 0; k < MOVE_COLUMNS; k++) st.col(k)[before + pos] = m.col[k][r];
+        }
+    }
+    __syncthreads();
+    uint32_t* sd = st.desc() + before * 16;
+    for (int e = skip * 16 + threadIdx.x; e < total * 16; e += TB) sd[e] = m.desc[(size_t)(r0 + src_of[e >> 4]) * 16 + (e & 15)];
+    if (m.xyz) {
+        uint32_t* sx = st.xyz() + before * 6;
+        for (int e = skip * 6 + threadIdx.x; e < total * 6; e += TB) {
+            const int j = e / 6;
+            sx[e] = m.xyz[(size_t)(r0 + src_of[j]) * 6 + (e - j * 6)];
+        }
+    }
+}
+
+// The staged survivors of the chunk (blocks [block0, block_end), region_rows = their rows, a multiple of TB) to rows dst0, dst0 + 1, ..:
+// dst0 = the chunk's first row minus the victims before it. Every copy is contiguous; a block of 256 threads serves one segment of the
+// flat index space [descriptor dwords | MOVE_COLUMNS column planes | world point dwords]. Reads the staging buffer, writes the table only.
+__global__ __launch_bounds__(256) void delete_scatter_kernel(StageColumns st, const int* __restrict__ victim_offsets, int block0, int block_end, int n,
+                                                             int region_rows, int first_row, MoveColumns m) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const long long start = (long long)block0 * TB, end = std::min<long long>((long long)block_end * TB, n);
+    const int victims_before = victim_offsets[block0];
+    const long long survivors = (end - start) - (victim_offsets[block_end] - victims_before);
+    const long long dst0 = start - victims_before;
+    const long long skip = std::max<long long>(first_row - dst0, 0);   // slots of rows that did not move (never staged)
+    const long long R = region_rows, g0 = (long long)blockIdx.x * 256;
+    if (g0 < R * 16) {
+        const long long e = g0 + threadIdx.x;
+        if (e >= skip * 16 && e < survivors * 16) m.desc[dst0 * 16 + e] = st.desc()[e];
+    } else if (g0 < R * (16 + MOVE_COLUMNS)) {
+        const int k = (int)((g0 - R * 16) / R);
+        const long long j = g0 - R * (16 + k) + threadIdx.x;
+        if (j >= skip && j < survivors) m.col[k][dst0 + j] = st.col(k)[j];
+    } else {
+        const long long e = g0 - R * (16 + MOVE_COLUMNS) + threadIdx.x;
+        if (e >= skip * 6 && e < survivors * 6) m.xyz[dst0 * 6 + e] = st.xyz()[e];
+    }
+}
+
 // A view of one table: the outputs of a selection and all the scratch it takes, allocated once (apds_db_view_create).
 struct TableView {
     KeypointTable* t = nullptr;
@@ -481,7 +641,7 @@ void dev_alloc(T*& p, size_t n) {
 void table_free(KeypointTable* t) {
     for (void* p : {(void*)t->x, (void*)t->y, (void*)t->size, (void*)t->angle, (void*)t->response, (void*)t->octave, (void*)t->class_id,
                     (void*)t->image_id, (void*)t->lod, (void*)t->desc64, (void*)t->view_rows, (void*)t->view_kps, (void*)t->view_image_id,
-                    (void*)t->view_desc64, (void*)t->all_kps, (void*)t->xyz})
+                    (void*)t->view_desc64, (void*)t->all_kps, (void*)t->xyz, (void*)t->id, (void*)t->stage})
         if (p) (void)hipFree(p);
     delete t;
 }
@@ -493,9 +653,58 @@ void view_free(TableView* v) {
     delete v;
 }
 TableColumns columns_of(KeypointTable* t) {
-    return TableColumns{t->x, t->y, t->size, t->angle, t->response, t->octave, t->class_id, t->image_id, t->lod, reinterpret_cast<uint32_t*>(t->desc64)};
+    return TableColumns{t->x, t->y, t->size, t->angle, t->response, t->octave, t->class_id, t->image_id, t->lod, reinterpret_cast<uint32_t*>(t->desc64), t->id};
 }
 float lift_offset(uint64_t index, uint64_t tile, int lod) { return (float)(index * tile * (1ull << lod)); }   // (u64 product) as f32
+
+// The rows `a` selects (or, with DELETE_MODE_FLAGGED, the rows already flagged) leave the table; the survivors close up in row order on the
+// calling thread's stream. One host synchronisation for the count and the first victim row, one at the end. Returns the rows deleted.
+int64_t table_delete_rows(KeypointTable* t, ThreadCtx& c, const SelectArgs& a, uint8_t* flags) {
+    hipStream_t s = c.stream;
+    const int n = (int)t->n, nb = ceil_div(n, TB);
+    int* counts = c.alloc_n<int>((size_t)nb + 2);   // victims per block -> their exclusive offsets; [nb] the sum, [nb + 1] the first victim row
+    static const int no_row = 0x7fffffff;
+    HIP_CHECK(hipMemcpyAsync(counts + nb + 1, &no_row, sizeof(int), hipMemcpyHostToDevice, s));
+    const TableColumns cols = columns_of(t);
+    hipLaunchKernelGGL(delete_count_kernel, dim3(nb), dim3(TB), 0, s, cols, n, a, flags, counts, counts + nb + 1);
+    hipLaunchKernelGGL(view_offsets_kernel, dim3(1), dim3(1024), 0, s, counts, nb);
+    HIP_CHECK(hipGetLastError());
+    int h[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(h, counts + nb, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const int m = h[0], first_row = h[1];
+    if (!m) return 0;
+    const bool xyz_valid = t->xyz && t->xyz_rows == t->n;
+    if ((int64_t)first_row + m < n) {   // a survivor sits behind a victim: rows move (a deleted tail moves nothing)
+        if (!t->stage) {
+            t->stage_rows = (int)std::min<int64_t>(DELETE_CHUNK_ROWS, (int64_t)ceil_div(t->capacity, TB) * TB);
+            dev_alloc(t->stage, (size_t)t->stage_rows * STAGE_ROW_DWORDS);
+        }
+        MoveColumns mv;
+        uint32_t* const planes[MOVE_COLUMNS] = {reinterpret_cast<uint32_t*>(t->x), reinterpret_cast<uint32_t*>(t->y), reinterpret_cast<uint32_t*>(t->size),
+                                               reinterpret_cast<uint32_t*>(t->angle), reinterpret_cast<uint32_t*>(t->response),
+                                               reinterpret_cast<uint32_t*>(t->octave), reinterpret_cast<uint32_t*>(t->class_id),
+                                               reinterpret_cast<uint32_t*>(t->image_id), reinterpret_cast<uint32_t*>(t->lod), reinterpret_cast<uint32_t*>(t->id)};
+        for (int k = 0; k < MOVE_COLUMNS; k++) mv.col[k] = planes[k];
+        mv.desc = reinterpret_cast<uint32_t*>(t->desc64);
+        mv.xyz = xyz_valid ? reinterpret_cast<uint32_t*>(t->xyz) : nullptr;
+        const StageColumns st{t->stage, t->stage_rows};
+        const int chunk_blocks = t->stage_rows / TB, segments = xyz_valid ? STAGE_ROW_DWORDS : STAGE_ROW_DWORDS - 6;
+        for (int b0 = first_row / TB; b0 < nb; b0 += chunk_blocks) {
+            const int b1 = std::min(b0 + chunk_blocks, nb), region_rows = (b1 - b0) * TB;
+            hipLaunchKernelGGL(delete_gather_kernel, dim3(b1 - b0), dim3(TB), 0, s, mv, n, (const uint8_t*)flags, (const int*)counts, b0, first_row, st);
+            hipLaunchKernelGGL(delete_scatter_kernel, dim3((unsigned int)((int64_t)region_rows * segments / 256)), dim3(256), 0, s, st, (const int*)counts, b0,
+                               b1, n, region_rows, first_row, mv);
+        }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(s));
+    }
+    t->n -= m;
+    t->view_n = 0;                                                     // the current view's row ids name rows that have moved
+    t->all_kps_rows = std::min<int64_t>(t->all_kps_rows, first_row);   // apds_db_table gathers the moved rows again
+    t->xyz_rows = xyz_valid ? t->n : -1;                               // the world points moved with their rows
+    return m;
+}
 }  // namespace
 
 namespace apds {
@@ -523,6 +732,7 @@ void table_insert_batch_device(void* db, const void* kps_dev, const void* desc64
         total += counts[i];
     }
     APDS_REQUIRE(t->n + total <= t->capacity, APDS_ERR_NOMEM, "keypoint table is full");
+    APDS_REQUIRE(t->next_id + total <= (1ll << 31), APDS_ERR_NOMEM, "keypoint table has given out every 32-bit id");
     for (int i = 0, off = 0; i < n_tiles; off += counts[i], i++) {
         table[i] = off;
         xy[2 * i] = lift_offset(columns_rows[2 * i], tile_w, lod);
@@ -537,10 +747,11 @@ void table_insert_batch_device(void* db, const void* kps_dev, const void* desc64
     HIP_CHECK(hipMemcpyAsync(dtab, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(table_insert_dev_kernel, dim3(ceil_div(total * 16, 256)), dim3(256), ((size_t)n_tiles + 1) * sizeof(int), s,
                        static_cast<const apds_keypoint*>(kps_dev), static_cast<const uint32_t*>(desc64_dev), n_tiles, capacity, (const int*)dtab,
-                       reinterpret_cast<const float2*>(dtab + xy_at), first_image_id, lod, ldexpf(1.0f, lod), (long long)t->n, columns_of(t));
+                       reinterpret_cast<const float2*>(dtab + xy_at), first_image_id, lod, ldexpf(1.0f, lod), (long long)t->n, (int)t->next_id, columns_of(t));
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(s));
     t->n += total;
+    t->next_id += total;
 }
 
 }  // namespace apds
@@ -558,6 +769,7 @@ int apds_db_create(void** db, int64_t capacity) {
             dev_alloc(t->x, capacity); dev_alloc(t->y, capacity); dev_alloc(t->size, capacity); dev_alloc(t->angle, capacity);
             dev_alloc(t->response, capacity); dev_alloc(t->octave, capacity); dev_alloc(t->class_id, capacity);
             dev_alloc(t->image_id, capacity); dev_alloc(t->lod, capacity); dev_alloc(t->desc64, (size_t)capacity * 64);
+            dev_alloc(t->id, capacity);
             t->view_cap = std::min<int64_t>(capacity, APDS_MAX_POINTS);
             dev_alloc(t->view_rows, t->view_cap); dev_alloc(t->view_kps, t->view_cap); dev_alloc(t->view_image_id, t->view_cap);
             dev_alloc(t->view_desc64, (size_t)t->view_cap * 64);
@@ -584,6 +796,7 @@ int apds_db_insert_image(void* db, const apds_keypoint* kps, const uint8_t* desc
         KeypointTable* t = static_cast<KeypointTable*>(db);
         APDS_REQUIRE(t && n >= 0 && lod >= 0 && lod < 31, APDS_ERR_BAD_ARG, "bad argument");
         APDS_REQUIRE(t->n + n <= t->capacity, APDS_ERR_NOMEM, "keypoint table is full");
+        APDS_REQUIRE(t->next_id + n <= (1ll << 31), APDS_ERR_NOMEM, "keypoint table has given out every 32-bit id");
         if (!n) return;
         APDS_REQUIRE(kps && desc61, APDS_ERR_BAD_ARG, "null argument");
         ThreadCtx& c = ctx();
@@ -596,10 +809,11 @@ int apds_db_insert_image(void* db, const apds_keypoint* kps, const uint8_t* desc
         const float scale = ldexpf(1.0f, lod);                                   // 2_f32.powi(lod)
         const float xoff = lift_offset(column, tile_w, lod), yoff = lift_offset(row, tile_h, lod);
         hipLaunchKernelGGL(table_insert_kernel, dim3(ceil_div((long long)n * 16, 256)), dim3(256), 0, s, (const apds_keypoint*)dk, (const uint8_t*)dd, n,
-                           image_id, lod, scale, xoff, yoff, (long long)t->n, columns_of(t));
+                           image_id, lod, scale, xoff, yoff, (long long)t->n, (int)t->next_id, columns_of(t));
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(s));
         t->n += n;
+        t->next_id += n;
     });
 }
 
@@ -796,7 +1010,8 @@ int apds_db_knn_match(void* db, const uint8_t* query_desc, int n_query, int desc
     });
 }
 
-// host copy of the current view: what the reference's Vec<models::Keypoint> holds (id = row + 1 like a SERIAL column)
+// host copy of the current view: what the reference's Vec<models::Keypoint> holds (id: the table's id column, a SERIAL column's values:
+// row + 1 on a table that never saw a delete)
 int apds_db_view_download(void* db, apds_keypoint* kps, uint8_t* desc61, int32_t* ids, int32_t* image_ids) {
     return guarded([&] {
         KeypointTable* t = static_cast<KeypointTable*>(db);
@@ -808,10 +1023,11 @@ int apds_db_view_download(void* db, apds_keypoint* kps, uint8_t* desc61, int32_t
         hipStream_t s = c.stream;
         if (kps) HIP_CHECK(hipMemcpyAsync(kps, t->view_kps, (size_t)m * sizeof(apds_keypoint), hipMemcpyDeviceToHost, s));
         if (image_ids) HIP_CHECK(hipMemcpyAsync(image_ids, t->view_image_id, (size_t)m * 4, hipMemcpyDeviceToHost, s));
-        std::vector<int> rows;
         if (ids) {
-            rows.resize(m);
-            HIP_CHECK(hipMemcpyAsync(rows.data(), t->view_rows, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+            int* view_ids = c.alloc_n<int>(m);
+            hipLaunchKernelGGL(table_ids_of_rows_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, s, (const int*)t->id, (const int*)t->view_rows, m, view_ids);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(ids, view_ids, (size_t)m * 4, hipMemcpyDeviceToHost, s));
         }
         if (desc61) {
             uint8_t* d61 = c.alloc_n<uint8_t>((size_t)m * 61);
@@ -819,8 +1035,6 @@ int apds_db_view_download(void* db, apds_keypoint* kps, uint8_t* desc61, int32_t
             HIP_CHECK(hipMemcpyAsync(desc61, d61, (size_t)m * 61, hipMemcpyDeviceToHost, s));
         }
         HIP_CHECK(hipStreamSynchronize(s));
-        if (ids)
-            for (int i = 0; i < m; i++) ids[i] = rows[i] + 1;
     });
 }
 
@@ -929,6 +1143,73 @@ int apds_db_view_pointers(const void* view, void** rows64_dev, void** kps_dev, v
         if (image_ids_dev) *image_ids_dev = v->image_id;
         if (xyz_dev) *xyz_dev = v->has_xyz ? v->xyz : nullptr;
         if (n) *n = v->n;
+    });
+}
+
+// ---- ids and deletes: keypointdb.rs:28-36 (read_keypoint_from_id) and 92-97 (delete_keypoint) ----------------------------------------
+int apds_db_ids(void* db, void** ids_dev) {
+    return guarded([&] {
+        KeypointTable* t = static_cast<KeypointTable*>(db);
+        APDS_REQUIRE(t && ids_dev, APDS_ERR_BAD_ARG, "null argument");
+        *ids_dev = t->id;
+    });
+}
+
+int apds_db_read_keypoint_from_id(void* db, int id, apds_keypoint* kp, uint8_t* desc61, int* image_id, int64_t* row) {
+    return guarded([&] {
+        KeypointTable* t = static_cast<KeypointTable*>(db);
+        APDS_REQUIRE(t, APDS_ERR_BAD_ARG, "null table");
+        APDS_REQUIRE(t->n > 0 && id >= 1, APDS_ERR_OUT_OF_RANGE, "no keypoint has this id");
+        ThreadCtx& c = ctx();
+        APDS_REQUIRE(t->device == c.device, APDS_ERR_BAD_ARG, "the table lives on another device than the calling thread's");
+        c.ws_reset();
+        hipStream_t s = c.stream;
+        FoundRow* out = c.alloc_n<FoundRow>(1);
+        hipLaunchKernelGGL(table_read_id_kernel, dim3(1), dim3(64), 0, s, columns_of(t), (long long)t->n, id, out);
+        HIP_CHECK(hipGetLastError());
+        FoundRow h;
+        HIP_CHECK(hipMemcpyAsync(&h, out, sizeof(h), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        APDS_REQUIRE(h.row >= 0, APDS_ERR_OUT_OF_RANGE, "no keypoint has this id");
+        if (kp) *kp = h.kp;
+        if (desc61) memcpy(desc61, h.desc, 61);
+        if (image_id) *image_id = h.image_id;
+        if (row) *row = h.row;
+    });
+}
+
+int apds_db_delete_where(void* db, int mode, int value, float x_start, float y_start, float x_end, float y_end, int64_t* n_deleted) {
+    return guarded([&] {
+        KeypointTable* t = static_cast<KeypointTable*>(db);
+        APDS_REQUIRE(t && mode >= 0 && mode <= 2, APDS_ERR_BAD_ARG, "bad argument");
+        if (n_deleted) *n_deleted = 0;
+        if (!t->n) return;
+        ThreadCtx& c = ctx();
+        APDS_REQUIRE(t->device == c.device, APDS_ERR_BAD_ARG, "the table lives on another device than the calling thread's");
+        c.ws_reset();
+        const SelectArgs a{mode, value, floorf(x_start), floorf(y_start), ceilf(x_end), ceilf(y_end)};
+        const int64_t m = table_delete_rows(t, c, a, c.alloc_n<uint8_t>((size_t)t->n));
+        if (n_deleted) *n_deleted = m;
+    });
+}
+
+int apds_db_delete_ids(void* db, const int32_t* ids, int n, int64_t* n_deleted) {
+    return guarded([&] {
+        KeypointTable* t = static_cast<KeypointTable*>(db);
+        APDS_REQUIRE(t && n >= 0 && (ids || !n), APDS_ERR_BAD_ARG, "bad argument");
+        if (n_deleted) *n_deleted = 0;
+        if (!t->n || !n) return;
+        ThreadCtx& c = ctx();
+        APDS_REQUIRE(t->device == c.device, APDS_ERR_BAD_ARG, "the table lives on another device than the calling thread's");
+        c.ws_reset();
+        hipStream_t s = c.stream;
+        uint8_t* flags = c.alloc_n<uint8_t>((size_t)t->n);
+        int* list = c.alloc_n<int>(n);
+        HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)t->n, s));
+        HIP_CHECK(hipMemcpyAsync(list, ids, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(delete_mark_ids_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, (const int*)t->id, (long long)t->n, (const int*)list, n, flags);
+        const int64_t m = table_delete_rows(t, c, SelectArgs{DELETE_MODE_FLAGGED, 0, 0, 0, 0, 0}, flags);
+        if (n_deleted) *n_deleted = m;
     });
 }
 

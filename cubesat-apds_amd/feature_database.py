@@ -72,8 +72,9 @@ class KeypointTable:
 
     def device_table(self):
         """(rows64, kps, xyz, n): device pointers of the WHOLE table in the layout a pipeline takes (descriptor rows, 28-byte keypoints,
-        world points; all indexed by table row = id - 1). xyz is None unless world_coordinates() has run since the last insert. The
-        pointers hold until the next insert or close()."""
+        world points; all indexed by table row: ids()[row] is its id, row + 1 until the first delete). xyz is None unless
+        world_coordinates() has run since the last insert; a delete keeps it current. The pointers hold until the next insert, delete or
+        close()."""
         r, k, x, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64(0)
         check(lib().apds_db_table(self._h, C.byref(r), C.byref(k), C.byref(x), C.byref(n)))
         return r.value, k.value, x.value, n.value
@@ -101,6 +102,54 @@ class KeypointTable:
     def read_keypoints_from_coordinates(self, x_start, y_start, x_end, y_end, level_of_detail):
         """keypointdb.rs:67-90"""
         return self._select(2, level_of_detail, (x_start, y_start, x_end, y_end))
+
+    def read_keypoint_from_id(self, id):
+        """keypointdb.rs:28-36 -> KeypointRows of one row (ids, keypoints, descriptors, image_ids of length 1). Raises
+        ApdsError(ERR_OUT_OF_RANGE) where the reference returns Err(NotFound): an id that was deleted or never given."""
+        kp = np.zeros(1, KEYPOINT_DTYPE)
+        d = np.zeros((1, 61), np.uint8)
+        img = C.c_int(0)
+        check(lib().apds_db_read_keypoint_from_id(self._h, int(id), ptr(kp), ptr(d), C.byref(img), None))
+        return KeypointRows(np.array([id], np.int32), kp, d, np.array([img.value], np.int32))
+
+    def ids(self):
+        """The id of every row, by row (int32): row + 1 until the first delete, the reference's SERIAL values ever after."""
+        out = np.zeros(len(self), np.int32)
+        if len(out):
+            p = C.c_void_p()
+            check(lib().apds_db_ids(self._h, C.byref(p)))
+            check(lib().apds_dev_download(ptr(out), p, out.nbytes, None))
+        return out
+
+    def _delete_where(self, mode, value, box=(0, 0, 0, 0)):
+        n = C.c_int64(0)
+        check(lib().apds_db_delete_where(self._h, mode, int(value), float(box[0]), float(box[1]), float(box[2]), float(box[3]), C.byref(n)))
+        return n.value
+
+    def delete_keypoints(self, ids):
+        """keypointdb.rs:92-97 for a list of ids at once -> the number of rows deleted. Unknown ids delete nothing (the reference's
+        Ok(())), duplicates count once. The surviving rows close up on the device in insertion order and keep their ids; device pointers,
+        the last selection and earlier row ids are void after a delete that removed a row."""
+        a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        n = C.c_int64(0)
+        check(lib().apds_db_delete_ids(self._h, ptr(a), len(a), C.byref(n)))
+        return n.value
+
+    def delete_keypoint(self, id):
+        """keypointdb.rs:92-97"""
+        return self.delete_keypoints([id])
+
+    def delete_keypoints_from_image_id(self, image_id):
+        """Every row read_keypoints_from_image_id qualifies (no 262143 limit) -> the number of rows deleted."""
+        return self._delete_where(0, image_id)
+
+    def delete_keypoints_from_lod(self, level_of_detail):
+        """Every row read_keypoints_from_lod qualifies."""
+        return self._delete_where(1, level_of_detail)
+
+    def delete_keypoints_from_coordinates(self, x_start, y_start, x_end, y_end, level_of_detail):
+        """Every row read_keypoints_from_coordinates qualifies (floor(start) <= v <= ceil(end))."""
+        return self._delete_where(2, level_of_detail, (x_start, y_start, x_end, y_end))
 
     def view_device_pointers(self):
         """(rows64, keypoints, row_ids, image_ids, n): device pointers of the last selection (a ready train set)."""

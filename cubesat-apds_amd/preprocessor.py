@@ -165,6 +165,33 @@ def downscale_from_lod(table, images, dataset, amount_lod, lod, workers=1, fused
     return out
 
 
+def replace_tiles(table, images, dataset, amount_lod, lod, cells, batch=1, resample="nearest", mask_nodata=False):
+    """The tiles `cells` = [(column, row), ...] of level `lod` again, from a DeviceMosaic that now holds their new imagery: the rows of each
+    tile's image leave the table (KeypointTable.delete_keypoints_from_image_id) and the tile goes through the device_insert path of
+    downscale_from_lod once more, under the image id it already has. The tiles' new rows follow every row that stayed, in the order of
+    `cells`, with new keypoint ids; nothing else in the table changes. Returns [(image_id, n_deleted, n_inserted), ...]."""
+    if not isinstance(dataset, DeviceMosaic):
+        raise ValueError("replace_tiles needs a DeviceMosaic dataset: the rows go from the extraction to the table on the device")
+    tile_size, _, _ = tile_grid(dataset.raster_size(), amount_lod, lod)
+    span = (tile_size[0] * 2 ** lod, tile_size[1] * 2 ** lod)
+    by_place = {(r["level_of_detail"], r["x_start"], r["y_start"]): r["id"] for r in images.rows}
+    cells = [(int(j), int(i)) for j, i in cells]
+    try:
+        ids = [by_place[(int(lod), j * span[0], i * span[1])] for j, i in cells]
+    except KeyError:
+        raise ValueError("replace_tiles: a tile that has no image row cannot be replaced") from None
+    deleted = [table.delete_keypoints_from_image_id(image_id) for image_id in ids]
+    inserted, k, step = [], 0, max(int(batch), 1)
+    while k < len(cells):          # one call per run of consecutive image ids, `batch` tiles at the most
+        e = k + 1
+        while e < len(cells) and e - k < step and ids[e] == ids[e - 1] + 1:
+            e += 1
+        inserted += feature_extraction.mosaic_tiles_to_database(dataset, table, [(j * span[0], i * span[1]) for j, i in cells[k:e]], span, tile_size,
+                                                                cells[k:e], ids[k], lod, resample, mask_nodata=mask_nodata)
+        k = e
+    return list(zip(ids, deleted, inserted))
+
+
 def process_lod_from_mosaic(table, images, dataset, lod, workers=1, fused=True, batch=1, resample="nearest", mask_nodata=False, device_insert=False):
     """main.rs:175-194 — all levels 0 .. lod-1."""
     if device_insert and not isinstance(dataset, DeviceMosaic):

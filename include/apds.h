@@ -392,9 +392,10 @@ int apds_db_world_coordinates(void* db, const double* dataset_gt, const double* 
 /* The WHOLE table in the layout the pipeline takes (no selection, no 262143-row limit, insertion order): *rows64_dev = the table's own
  * descriptor column (not a copy), *kps_dev = a table-owned buffer of 28-byte keypoints with the lifted coordinates, indexed by row
  * (gathered by one kernel, and only for rows added since the last call), *xyz_dev = the column of apds_db_world_coordinates, or NULL if
- * it was never computed or rows were added since it was; *n = rows. Any output may be NULL. The pointers hold until the next insert or
- * apds_db_destroy. They are the arguments of apds_pipeline_create(.., rows64, n, 0, NULL, kps, n, ..) and apds_pipeline_pose_params'
- * db_xyz_dev; a match's trainIdx is then the table row, i.e. the id - 1 that apds_db_view_download reports. */
+ * it was never computed or rows were added since it was; *n = rows. Any output may be NULL. The pointers hold until the next insert, delete
+ * or apds_db_destroy. They are the arguments of apds_pipeline_create(.., rows64, n, 0, NULL, kps, n, ..) and apds_pipeline_pose_params'
+ * db_xyz_dev; a match's trainIdx is then the table row: the id - 1 that apds_db_view_download reports while the table has seen no
+ * delete, and the index into apds_db_ids always. */
 int apds_db_table(void* db, void** rows64_dev, void** kps_dev, void** xyz_dev, int64_t* n);
 /* View objects: the read of keypointdb.rs:50-90 (read_keypoints_from_lod / read_keypoints_from_coordinates: the rows of one level of
  * detail, optionally inside a bounding box, ORDER BY response DESC LIMIT 262143) as something a caller repeats for every frame. A view
@@ -420,6 +421,33 @@ int apds_db_view_select(void* view, int mode, int value, float x_start, float y_
  * be NULL. The pointers hold until apds_db_view_destroy; their contents until the next select. */
 int apds_db_view_pointers(const void* view, void** rows64_dev, void** kps_dev, void** row_ids_dev, void** image_ids_dev, void** xyz_dev,
                           int* n);
+/* Ids and deletes: the two access paths of the reference's KeypointDatabase trait that take an id, read_keypoint_from_id
+ * (keypointdb.rs:28-36) and delete_keypoint (keypointdb.rs:92-97), and the deletes by image, level of detail and region that replacing
+ * imagery needs. Every row has an id that behaves like the reference's SERIAL column: the first row ever inserted gets 1, every insert
+ * continues from the highest id ever given plus one, an id is never reused and never changes when other rows are deleted. Ids therefore
+ * ascend with the row; on a table that never saw a delete, id = row + 1. apds_db_view_download reports these ids.
+ * A delete closes the table up on the device: the surviving rows keep their order and every bit of every column, their world points
+ * (apds_db_world_coordinates) move with them and stay current, and apds_db_rows shrinks. A delete is a writer like an insert: single-
+ * threaded per table, never while a select of any view of the table is in flight, never while a pipeline holds the table
+ * (apds_pipeline_create_table). A delete that removes at least one row invalidates the pointers of apds_db_table and apds_db_ids (ask
+ * again), the table's current view (apds_db_select: it is emptied) and the row ids of every earlier selection. View objects stay usable:
+ * their next select sees the new table. Handles made by apds_db_shard earlier are copies and do not change. A delete that removes
+ * nothing changes nothing, and pointers handed out earlier stay valid. The calls run on the calling thread's own stream and return when
+ * the table is final. */
+/* *ids_dev = the id column by row (int32, apds_db_rows of them; the table's own column, not a copy). Holds until the next insert or
+ * delete. Indexing it with the row ids of apds_db_view / apds_db_view_pointers, or with a match's trainIdx over apds_db_table, gives ids. */
+int apds_db_ids(void* db, void** ids_dev);
+/* keypointdb.rs:28-36: the row that has `id` (a binary search of the id column on the device): its keypoint (lifted coordinates), the
+ * first 61 bytes of its descriptor, its image id and its current row. Any output may be NULL. An id no row has - deleted, never given,
+ * below 1 - is APDS_ERR_OUT_OF_RANGE (the reference returns Err(NotFound)). */
+int apds_db_read_keypoint_from_id(void* db, int id, apds_keypoint* kp, uint8_t* desc61, int* image_id, int64_t* row);
+/* Deletes every row apds_db_select qualifies for the same mode, value and box (mode 0: an image's keypoints; 1: a level of detail; 2: a
+ * region at a level of detail, floor(start) <= v <= ceil(end)) - all of them: no 262143-row limit, no ordering. *n_deleted (may be
+ * NULL) = the exact number of rows removed. */
+int apds_db_delete_where(void* db, int mode, int value, float x_start, float y_start, float x_end, float y_end, int64_t* n_deleted);
+/* Deletes the rows whose id is in the host array ids[0 .. n). An id no row has deletes nothing and is no error (keypointdb.rs:92-97: diesel's
+ * execute returns Ok(0)); an id listed twice counts once; the list need not be sorted. n == 1 is the reference's delete_keypoint. */
+int apds_db_delete_ids(void* db, const int32_t* ids, int n, int64_t* n_deleted);
 
 /* ---- multi-GPU: the descriptor DB row-sharded over the GPUs of one node (BASELINE config 5) -------------------------------
  * No counterpart upstream: the reference matches on one CPU (feature_extraction/src/lib.rs:94-126) against whatever train set
