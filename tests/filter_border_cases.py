@@ -11,8 +11,8 @@ SCAN_BLOCK = 1024                          # flags per block of scan_block_count
 WAVE = 64                                  # the ballots of block_exclusive_pos
 SCAN_TRIP = 1024                           # block counts per trip of scan_offsets_kernel's loop
 CARRY_N = SCAN_BLOCK * SCAN_TRIP           # 1 048 576: flags beyond this one are placed through `carry`
-# ---- csrc/keypoint_table.hip ----------------------------------------------------------------------------------------------------------
-TB = 1024                                  # table_emit_keys_kernel / key_compact_kernel
+# ---- csrc/keypoint_select.hip ---------------------------------------------------------------------------------------------------------
+TB = 1024                                  # keypoint_table.h: rows / keys per block of the select kernels
 # ---- include/apds.h -------------------------------------------------------------------------------------------------------------------
 APDS_MAX_POINTS = 2 ** 18 - 1              # LIMIT of every select (keypointdb.rs:12)
 # ---- csrc/topk_keys.h -----------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
-"""GPU: apds_db_view_select (csrc/keypoint_table.hip, the view path) - the read of keypointdb.rs:50-90 on a view object, on the caller's
+"""GPU: apds_db_view_select (csrc/keypoint_select.hip, the view objects) - the read of keypointdb.rs:50-90 on a view object, on the caller's
 stream. Every result is compared bit for bit with a numpy reference written from the definition (a predicate, a stable sort on
-(-response with -0.0 -> +0.0, row), a cut) and, wherever the limits are equal, with apds_db_select + apds_db_view_download, the older
-host-driven path. Tables are built with apds_db_insert_image from synthetic rows; nothing is extracted.
+(-response with -0.0 -> +0.0, row), a cut); wherever the limits are equal, apds_db_select + apds_db_view_download - the other front of
+the same selection engine - is held to the same numpy reference. Tables are built with apds_db_insert_image from synthetic rows; nothing is extracted.
 
 The borders: 0, 1, 2 qualifying rows; capacity - 1, capacity, capacity + 1 (the radix cut starts at capacity + 1); the LDS sort block
 SORT_B = 2048 keys: B - 1, B, B + 1, 2B + 1 (one block, two blocks, a global merge step); a capacity that is no power of two; the cut inside
@@ -15,7 +15,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-SORT_B = 2048          # csrc/keypoint_table.hip
+SORT_B = 2048          # csrc/keypoint_select.hip
 CAP = 3000             # a view capacity that is no power of two
 LIMIT = 2 ** 18 - 1    # keypointdb.rs:12
 
@@ -311,6 +311,64 @@ def test_table_current_view_is_untouched(borders):
     assert m == SORT_B - 1 and tb.t.view_device_pointers()[4] == m
     assert np.array_equal(ids, before.ids) and np.array_equal(_bits(kp), _bits(before.keypoints)) and np.array_equal(d, before.descriptors)
     assert np.array_equal(img, before.image_ids)
+
+
+def test_view_object_is_untouched_by_a_table_select(borders):
+    """the reverse: apds_db_select runs the same kernels from the same thread, on the workspace and the table's own current view"""
+    tb, pkg = borders, borders.pkg
+    view = tb.t.view(5000)
+    try:
+        want16 = reference(tb.kp["response"], tb.mask(0, 16), 5000)
+        n = select(view, 0, 16)
+        assert n == 2 * SORT_B + 1
+        check_view(tb, view, n, want16)
+        first = download(pkg, view)
+        check_old_path(tb, 0, 13, None, reference(tb.kp["response"], tb.mask(0, 13), LIMIT))
+        assert tb.t.view_device_pointers()[4] == SORT_B - 1
+        again = download(pkg, view)
+        for a, b in zip(first[:4], again[:4]):
+            assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+        assert view.device_pointers()[5] == n
+    finally:
+        view.close()
+
+
+def test_interleaved_table_and_view_selects(borders):
+    """twenty selects of one thread, the two fronts alternating with different arguments: each one against the numpy reference"""
+    tb = borders
+    args = [(0, 16, None), (1, 1, None), (0, 13, None), (2, 1, (10.3, 20.7, 250.2, 300.1)), (0, 3, None), (1, 0, None), (0, 99, None),
+            (2, 0, (0.0, 0.0, 120.5, 399.0)), (0, 19, None), (0, 14, None)]
+    view = tb.t.view(CAP)
+    try:
+        for i in range(20):
+            mode, value, box = args[(3 * i + i // 2) % len(args)]
+            mask = tb.mask(mode, value, box)
+            if i % 2 == 0:
+                check_old_path(tb, mode, value, box, reference(tb.kp["response"], mask, LIMIT))
+            else:
+                check_view(tb, view, select(view, mode, value, box), reference(tb.kp["response"], mask, CAP))
+    finally:
+        view.close()
+
+
+def test_repeated_table_selects_allocate_nothing(borders):
+    """apds_db_select's scratch is the thread's workspace, sized by the table's rows: after the largest selection nothing more is taken"""
+    import torch
+    tb, pkg = borders, borders.pkg
+    L, n = pkg.lib(), C.c_int(0)
+    jobs = [(1, 1, len(reference(tb.kp["response"], tb.mask(1, 1), LIMIT))), (0, 16, 2 * SORT_B + 1), (0, 99, 0), (1, 0, int(tb.mask(1, 0).sum()))]
+    assert jobs[0][2] == max(j[2] for j in jobs)
+    pkg._lib.check(L.apds_db_select(tb.t._h, jobs[0][0], jobs[0][1], 0.0, 0.0, 0.0, 0.0, C.byref(n)))
+    assert n.value == jobs[0][2]
+    torch.cuda.synchronize()
+    live, free = L.apds_live_contexts(), torch.cuda.mem_get_info()[0]
+    for i in range(50):
+        mode, value, want = jobs[i % len(jobs)]
+        pkg._lib.check(L.apds_db_select(tb.t._h, mode, value, 0.0, 0.0, 0.0, 0.0, C.byref(n)))
+        assert n.value == want
+    torch.cuda.synchronize()
+    assert L.apds_live_contexts() == live and torch.cuda.mem_get_info()[0] == free
+    check_old_path(tb, 1, 1, None, reference(tb.kp["response"], tb.mask(1, 1), LIMIT))
 
 
 def test_repeated_selects_allocate_nothing(borders):

@@ -1,4 +1,4 @@
-"""GPU: csrc/keypoint_table.hip at its borders - selects on a table of more than 1024 scan blocks, the LIMIT cut inside groups of equal
+"""GPU: apds_db_select (csrc/keypoint_select.hip) at its borders - selects on a table of more than 1024 scan blocks, the LIMIT cut inside groups of equal
 responses, the sort network around a power of two, ORDER BY response DESC over zeros, subnormals, negative responses and +inf, the
 bounding box on, and one ulp beside, its inclusive edges, the insert's zero padding and capacity, and the view after an empty select.
 Exact equality with the numpy restatements of filter_border_cases.py (test_filter_border_inputs_cpu.py shows that the inputs sit where they

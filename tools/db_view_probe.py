@@ -2,9 +2,11 @@
 """What a per-frame select costs beside the scan, on one GPU, on a 1 M-row keypoint table (the rolled copies of the frames, then random rows;
 one level of detail, coordinates spread over a 16384^2 mosaic).
 
- 1. apds_db_view_select (the stream-ordered view path) against apds_db_select (the host-driven path it is compared with) in one process,
-    the two calls alternating, medians of the wall time until the view is complete. Two cases: a bounding box that qualifies fewer rows
-    than the 262143-row limit, and a level-of-detail select that qualifies every row (radix cut + the full 2^18 sort).
+ 1. the two fronts of the one selection engine (csrc/keypoint_select.hip) in one process, the two calls alternating, medians of the wall
+    time until the view is complete: apds_db_view_select (a view object's buffers, the caller's stream; view_select_ms) and apds_db_select
+    (the table's current view, scratch from the thread's workspace, synchronised; db_select_ms - up to profiles/db_view/ that key timed a
+    host-driven implementation of its own, the keys are kept so the runs stay comparable). Two cases: a bounding box that qualifies
+    fewer rows than the 262143-row limit, and a level-of-detail select that qualifies every row (radix cut + the full 2^18 sort).
  2. frames/s of a pipeline whose train set is selected per frame (every selection returns the full 262143 rows) against the whole-table
     pipeline on the same table and frames, off / on alternating, and the select's share of the per-frame-view frame period.
 
@@ -73,7 +75,7 @@ def main():
         table.create_keypoints(_Ex(kp, synth.make_descriptor_db(m, seed=synth.DB_SEED + len(table))), 100, 0)
     view = table.view()
 
-    # ---- 1. the two select paths, alternating
+    # ---- 1. the two fronts of the selection engine, alternating
     cases = {"box_below_limit": (2, 0, (0.0, 0.0, 7000.0, 7000.0)), "lod_all_rows": (1, 0, (0.0, 0.0, 0.0, 0.0))}
     select = {}
     for name, (mode, value, box) in cases.items():
