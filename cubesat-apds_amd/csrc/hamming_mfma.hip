@@ -52,6 +52,17 @@ static constexpr int HM_TM = 16 * HM_WAVES;      // train rows per tile
 #endif
 // waves per SIMD the kernel is compiled for (4: two 8-wave workgroups per CU. The 12-wave shape - APDS_HM_WAVES=12 APDS_HM_WPE=3, one
 // workgroup per CU with a quarter of the registers left to the other stages' kernels - is a build-time experiment)
+// The top-2 kernel's register cap. A wave's allocation is its count rounded up to the granule of 8, and a SIMD holds 512 registers per lane:
+//     4 waves x 104 = 416, and 96 are left - one wave of any kernel of 96 registers or fewer beside the four match waves, on every SIMD
+//     of the chip, for as long as the match runs (at 113 -> 120 allocated, 4 x 120 = 480 left 32: no wave of any other stage fitted, and
+//     the extraction ran only where a whole match workgroup had retired).
+// Stated to the compiler so that an edit cannot cross the granule unseen (tests/test_hamming_mfma_budget.py reads the count, scratch and
+// spills back). The attribute counts the architected half of gfx90a-and-later's unified file: the backend doubles what it is given and
+// clamps that to the range of amdgpu_waves_per_eu, so the kernel asks for half the cap. (128: the same as no cap - the A/B build.)
+#ifndef APDS_HM_TOP2_VGPRS
+#define APDS_HM_TOP2_VGPRS (APDS_HM_WPE == 4 ? 104 : 512 / APDS_HM_WPE / 8 * 8)
+#endif
+static_assert(APDS_HM_TOP2_VGPRS % 8 == 0 && APDS_HM_WPE * APDS_HM_TOP2_VGPRS <= 512, "the cap is whole granules that fit the SIMD's file");
 #ifndef APDS_HM_NC
 #define APDS_HM_NC 3
 #endif
@@ -126,38 +137,45 @@ __device__ __forceinline__ void hm_insert(HmTop2& b, uint32_t d, uint32_t idx) {
 
 // ---- the tile loop of both kernels ----
 // One wave's share of a tile by LDS-DMA: rows [16 wave, 16 wave + 16) as four pieces of 1 KB (4 rows each). The source of piece i is the
-// wave-uniform tile base + a per-lane constant (voff[i] + 1024 i); the destination is wave-uniform (m0) + 1024 i + 16 lane - the instruction
-// offset counts on both sides. Written as assembly because the DMA has to stay in flight while the tile in the OTHER buffer is read: the
+// wave-uniform tile base + a per-lane constant ((voff0 ^ 64 i) + 1024 i: hm_scan_tiles says why; pieces 1 .. 3 make theirs here, in a
+// register the statement gives back - the v_xor behind the write of m0 is also the wait state a DMA needs behind it); the destination is
+// wave-uniform (m0) + 1024 i + 16 lane - the instruction offset counts on both sides. Written as assembly because the DMA has to stay in flight while the tile in the OTHER buffer is read: the
 // compiler cannot tell the two halves of one LDS array apart and, for a DMA it knows of, waits vmcnt(0) in front of the next ds_read
 // (the builtin form of this loop had that wait two instructions behind the DMA issue, in front of every tile's first MFMA). Nothing else
 // in the loop uses the vector-memory counter; the wave that issued a DMA waits for it itself (hm_dma_wait) in front of the barrier
 // behind which the tile is read - a barrier alone does not wait for a DMA. m0 is the compiler's: saved and restored.
-__device__ __forceinline__ void hm_dma_rows(const unsigned char* tile_base, const int (&voff)[4], uint32_t lds_dst) {
+__device__ __forceinline__ void hm_dma_rows(const unsigned char* tile_base, int voff0, uint32_t lds_dst) {
     uint32_t keep;
+    int t;   // the source constant of pieces 1 .. 3 (see hm_scan_tiles): live inside this statement only
     asm volatile(
         "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %6\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %5\n\t"
-        "global_load_lds_dwordx4 %2, %5 offset:1024\n\t"
-        "global_load_lds_dwordx4 %3, %5 offset:2048\n\t"
-        "global_load_lds_dwordx4 %4, %5 offset:3072\n\t"
+        "s_mov_b32 m0, %4\n\t"
+        "v_xor_b32 %1, 64, %2\n\t"
+        "global_load_lds_dwordx4 %2, %3\n\t"
+        "global_load_lds_dwordx4 %1, %3 offset:1024\n\t"
+        "v_xor_b32 %1, 0x80, %2\n\t"
+        "global_load_lds_dwordx4 %1, %3 offset:2048\n\t"
+        "v_xor_b32 %1, 0xc0, %2\n\t"
+        "global_load_lds_dwordx4 %1, %3 offset:3072\n\t"
         "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(tile_base), "s"(lds_dst)
+        : "=&s"(keep), "=&v"(t)
+        : "v"(voff0), "s"(tile_base), "s"(lds_dst)
         : "memory");
 }
-// 64 popcounts (one float per lane)
-__device__ __forceinline__ void hm_dma_popcounts(const float* src, int voff, uint32_t lds_dst) {
+// 64 popcounts (one float per lane; the source offset 4 * lane is made here, in a register that is free again behind the statement)
+__device__ __forceinline__ void hm_dma_popcounts(const float* src, uint32_t lds_dst) {
     uint32_t keep;
+    int t;
     asm volatile(
         "s_mov_b32 %0, m0\n\t"
         "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"
+        "v_mbcnt_lo_u32_b32 %1, -1, 0\n\t"
+        "v_mbcnt_hi_u32_b32 %1, -1, %1\n\t"
+        "v_lshlrev_b32 %1, 2, %1\n\t"
         "global_load_lds_dword %1, %2\n\t"
         "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(src), "s"(lds_dst)
+        : "=&s"(keep), "=&v"(t)
+        : "s"(src), "s"(lds_dst)
         : "memory");
 }
 __device__ __forceinline__ void hm_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
@@ -187,15 +205,14 @@ __device__ __forceinline__ void hm_scan_tiles(const uint4* __restrict__ train_fp
     const uint32_t lds0 = (uint32_t)(__SIZE_TYPE__)(__attribute__((address_space(3))) unsigned char*)hm_lds;
     // (the expanded rows are padded to whole tiles - zero rows with a popcount of +inf - so a piece's source is a uniform tile base plus a
     // per-lane constant: scalar address arithmetic only)
-    int voff[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int r = 16 * wave + 4 * i + (lane >> 4);
-        voff[i] = r * 256 + (((lane & 15) ^ (r & 15)) << 4) - 1024 * i;
-    }
+    // Piece i holds rows r = 16 wave + 4 i + kq, and its constant is 256 r + ((col ^ (r & 15)) << 4) - 1024 i. With r & 15 = 4 i + kq = 4 i ^ kq
+    // that is 4096 wave + 256 kq + (((col ^ kq) ^ 4 i) << 4): piece 0's constant with 64 i XORed in (bits 6 and 7, which no other term
+    // touches). One register holds piece 0's; hm_dma_rows derives the others where it issues them - three v_xor per tile (once in about
+    // 6 000 cycles) for three registers of the whole loop.
+    const int voff0 = (16 * wave + kq) * 256 + ((col ^ kq) << 4);
     auto stage = [&](int tile, int buf) {
-        hm_dma_rows(reinterpret_cast<const unsigned char*>(train_fp4) + (size_t)tile * TILE_BYTES, voff, lds0 + buf * TILE_BYTES + 16 * wave * 256);
-        if (wave < HM_TM / 64) hm_dma_popcounts(tpc + (size_t)tile * HM_TM + 64 * wave, 4 * lane, lds0 + 2 * TILE_BYTES + buf * (HM_TM * 4) + 256 * wave);
+        hm_dma_rows(reinterpret_cast<const unsigned char*>(train_fp4) + (size_t)tile * TILE_BYTES, voff0, lds0 + buf * TILE_BYTES + 16 * wave * 256);
+        if (wave < HM_TM / 64) hm_dma_popcounts(tpc + (size_t)tile * HM_TM + 64 * wave, lds0 + 2 * TILE_BYTES + buf * (HM_TM * 4) + 256 * wave);
     };
     // this lane's four A reads of a 16-row block: row (16 rb + col), chunk 4 s + kq at position (4 s + kq) ^ col; behind them the popcounts
     // of rows 4 kq .. + 3 of a block. Offsets into the buffer being read: they change sides at every tile border.
@@ -293,7 +310,17 @@ __device__ __forceinline__ HmItem hm_work_item(int n_train, int tiles_per_split,
     w.col = lane & 15, w.kq = lane >> 4;
     return w;
 }
-// B operands: query (q0 + 16 c + col), elements 128 s + 32 kq .. + 31 (dword 4 s + kq of the row), for the four k steps s; qq: its popcount
+// B operands: query (q0 + 16 c + col), elements 128 s + 32 kq .. + 31 (dword 4 s + kq of the row), for the four k steps s
+template <int NC>
+__device__ __forceinline__ void hm_load_operands(const uint4* query_fp4, int nq, int q0, int col, int kq, uint4 (&B)[NC][4]) {
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        const int qi = min(q0 + 16 * c + col, nq - 1);
+#pragma unroll
+        for (int s = 0; s < 4; s++) B[c][s] = query_fp4[(size_t)qi * 16 + 4 * s + kq];
+    }
+}
+// ... and qq: the queries' popcounts, for a kernel that keeps them in registers across the tile loop
 template <int NC>
 __device__ __forceinline__ void hm_load_queries(const uint4* query_fp4, const float* qpc, int nq, int q0, int col, int kq, uint4 (&B)[NC][4], float (&qq)[NC]) {
 #pragma unroll
@@ -323,7 +350,7 @@ __device__ __forceinline__ uint32_t hm_distance(float qq, uint32_t d) { return (
 // THR: the launch starts from thresholds (the main launch behind a threshold launch) - a template parameter so that profilers list the two
 // launches of a match under two names
 template <int PRIO, bool THR>
-__global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(APDS_HM_WPE, APDS_HM_WPE))) void hamming_mfma_kernel(const uint4* __restrict__ train_fp4, const float* __restrict__ tpc, int n_train,
+__global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(APDS_HM_WPE, APDS_HM_WPE), amdgpu_num_vgpr(APDS_HM_TOP2_VGPRS / 2))) void hamming_mfma_kernel(const uint4* __restrict__ train_fp4, const float* __restrict__ tpc, int n_train,
                                                            const uint4* __restrict__ query_fp4, const float* __restrict__ qpc, int nq, int tiles_per_split,
                                                            int q_tiles, int splits, uint32_t index_base, const uint32_t* __restrict__ thr,
                                                            uint64_t* __restrict__ out) {
@@ -332,13 +359,12 @@ __global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(A
     // (locals, and by value into the helpers: with the struct handed on by reference the kernels' register allocation changed)
     const int split = w.split, q0 = w.q0, tile_begin = w.tile_begin, tile_end = w.tile_end, col = w.col, kq = w.kq;
     uint4 B[HM_NC][4];
-    float qq[HM_NC];
-    hm_load_queries<HM_NC>(query_fp4, qpc, nq, q0, col, kq, B, qq);
+    hm_load_operands<HM_NC>(query_fp4, nq, q0, col, kq, B);   // (the queries' popcounts are read where they are used: behind the tile loop)
     HmTop2 best[HM_NC];   // both entries start as hm_start_value
 #pragma unroll
     for (int c = 0; c < HM_NC; c++) {
         best[c].d0 = hm_start_value<THR>(thr, min(q0 + 16 * c + col, nq - 1));
-        hm_settle(best[c].d0), hm_settle(qq[c]);
+        hm_settle(best[c].d0);
         best[c].d1 = best[c].d0;
         best[c].i0 = best[c].i1 = 0xFFFFFFFFu;
     }
@@ -395,8 +421,9 @@ __global__ __launch_bounds__(64 * HM_WAVES) __attribute__((amdgpu_waves_per_eu(A
         const int qi = q0 + 16 * c + col;
         if (kq == 0 && qi < nq) {
             uint64_t* o = out + ((size_t)split * nq + qi) * 2;
-            o[0] = b.i0 == 0xFFFFFFFFu ? EMPTY_KEY : make_key(hm_distance(qq[c], b.d0), b.i0);
-            o[1] = b.i1 == 0xFFFFFFFFu ? EMPTY_KEY : make_key(hm_distance(qq[c], b.d1), b.i1);
+            const float qq = qpc[qi];   // the query's popcount: one load per output pair, not a register per column block across the loop
+            o[0] = b.i0 == 0xFFFFFFFFu ? EMPTY_KEY : make_key(hm_distance(qq, b.d0), b.i0);
+            o[1] = b.i1 == 0xFFFFFFFFu ? EMPTY_KEY : make_key(hm_distance(qq, b.d1), b.i1);
         }
     }
 }
