@@ -40,16 +40,26 @@ struct Top2 {
     uint32_t i0, i1;
 };
 
-__device__ __forceinline__ void top2_insert(Top2& b, float d, uint32_t idx) {
-    if (d < b.d1) {
-        if (d < b.d0) {
-            b.d1 = b.d0;
-            b.i1 = b.i0;
-            b.d0 = d;
-            b.i0 = idx;
-        } else {
-            b.d1 = d;
-            b.i1 = idx;
+// d^2 as the keys carry it. The map u -> d^2 is monotone but merges distinct u (the clamp at 0, the rounding of the add)
+__device__ __forceinline__ float l2_d2(float qq, float u) { return fmaxf(qq + u, 0.f); }
+
+// A lane's list holds u, but is ranked on d^2 = l2_d2(qq, u), the value its keys will carry: rows arrive in ascending order, so a strict
+// `<` on d^2 keeps the lower row among equal d^2 and the list is the lane's two smallest (d^2, row), which is the order of every later
+// merge. (Ranked on u, three near-duplicates of a query in one lane kept the two smallest u, not the two lowest rows of equal d^2.)
+// The tile loop's hit test stays on u: l2_d2(u) < l2_d2(b.d1) implies u < b.d1, so it never misses an insertion.
+__device__ __forceinline__ void top2_insert(Top2& b, float qq, float u, uint32_t idx) {
+    if (u < b.d1) {   // necessary for the test on d^2 below, and false for nearly every value: the common case costs what it did
+        const float d = l2_d2(qq, u);
+        if (d < l2_d2(qq, b.d1)) {
+            if (d < l2_d2(qq, b.d0)) {
+                b.d1 = b.d0;
+                b.i1 = b.i0;
+                b.d0 = u;
+                b.i0 = idx;
+            } else {
+                b.d1 = u;
+                b.i1 = idx;
+            }
         }
     }
 }
@@ -202,7 +212,7 @@ __global__ __launch_bounds__(512) void l2_topk_kernel(const float* __restrict__ 
         }
 #undef L2_STEP
 #undef L2_LOAD
-        // epilogue: candidates are ranked on u = |t|^2 - 2 q.t (|q|^2 is constant per query and added once at the end).
+        // epilogue: candidates are screened on u = |t|^2 - 2 q.t (|q|^2 is constant per query; top2_insert adds it to rank).
         // A lane holds rows 4*(lane>>4) + r of the wave's 16 for its query column of each of the 8 column blocks:
         // screen all 32 values with min chains, insert only when some lane has a hit
         const float4 t4 = *reinterpret_cast<const float4*>(&wTT[4 * kc]);
@@ -222,15 +232,15 @@ __global__ __launch_bounds__(512) void l2_topk_kernel(const float* __restrict__ 
 #pragma unroll
             for (int n = 0; n < 8; n++)
 #pragma unroll
-                for (int r = 0; r < 4; r++) top2_insert(best[n], vals[n][r], row0 + r);
+                for (int r = 0; r < 4; r++) top2_insert(best[n], qq[n], vals[n][r], row0 + r);
         }
         if (more) commit();
     }
-    // d^2 = max(|q|^2 + u, 0): same value as ranking on d^2 directly, the add is monotone
+    // d^2 = max(|q|^2 + u, 0): the value the insertions ranked on
 #pragma unroll
     for (int n = 0; n < 8; n++) {
-        best[n].d0 = fmaxf(qq[n] + best[n].d0, 0.f);
-        best[n].d1 = fmaxf(qq[n] + best[n].d1, 0.f);
+        best[n].d0 = l2_d2(qq[n], best[n].d0);
+        best[n].d1 = l2_d2(qq[n], best[n].d1);
     }
     // merge the 32 partial lists of every query (8 waves x 4 row classes) through LDS, source-major so that the final scan
     // reads conflict-free; the LDS is reused from its start, hence the barrier (slower waves may still read sQ)

@@ -5,8 +5,8 @@
 //
 //   pass A  S(q,t) = |q|^2 + |t|^2 - 2 q~.t~ with q~, t~ the operands rounded to bf16, products exact and accumulation in f32
 //           inside v_mfma_f32_16x16x32_bf16; fused running top-2 per query -> s2(q), the second smallest screen value. Run over a
-//           SAMPLE of the train rows (the first 1/16, at least 8192): its s2 is an upper bound of the whole set's, which is all the
-//           proof below needs, and it costs 1/16 of a pass;
+//           SAMPLE of the train rows (the first 1/12 by default, APDS_L2_SAMPLE_DIV, at least 8192): its s2 is an upper bound of the
+//           whole set's, which is all the proof below needs, and it costs 1/12 of a pass;
 //   pass B  the products of ALL rows; every row with S(q,t) <= s2(q) + 2 eps(q) is appended to a candidate list;
 //   pass C  the candidates are re-ranked with EXACTLY the arithmetic of l2_match.hip (the same binary32 fmaf chain over k, the same
 //           |t|^2 - 2 q.t and |q|^2 + . and max(., 0)), keys (distance bits << 32 | row) reduced by 64-bit atomic min.
@@ -20,7 +20,7 @@
 // <= s2 + eps; every row of the exact top-2 (ties included) has F <= that, hence S <= s2 + 2 eps: it is a candidate. (A looser s2
 // only admits more candidates: a sample of 1/12 of the rows admits ~2 * 12 * 2.5 = 60 per query on BASELINE config 3, ~5 with the
 // exact s2: 25 ms more re-rank against 190 ms less screening.) The re-rank therefore returns the keys l2_match.hip returns, bit for bit
-// (tests/test_l2_match_gpu.py compares the two modes directly).
+// (tests/test_l2_match_gpu.py and tests/test_l2_borders_gpu.py compare the two modes directly).
 //
 // Screen kernel (CDNA4): block = 8 waves = 384 queries x a stream of 128-row train tiles. A wave keeps its 48 queries (three 16-column
 // blocks) as MFMA B operands in registers for the whole kernel (bf16: 48 VGPRs); train tiles are staged in LDS (bf16, pre-scaled by
