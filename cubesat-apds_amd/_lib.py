@@ -48,6 +48,8 @@ SYMBOLS = [
     "apds_db_view_create", "apds_db_view_destroy", "apds_db_view_select", "apds_db_view_pointers", "apds_pipeline_create_table", "apds_pipeline_submit_select",
     "apds_dev_crosscheck_match", "apds_pipeline_set_matcher",
     "apds_db_ids", "apds_db_read_keypoint_from_id", "apds_db_delete_where", "apds_db_delete_ids",
+    "apds_distort_points", "apds_undistort_points", "apds_dev_undistort_points", "apds_undistort_image", "apds_dev_undistort_image",
+    "apds_pnp_solver_ransac_dist", "apds_pipeline_set_lens",
 ]
 
 RESAMPLE_NEAREST, RESAMPLE_LANCZOS = 0, 1
@@ -304,6 +306,13 @@ def lib():
             "apds_db_read_keypoint_from_id": (i, [vp, i, vp, vp, ip, C.POINTER(i64)]),
             "apds_db_delete_where": (i, [vp, i, i, f, f, f, f, C.POINTER(i64)]),
             "apds_db_delete_ids": (i, [vp, vp, i, C.POINTER(i64)]),
+            "apds_distort_points": (i, [vp, i, vp, vp, i, vp]),
+            "apds_undistort_points": (i, [vp, i, vp, vp, i, i, vp]),
+            "apds_dev_undistort_points": (i, [vp, i, i, vp, vp, i, i, vp]),
+            "apds_undistort_image": (i, [vp, i, i, i, vp, vp, i, vp, vp]),
+            "apds_dev_undistort_image": (i, [vp, i, i, i, vp, vp, i, vp, vp, vp]),
+            "apds_pnp_solver_ransac_dist": (i, [vp, vp, i, vp, i, f, d, i, vp, i, vp, vp, vp, ip, ip]),
+            "apds_pipeline_set_lens": (i, [vp, vp, vp, i, i]),
         }
         for name, (rt, at) in sig.items():
             fn = getattr(L, name)
@@ -311,6 +320,16 @@ def lib():
             fn.argtypes = at
         _LIB = L
     return _LIB
+
+
+def lens_args(K, dist):
+    """(K [3, 3] f64, dist f64 or None, pointer to K, pointer to dist or None, n_dist) of a camera matrix and OpenCV-ordered distortion
+    coefficients (None or empty: no distortion) as the apds_*distort* calls take them. Keep the arrays alive across the call."""
+    K = np.ascontiguousarray(K, np.float64).reshape(3, 3)
+    d = None if dist is None else np.ascontiguousarray(dist, np.float64).ravel()
+    if d is not None and d.size == 0:
+        d = None
+    return K, d, ptr(K), (ptr(d) if d is not None else None), (int(d.size) if d is not None else 0)
 
 
 def check(rc):

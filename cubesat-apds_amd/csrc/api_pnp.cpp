@@ -17,6 +17,33 @@ int apds_pnp_solver_ransac(const double* obj_xyz, const double* img_xy, int n, c
     });
 }
 
+int apds_pnp_solver_ransac_dist(const double* obj_xyz, const double* img_xy, int n, const double* camera_intrinsic, int iter_count, float reproj_thres,
+                                double confidence, int method, const double* dist, int n_dist, double* rvec, double* tvec, int32_t* inliers,
+                                int* n_inliers, int* found) {
+    APDS_RANGE("apds_pnp_solver_ransac_dist");
+    return guarded([&] {
+        APDS_REQUIRE(found, APDS_ERR_BAD_ARG, "null argument");
+        *found = 0;
+        // argument errors before any device work: the lens, then what the plain call checks
+        lens::Lens L;
+        const bool distorts = lens_from_args(camera_intrinsic, dist, n_dist, &L);
+        APDS_REQUIRE(n_inliers, APDS_ERR_BAD_ARG, "null argument");
+        *n_inliers = 0;
+        APDS_REQUIRE(obj_xyz && img_xy && rvec && tvec && inliers, APDS_ERR_BAD_ARG, "null argument");
+        (void)pnp_checked_method(n, method);
+        ThreadCtx& c = ctx();
+        c.ws_reset();
+        if (!distorts) {   // apds_pnp_solver_ransac itself
+            *found = pnp_ransac_device(obj_xyz, img_xy, n, camera_intrinsic, iter_count, reproj_thres, confidence, method, rvec, tvec, inliers, n_inliers, c.stream);
+            return;
+        }
+        // the image points to ideal pixels in f64 (cv::undistortPoints' five steps, P = cameraMatrix), then the f32 conversion and the loop
+        std::vector<double> ideal((size_t)n * 2);
+        lens_points_host(img_xy, n, L, lens::DEFAULT_ITERS, ideal.data(), c.stream);
+        *found = pnp_ransac_device(obj_xyz, ideal.data(), n, camera_intrinsic, iter_count, reproj_thres, confidence, method, rvec, tvec, inliers, n_inliers, c.stream);
+    });
+}
+
 int apds_dev_pnp_solver_ransac(const void* obj_xyz_dev, const void* img_xy_dev, int n, const double* camera_intrinsic, int iter_count, float reproj_thres,
                                double confidence, int method, double* rvec, double* tvec, int32_t* inliers, int* n_inliers, int* found, void* stream) {
     APDS_RANGE("apds_dev_pnp_solver_ransac");

@@ -9,8 +9,11 @@
 
 #include "kernels.h"
 #include "pnp_core.h"
+#include "warp_sample.h"
 
 namespace apds {
+
+constexpr int WARP_BORDER = 1;   // warp_image_perspective: BORDER_CONSTANT, Scalar(1,1,1,1) (mod.rs:271-300)
 
 struct GeoTransform {
     double c[6];
@@ -40,10 +43,7 @@ __global__ void band_merger_kernel(const float* __restrict__ red, const float* _
     }
 }
 
-__device__ __forceinline__ int sat_int_rn(double v) {
-    return v <= (double)INT_MIN ? INT_MIN : (v >= (double)INT_MAX ? INT_MAX : __double2int_rn(v));
-}
-
+// warp_perspective_kernel: the 8UC4 form, one thread per destination pixel, whole pixels as uint32_t (the sampling tail: warp_sample.h)
 __global__ void warp_perspective_kernel(const uint32_t* __restrict__ src, int rows, int cols, double m0, double m1, double m2, double m3, double m4,
                                         double m5, double m6, double m7, double m8, const short* __restrict__ tab, int dst_rows, int dst_cols,
                                         uint32_t* __restrict__ dst) {
@@ -57,26 +57,12 @@ __global__ void warp_perspective_kernel(const uint32_t* __restrict__ src, int ro
     const double fX = fmax((double)INT_MIN, fmin((double)INT_MAX, X0 * W));
     const double fY = fmax((double)INT_MIN, fmin((double)INT_MAX, Y0 * W));
     const int X = sat_int_rn(fX), Y = sat_int_rn(fY);
-    const int sx = X >> 5, sy = Y >> 5;
-    const short* w = &tab[((Y & 31) * 32 + (X & 31)) * 4];
-    uint32_t p[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int xx = sx + (k & 1), yy = sy + (k >> 1);
-        p[k] = (xx >= 0 && xx < cols && yy >= 0 && yy < rows) ? src[(size_t)yy * cols + xx] : 0x01010101u;   // border value (1,1,1,1)
-    }
-    uint32_t out = 0;
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const int v = (int)((p[0] >> (8 * c)) & 0xFF) * w[0] + (int)((p[1] >> (8 * c)) & 0xFF) * w[1] + (int)((p[2] >> (8 * c)) & 0xFF) * w[2] +
-                      (int)((p[3] >> (8 * c)) & 0xFF) * w[3];
-        out |= (uint32_t)(((v + (1 << 14)) >> 15) & 0xFF) << (8 * c);
-    }
-    dst[(size_t)y * dst_cols + x] = out;
+    sample_bilinear_u8<4>(reinterpret_cast<const uint8_t*>(src), rows, cols, X, Y, tab, WARP_BORDER,
+                          reinterpret_cast<uint8_t*>(dst + (size_t)y * dst_cols + x));   // border value (1,1,1,1)
 }
 
 // The same map for the other element types warp_image_perspective<T: DataType> admits (mod.rs:271-300 is generic): CH interleaved channels
-// of u8 (OpenCV's fixed-point path: the 15-bit weight table above, (sum + 2^14) >> 15) or f32 (remapBilinear's float path: the four
+// of u8 (OpenCV's fixed-point path: warp_sample.h) or f32 (remapBilinear's float path: the four
 // weights (1-fy)(1-fx), (1-fy)fx, fy(1-fx), fy fx as float products of the 1/32-step fractions, ((v0 w0 + v1 w1) + v2 w2) + v3 w3 in
 // binary32, one operation each; a destination pixel whose 2x2 footprint lies wholly outside the source IS the border value).
 template <class T, int CH>
@@ -92,24 +78,17 @@ __global__ void warp_perspective_generic_kernel(const T* __restrict__ src, int r
     const double fX = fmax((double)INT_MIN, fmin((double)INT_MAX, X0 * W));
     const double fY = fmax((double)INT_MIN, fmin((double)INT_MAX, Y0 * W));
     const int X = sat_int_rn(fX), Y = sat_int_rn(fY);
-    const int sx = X >> 5, sy = Y >> 5;
     T* d = dst + ((size_t)y * dst_cols + x) * CH;
-    bool in[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int xx = sx + (k & 1), yy = sy + (k >> 1);
-        in[k] = xx >= 0 && xx < cols && yy >= 0 && yy < rows;
-    }
     if constexpr (sizeof(T) == 1) {
-        const short* w = &tab[((Y & 31) * 32 + (X & 31)) * 4];
-#pragma unroll
-        for (int c = 0; c < CH; c++) {
-            int v = 0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) v += (in[k] ? (int)src[((size_t)(sy + (k >> 1)) * cols + sx + (k & 1)) * CH + c] : 1) * w[k];   // border value 1
-            d[c] = (T)((v + (1 << 14)) >> 15);
-        }
+        sample_bilinear_u8<CH>(src, rows, cols, X, Y, tab, WARP_BORDER, d);   // border value 1
     } else {
+        const int sx = X >> 5, sy = Y >> 5;
+        bool in[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int xx = sx + (k & 1), yy = sy + (k >> 1);
+            in[k] = xx >= 0 && xx < cols && yy >= 0 && yy < rows;
+        }
         if (!(in[0] || in[1] || in[2] || in[3])) {
 #pragma unroll
             for (int c = 0; c < CH; c++) d[c] = (T)1;
@@ -130,8 +109,6 @@ __global__ void warp_perspective_generic_kernel(const T* __restrict__ src, int r
         }
     }
 }
-
-namespace {
 
 // 32x32 table of 2x2 fixed-point (15 bit) bilinear weights that sum to 2^15 (OpenCV's BilinearTab_i restated)
 const short* bilinear_tab_host() {
@@ -167,6 +144,8 @@ const short* bilinear_tab_host() {
     }
     return tab;
 }
+
+namespace {
 
 bool invert3x3(const double* m, double* inv) {
     const double d = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);

@@ -2,6 +2,7 @@
 #pragma once
 #include <atomic>
 #include "common.h"
+#include "lens_core.h"
 
 namespace apds {
 
@@ -86,6 +87,15 @@ int world_coordinates_device(const double* xy, int n, const double* dgt_host, co
                              hipStream_t s);
 int64_t world_coordinates_columns_device(const float* x, const float* y, int n, const double* dgt_host, const double* egt_host, const double* elev, int ew,
                                          int eh, double* xyz, hipStream_t s);   // x, y: device f32 columns; returns the number of missed lookups
+
+// lens.hip (the model: lens_core.h). lens_from_args: every argument check of a (K, dist, n_dist) triple, before any device work; returns
+// whether the lens distorts at all. points_f64: iters 0 = forward model, >= 1 = that many inverse steps. points_host: host arrays through
+// the calling thread's workspace (not reset), synchronises s. undistort_points_f32: in place on f32 pairs every stride_bytes, no workspace.
+bool lens_from_args(const double* K, const double* dist, int n_dist, lens::Lens* out);
+void lens_points_f64_device(const double* xy_dev, int n, const lens::Lens& L, int iters, double* out_dev, hipStream_t s);
+void lens_points_host(const double* xy, int n, const lens::Lens& L, int iters, double* out, hipStream_t s);
+void lens_undistort_points_f32_device(void* xy_dev, int n, size_t stride_bytes, const lens::Lens& L, int iters, hipStream_t s);
+void undistort_image_device(const uint8_t* src, int rows, int cols, int channels, const lens::Lens& L, const double* new_K, uint8_t* dst, hipStream_t s);
 
 // keypoint_table.hip: the device a table lives on; n_tiles tiles of an extraction's device output (tile i at i * capacity rows) appended in
 // tile order by one launch on s (checks first, then writes; takes its small tile table from the calling thread's workspace WITHOUT

@@ -152,6 +152,9 @@ struct Pipeline {
     float* db_plain_pc = nullptr;   // cross-check mode on the expanded copy: the train rows' popcounts as the swapped scan's column side takes them
     int view_capacity = 0;
     apds_pipeline_pose_params pose{};
+    std::atomic<bool> lens_on{false};   // set before the first submit (apds_pipeline_set_lens), and only for a lens that distorts
+    lens::Lens lens{};
+    int lens_iters = lens::DEFAULT_ITERS;
 
     std::mutex m;   // results, counters, errors
     std::condition_variable cv;
@@ -486,6 +489,8 @@ struct Pipeline {
                 if (M >= 4) {
                     // query_idx -> this frame's keypoints, train_idx -> the DB rows' keypoints (the intended gather: lib.rs:161-180 has two bugs)
                     PIPE_OK(apds_dev_points_from_matches(s->kps, s->K, train_kps, n_train, s->matches, M, 0, s->p1, s->p2, st));
+                    // the frame side of the matches to ideal pixels (the train side is map geometry): one launch on this stream, no workspace
+                    if (lens_on) PIPE_OK(guarded([&] { lens_undistort_points_f32_device(s->p1, M, 2 * sizeof(float), lens, lens_iters, st); }));
                     const int rc = apds_dev_find_homography(s->p1, s->p2, M, p.homography_method, p.reproj_threshold, p.max_iters, p.confidence, r.H, s->mask, st);
                     if (rc == APDS_OK) {
                         r.homography_found = 1;
@@ -529,6 +534,7 @@ struct Pipeline {
                 try {
                     HIP_CHECK(hipStreamWaitEvent(st, s->ev_homography, 0));
                     PIPE_OK(apds_dev_pnp_correspondences(s->kps, s->K, table ? s->view_xyz : pose.db_xyz_dev, table ? (int64_t)s->n_view : n_db_total, pose.origin, s->matches, M, s->pose_img, s->pose_obj, st));
+                    if (lens_on) PIPE_OK(guarded([&] { lens_undistort_points_f32_device(s->pose_img, M, 2 * sizeof(float), lens, lens_iters, st); }));
                     // fewer than four pairs: the one-call entry's APDS_ERR_ASSERT, without device work
                     fp.status = apds_dev_pnp_solver_ransac(s->pose_obj, s->pose_img, M, pose.camera_intrinsic, pose.iter_count, pose.reproj_thres, pose.confidence,
                                                           pose.method, fp.rvec, fp.tvec, nullptr, &fp.n_inliers, &fp.found, st);
@@ -892,6 +898,23 @@ int apds_pipeline_set_matcher(void* pipe, int matcher) {
             if (previous >= 0 && previous != P->device) (void)hipSetDevice(previous);
         }
         P->matcher = matcher;
+    });
+}
+
+int apds_pipeline_set_lens(void* pipe, const double* K, const double* dist, int n_dist, int iters) {
+    return guarded([&] {
+        lens::Lens L;
+        const bool distorts = lens_from_args(K, dist, n_dist, &L);   // the argument checks first, before the handle is touched
+        Pipeline* P = pipe_handle(pipe);
+        std::lock_guard<std::mutex> one(P->submit_m);
+        {
+            std::lock_guard<std::mutex> g(P->m);
+            if (P->failed) fail(P->fail_code, P->fail_msg);
+            APDS_REQUIRE(P->next_submit == 0, APDS_ERR_BAD_ARG, "the lens is set before the first submit");
+        }
+        P->lens = L;
+        P->lens_iters = iters > 0 ? iters : lens::DEFAULT_ITERS;
+        P->lens_on = distorts;   // no distortion: the stages launch what they launched without a lens
     });
 }
 

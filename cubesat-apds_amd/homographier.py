@@ -122,6 +122,48 @@ def warp_image_perspective(src, m, size=None):
     return Cmat(out, img.dtype.type, ch if img.ndim == 3 else 1)
 
 
+def _lens_points(fn, points, camera_matrix, dist_coeffs, *extra):
+    xy = np.ascontiguousarray(points, np.float64).reshape(-1, 2)
+    K, d, pK, pd, nd = _lib.lens_args(getattr(camera_matrix, "mat", camera_matrix), getattr(dist_coeffs, "mat", dist_coeffs))
+    out = np.zeros_like(xy)
+    try:
+        check(fn(ptr(xy), len(xy), pK, pd, nd, *extra, ptr(out)))
+    except ApdsError as e:
+        raise MatError("Opencv", e)
+    return out
+
+
+def distort_points(points, camera_matrix, dist_coeffs):
+    """Ideal pixels -> the pixels a lens with these coefficients shows them at (apds_distort_points): points [n, 2] f64, camera_matrix 3x3
+    (array or Cmat), dist_coeffs 4, 5 or 8 values in OpenCV's order (k1, k2, p1, p2[, k3[, k4, k5, k6]]); None / empty / all zero returns
+    the input bits. The model and its evaluation order: include/apds.h, csrc/lens_core.h."""
+    return _lens_points(lib().apds_distort_points, points, camera_matrix, dist_coeffs)
+
+
+def undistort_points(points, camera_matrix, dist_coeffs, iters=5):
+    """cv::undistortPoints with P = cameraMatrix (apds_undistort_points): distorted pixels -> ideal pixels by exactly `iters` steps of the
+    fixed-point iteration (<= 0: 5, OpenCV's count)."""
+    return _lens_points(lib().apds_undistort_points, points, camera_matrix, dist_coeffs, int(iters))
+
+
+def undistort_image(src, camera_matrix, dist_coeffs, new_camera_matrix=None):
+    """cv::undistort (apds_undistort_image): src a Cmat (or array) of HxW or HxWxC u8, C = 1, 3, 4; returns a Cmat of the same shape: the
+    image an ideal camera new_camera_matrix (None: camera_matrix) would have taken; fixed-point bilinear, border value 0."""
+    a = np.asarray(getattr(src, "mat", src))
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3, 4)):
+        raise MatError("Opencv", ApdsError(_lib.ERR_ASSERT, "undistort_image serves u8 images of 1, 3 or 4 channels"))
+    img = np.ascontiguousarray(a)
+    K, d, pK, pd, nd = _lib.lens_args(getattr(camera_matrix, "mat", camera_matrix), getattr(dist_coeffs, "mat", dist_coeffs))
+    nK = None if new_camera_matrix is None else np.ascontiguousarray(getattr(new_camera_matrix, "mat", new_camera_matrix), np.float64).reshape(3, 3)
+    out = np.zeros_like(img)
+    ch = 1 if img.ndim == 2 else img.shape[2]
+    try:
+        check(lib().apds_undistort_image(ptr(img), img.shape[0], img.shape[1], ch, pK, pd, nd, ptr(nK) if nK is not None else None, ptr(out)))
+    except ApdsError as e:
+        raise MatError("Opencv", e)
+    return Cmat(out, np.uint8, ch if img.ndim == 3 else 1)
+
+
 class SolvePnPMethod(enum.IntEnum):
     """opencv::calib3d::SolvePnPMethod values the reference can pass (mod.rs:4,327)."""
     SOLVEPNP_ITERATIVE = 0
@@ -154,12 +196,13 @@ class PNPRANSACSolution:
 
 def pnp_solver_ransac(point_correspondences, camera_intrinsic, iter_count, reproj_thres, confidence, dist_coeffs=None, method=None):
     """mod.rs:320-369 — solvePnPRansac(useExtrinsicGuess = false). Returns a PNPRANSACSolution, or None when no pose was found
-    (Ok(None)); raises MatError("Opencv") for fewer than 4 correspondences (mod.rs:627-638). `dist_coeffs` is accepted and ignored,
-    as in the reference, which shadows it with zeros(4,1) before the call (mod.rs:344). Built: SOLVEPNP_EPNP (the default),
+    (Ok(None)); raises MatError("Opencv") for fewer than 4 correspondences (mod.rs:627-638). `dist_coeffs` None is the reference's call,
+    which shadows the argument with zeros(4,1) (mod.rs:344); anything else is what the reference documents the argument to be (mod.rs:310,
+    326) and goes to apds_pnp_solver_ransac_dist: 4, 5 or 8 coefficients in OpenCV's order, the image points undistorted in f64 before the
+    solve, reproj_thres in undistorted pixels (include/apds.h). Built: SOLVEPNP_EPNP (the default),
     SOLVEPNP_P3P, SOLVEPNP_AP3P, SOLVEPNP_ITERATIVE (EPnP RANSAC, then solvePnP(ITERATIVE) over the inliers without an extrinsic guess),
     SOLVEPNP_SQPNP (EPnP RANSAC, then SQPnP over the inliers) and SOLVEPNP_DLS / SOLVEPNP_UPNP (EPnP, as in OpenCV 4); four correspondences go through P3P
     whatever the method, as in OpenCV."""
-    del dist_coeffs
     n = len(point_correspondences)
     obj = np.ascontiguousarray([p.obj_point for p in point_correspondences], np.float64).reshape(n, 3)
     img = np.ascontiguousarray([p.img_point for p in point_correspondences], np.float64).reshape(n, 2)
@@ -171,8 +214,14 @@ def pnp_solver_ransac(point_correspondences, camera_intrinsic, iter_count, repro
     inliers = np.zeros(max(n, 1), np.int32)
     n_inl, found = C.c_int(0), C.c_int(0)
     try:
-        check(lib().apds_pnp_solver_ransac(ptr(obj), ptr(img), n, ptr(K), int(iter_count), float(reproj_thres), float(confidence), method_i,
-                                           ptr(rvec), ptr(tvec), ptr(inliers), C.byref(n_inl), C.byref(found)))
+        if dist_coeffs is None:
+            check(lib().apds_pnp_solver_ransac(ptr(obj), ptr(img), n, ptr(K), int(iter_count), float(reproj_thres), float(confidence), method_i,
+                                               ptr(rvec), ptr(tvec), ptr(inliers), C.byref(n_inl), C.byref(found)))
+        else:
+            dist = np.ascontiguousarray(getattr(dist_coeffs, "mat", dist_coeffs), np.float64).ravel()
+            check(lib().apds_pnp_solver_ransac_dist(ptr(obj), ptr(img), n, ptr(K), int(iter_count), float(reproj_thres), float(confidence), method_i,
+                                                    ptr(dist) if dist.size else None, int(dist.size), ptr(rvec), ptr(tvec), ptr(inliers),
+                                                    C.byref(n_inl), C.byref(found)))
     except ApdsError as e:
         raise MatError("Opencv", e)
     if not found.value:

@@ -319,6 +319,19 @@ def dev_crosscheck_match(q_rows64, t_rows64, index_base=0, out=None):
     return dst[:n.value]
 
 
+def dev_undistort_points(points, camera_matrix, dist_coeffs, iters=5):
+    """apds_dev_undistort_points on the CURRENT stream, in place: `points` is a device tensor of f32 rows whose first two elements are
+    (x, y) - [n, 2] points, [n, 7] keypoint rows (28 bytes), or any row stride of at least 8 bytes; only x and y are rewritten, each pair
+    widened to f64, undistorted by `iters` steps (<= 0: 5) and rounded once. Returns `points`."""
+    n = int(points.shape[0]) if points.dim() == 2 else -1
+    if points.dtype != torch.float32 or n < 0 or points.shape[1] < 2 or (n > 0 and points.stride(1) != 1):
+        raise ValueError("points: a [n, >= 2] float32 device tensor with unit column stride")
+    K, d, pK, pd, nd = _lib.lens_args(camera_matrix, dist_coeffs)
+    stride = int(points.stride(0)) * 4 if n > 1 else 4 * int(points.shape[1])     # (an empty or one-row tensor's row stride means nothing)
+    check(lib().apds_dev_undistort_points(points.data_ptr() if n else None, n, stride, pK, pd, nd, int(iters), torch_stream()))
+    return points
+
+
 SOLVEPNP_EPNP = 1
 
 
@@ -469,8 +482,11 @@ class StreamedFramePipeline:
 
     def __init__(self, db_rows64, db_xy, index_base=0, group=None, max_points=(1 << 18) - 1, device="cuda:0", slots=6, reserve_cus=0,
                  n_cus=256, meta_group=None, extract_workers=None, transport="rccl", pose=None, db_kp=None, per_frame_table=None, view_capacity=None,
-                 matcher="ratio"):
+                 matcher="ratio", lens=None):
         import os
+        # lens = (K, dist_coeffs, iters): apds_pipeline_set_lens - the image side of every frame's matches is undistorted on the device in
+        # front of the homography and the pose (K is expected to be the pose stage's camera matrix); None: no lens
+        self.lens = None if lens is None else (_lib.lens_args(lens[0], lens[1]), int(lens[2]) if len(lens) > 2 else 5)
         self.matcher_mode = _matcher_code(matcher)   # "ratio" | "crosscheck" (apds_pipeline_set_matcher; one GPU and per-frame-view pipelines)
         self.dev = torch.device(device)
         self.per_frame_table = per_frame_table     # a KeypointTable: the train set is selected from it per frame (from_table)
@@ -552,6 +568,14 @@ class StreamedFramePipeline:
         self._pipe, self._key = h, key
         if self.matcher_mode != _lib.PIPELINE_MATCH_RATIO:     # (a pipeline that never asks runs the ratio matcher)
             rc = lib().apds_pipeline_set_matcher(h, self.matcher_mode)
+            if rc != 0:
+                why = lib().apds_last_error().decode("utf-8", "replace")
+                self._pipe = None
+                lib().apds_pipeline_destroy(h)
+                raise _lib.ApdsError(rc, why)
+        if self.lens is not None:
+            (K, d, pK, pd, nd), iters = self.lens
+            rc = lib().apds_pipeline_set_lens(h, pK, pd, nd, iters)
             if rc != 0:
                 why = lib().apds_last_error().decode("utf-8", "replace")
                 self._pipe = None

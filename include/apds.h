@@ -302,6 +302,49 @@ int apds_warp_perspective_f32(const float* src, int rows, int cols, int channels
 #define APDS_SOLVEPNP_SQPNP 8
 int apds_pnp_solver_ransac(const double* obj_xyz, const double* img_xy, int n, const double* camera_intrinsic, int iter_count, float reproj_thres,
                            double confidence, int method, double* rvec, double* tvec, int32_t* inliers, int* n_inliers, int* found);
+/* pnp_solver_ransac with the argument the reference documents ("distortion coefficients from camera calibration", mod.rs:310,326) and
+ * then shadows: dist = n_dist coefficients of the lens model below (see apds_undistort_points). The image points are undistorted in f64
+ * (apds_undistort_points' arithmetic with iters = 5 and K = camera_intrinsic) before solvePnPRansac's f32 conversion; everything after
+ * that is apds_pnp_solver_ransac. With no distortion (n_dist 0, dist NULL, or every coefficient exactly 0) it IS apds_pnp_solver_ransac,
+ * bit for bit. reproj_thres is therefore measured in UNDISTORTED pixels. OpenCV measures it in the distorted image (it projects with the
+ * coefficients inside the RANSAC loop): a deliberate difference, not pinned against OpenCV. The lens arguments are checked first
+ * (status codes: apds_undistort_points), then the plain call's own (n < 4 -> APDS_ERR_ASSERT), all before any device work. */
+int apds_pnp_solver_ransac_dist(const double* obj_xyz, const double* img_xy, int n, const double* camera_intrinsic, int iter_count, float reproj_thres,
+                                double confidence, int method, const double* dist, int n_dist, double* rvec, double* tvec, int32_t* inliers,
+                                int* n_inliers, int* found);
+
+/* ---- lens distortion ------------------------------------------------------------------------------------------------------------------
+ * OpenCV's radial-tangential model with the rational denominator; the reference's calibrator computes these coefficients
+ * (calibrator/src/main.rs:59-73, calibrate_camera_def). All arithmetic in f64, every operation in the order csrc/lens_core.h writes down.
+ * K: 3x3 row major, fx = K[0], cx = K[2], fy = K[4], cy = K[5]; the skew K[1] is ignored, as OpenCV ignores it. Normalised coordinates
+ * x = (u - cx) / fx, y = (v - cy) / fy, r2 = x x + y y. dist in OpenCV's order (k1, k2, p1, p2[, k3[, k4, k5, k6]]):
+ *   forward (ideal -> distorted): rc = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3),
+ *       x' = x rc + 2 p1 x y + p2 (r2 + 2 x x), y' = y rc + p1 (r2 + 2 y y) + 2 p2 x y, u' = fx x' + cx, v' = fy y' + cy;
+ *   inverse (distorted -> ideal): cv::undistortPoints' fixed-point iteration from x = x': x <- (x' - dx(x, y)) / rc(x, y), likewise y (dx, dy
+ *       the tangential part), EXACTLY iters steps, no early exit (the result is a pure function of the inputs); iters <= 0: 5, what
+ *       cv::undistortPoints runs; output fx x + cx (P = cameraMatrix).
+ * n_dist: 0 (or dist NULL) = no distortion; 4, 5, 8 served; 12 and 14 (thin prism, tilt) APDS_ERR_NOT_IMPLEMENTED; anything else
+ * APDS_ERR_BAD_ARG; a coefficient that is not finite, or a focal length that is not finite and positive: APDS_ERR_BAD_ARG - all before any
+ * device work. No distortion - n_dist 0 or every coefficient exactly 0 - launches nothing: points and images come back bit for bit. */
+/* xy, out: n x 2 doubles on the host (out may be xy); computed on the device. n == 0: APDS_OK without touching the device. */
+int apds_distort_points(const double* xy, int n, const double* K, const double* dist, int n_dist, double* out);
+int apds_undistort_points(const double* xy, int n, const double* K, const double* dist, int n_dist, int iters, double* out);
+/* The inverse in place on device points: n pairs of f32 (x, y), one pair at the head of every stride_bytes bytes - 8: a point array
+ * (apds_dev_points_from_matches, apds_dev_pnp_correspondences' img_xy); 28: apds_keypoint rows, of which only x and y are rewritten; any
+ * other stride >= 8 that is a multiple of 4 (else APDS_ERR_BAD_ARG). Each pair is widened to f64, undistorted, and rounded once on the
+ * store. One kernel, one thread per point, asynchronous on `stream` (NULL: the thread's own); it takes nothing from the workspace. */
+int apds_dev_undistort_points(void* xy_dev, int n, int stride_bytes, const double* K, const double* dist, int n_dist, int iters, void* stream);
+/* cv::undistort's shape: dst (rows x cols x channels u8, packed, channels 1, 3 or 4; the size of src) = the image an ideal camera new_K
+ * (NULL: K) would have taken. Per destination pixel (u, v), no iteration: x = (u - cx') / fx', y = (v - cy') / fy' with new_K's entries,
+ * the forward model with K gives (us, vs), X = sat_int_rn(32 us), Y = sat_int_rn(32 vs), then the fixed-point bilinear sample of
+ * apds_warp_perspective (1/32-pixel fractions, 15-bit weights, (sum + 2^14) >> 15) with border value 0 in every channel, as in
+ * cv::undistort (the warp keeps the reference's 1). cv::initUndistortRectifyMap accumulates its map along the row, so bit parity with
+ * OpenCV is not claimed. No distortion and new_K NULL: dst = src, no launch. rows <= 65535. The device form is asynchronous on `stream`,
+ * takes its weight table from the calling thread's workspace, and needs dst_dev apart from src_dev (APDS_ERR_BAD_ARG otherwise). */
+int apds_undistort_image(const uint8_t* src, int rows, int cols, int channels, const double* K, const double* dist, int n_dist, const double* new_K,
+                         uint8_t* dst);
+int apds_dev_undistort_image(const void* src_dev, int rows, int cols, int channels, const double* K, const double* dist, int n_dist, const double* new_K,
+                             void* dst_dev, void* stream);
 
 /* apds_pnp_solver_ransac (mod.rs:320-369) on correspondences that are already on the device as the float values solvePnPRansac converts
  * its points to: obj_xyz_dev n x 3 floats, img_xy_dev n x 2 floats, ordered on `stream` (NULL: the thread's own). rvec, tvec, *n_inliers
@@ -638,6 +681,15 @@ int apds_pipeline_submit_select(void* pipe, const void* frame, size_t stride_byt
 #define APDS_PIPELINE_MATCH_RATIO 0
 #define APDS_PIPELINE_MATCH_CROSSCHECK 1
 int apds_pipeline_set_matcher(void* pipe, int matcher);
+/* The pipeline's lens (opt-in; a pipeline that never calls this, or calls it with no distortion, issues the launches it issued before).
+ * The image-side matched points of every frame are undistorted on the device (apds_dev_undistort_points, stride 8, `iters` steps, <= 0: 5)
+ * on the stage's own stream, with nothing more synchronised with the host: in the homography stage right after the matched-points gather
+ * and in front of the estimator (reproj_threshold is then in undistorted pixels); in the pose stage on img_xy right after
+ * apds_dev_pnp_correspondences. Only the matches are touched: the frame's keypoints, the match lists and every counter stay as they are.
+ * The pose stage keeps solving with apds_pipeline_pose_params.camera_intrinsic: the two K are expected to be the same matrix.
+ * Before the first submit (else APDS_ERR_BAD_ARG); the lens arguments are checked as apds_undistort_points checks them, before any device
+ * work. Plain, table and shard pipelines. */
+int apds_pipeline_set_lens(void* pipe, const double* K, const double* dist, int n_dist, int iters);
 
 /* ---- device-resident API ------------------------------------------------------------------- */
 /* All pointers below are HIP device pointers. stream: hipStream_t or NULL (the thread's own stream).

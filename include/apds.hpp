@@ -223,12 +223,10 @@ struct PNPRANSACSolution {
     Cmat<int32_t> inliers;
 };
 
-/// mod.rs:320-369 — solvePnPRansac(useExtrinsicGuess = false); dist_coeffs is accepted and ignored, as the reference shadows it with
-/// zeros(4,1) (mod.rs:344). Ok(nullopt) when no pose was found.
-inline Result<std::optional<PNPRANSACSolution>, MatError> pnp_solver_ransac(const std::vector<ImgObjCorrespondence>& point_correspondences,
-                                                                            const Cmat<double>& camera_intrinsic, int iter_count, float reproj_thres,
-                                                                            double confidence, std::optional<std::vector<double>> /*dist_coeffs*/,
-                                                                            std::optional<SolvePnPMethod> method) {
+/// the body of the two fronts below: dist == nullptr is apds_pnp_solver_ransac, anything else apds_pnp_solver_ransac_dist
+inline Result<std::optional<PNPRANSACSolution>, MatError> pnp_solve_(const std::vector<ImgObjCorrespondence>& point_correspondences,
+                                                                     const Cmat<double>& camera_intrinsic, int iter_count, float reproj_thres, double confidence,
+                                                                     const std::vector<double>* dist, std::optional<SolvePnPMethod> method) {
     using R = Result<std::optional<PNPRANSACSolution>, MatError>;
     const int n = (int)point_correspondences.size();
     std::vector<double> obj, img;
@@ -243,9 +241,12 @@ inline Result<std::optional<PNPRANSACSolution>, MatError> pnp_solver_ransac(cons
     Mat<double> rvec(3, 1), tvec(3, 1);
     std::vector<int32_t> inl((size_t)(n > 0 ? n : 1));
     int n_inl = 0, found = 0;
-    const int rc = apds_pnp_solver_ransac(obj.data(), img.data(), n, camera_intrinsic.mat.data.data(), iter_count, reproj_thres, confidence,
-                                          (int)method.value_or(SolvePnPMethod::SOLVEPNP_EPNP),   // mod.rs:360
-                                          rvec.data.data(), tvec.data.data(), inl.data(), &n_inl, &found);
+    const int m = (int)method.value_or(SolvePnPMethod::SOLVEPNP_EPNP);   // mod.rs:360
+    const int rc = dist ? apds_pnp_solver_ransac_dist(obj.data(), img.data(), n, camera_intrinsic.mat.data.data(), iter_count, reproj_thres, confidence, m,
+                                                      dist->empty() ? nullptr : dist->data(), (int)dist->size(), rvec.data.data(), tvec.data.data(), inl.data(),
+                                                      &n_inl, &found)
+                        : apds_pnp_solver_ransac(obj.data(), img.data(), n, camera_intrinsic.mat.data.data(), iter_count, reproj_thres, confidence, m,
+                                                 rvec.data.data(), tvec.data.data(), inl.data(), &n_inl, &found);
     if (rc != 0) return R::Err(MatError::opencv(last_error(rc)));
     if (!found) return R::Ok(std::nullopt);   // res.then_some(solution), mod.rs:367
     Mat<int32_t> im(n_inl, 1);
@@ -253,6 +254,57 @@ inline Result<std::optional<PNPRANSACSolution>, MatError> pnp_solver_ransac(cons
     PNPRANSACSolution sol{Cmat<double>::new_(std::move(rvec)).unwrap(), Cmat<double>::new_(std::move(tvec)).unwrap(),
                           Cmat<int32_t>::new_(std::move(im)).unwrap()};
     return R::Ok(std::optional<PNPRANSACSolution>(std::move(sol)));
+}
+
+/// mod.rs:320-369 — solvePnPRansac(useExtrinsicGuess = false); dist_coeffs is accepted and ignored, as the reference shadows it with
+/// zeros(4,1) (mod.rs:344). Ok(nullopt) when no pose was found.
+inline Result<std::optional<PNPRANSACSolution>, MatError> pnp_solver_ransac(const std::vector<ImgObjCorrespondence>& point_correspondences,
+                                                                            const Cmat<double>& camera_intrinsic, int iter_count, float reproj_thres,
+                                                                            double confidence, std::optional<std::vector<double>> /*dist_coeffs*/,
+                                                                            std::optional<SolvePnPMethod> method) {
+    return pnp_solve_(point_correspondences, camera_intrinsic, iter_count, reproj_thres, confidence, nullptr, method);
+}
+
+/// The same with the argument the reference documents (mod.rs:310,326): dist_coeffs (OpenCV's order; 4, 5 or 8 values) reach the solve - the
+/// image points are undistorted in f64 before solvePnPRansac's f32 conversion, reproj_thres is in undistorted pixels (include/apds.h).
+/// nullopt, an empty vector or all zeros is pnp_solver_ransac bit for bit.
+inline Result<std::optional<PNPRANSACSolution>, MatError> pnp_solver_ransac_dist(const std::vector<ImgObjCorrespondence>& point_correspondences,
+                                                                                 const Cmat<double>& camera_intrinsic, int iter_count, float reproj_thres,
+                                                                                 double confidence, std::optional<std::vector<double>> dist_coeffs,
+                                                                                 std::optional<SolvePnPMethod> method) {
+    const std::vector<double> none;
+    return pnp_solve_(point_correspondences, camera_intrinsic, iter_count, reproj_thres, confidence, dist_coeffs ? &*dist_coeffs : &none, method);
+}
+
+/// cv::undistortPoints with P = cameraMatrix: distorted pixels -> ideal pixels by exactly `iters` steps (<= 0: 5) of the fixed-point
+/// iteration; the lens model and its evaluation order: include/apds.h, csrc/lens_core.h. No distortion returns the input bits.
+inline Result<std::vector<Point2d>, MatError> undistort_points(const std::vector<Point2d>& points, const Cmat<double>& camera_matrix,
+                                                               const std::vector<double>& dist_coeffs, int iters = 5) {
+    using R = Result<std::vector<Point2d>, MatError>;
+    static_assert(sizeof(Point2d) == 2 * sizeof(double), "Point2d is two doubles");
+    if (camera_matrix.mat.rows != 3 || camera_matrix.mat.cols != 3) return R::Err(MatError::opencv(Error{APDS_ERR_ASSERT, "camera_matrix must be 3x3"}));
+    std::vector<Point2d> out(points.size());
+    const int rc = apds_undistort_points(reinterpret_cast<const double*>(points.data()), (int)points.size(), camera_matrix.mat.data.data(),
+                                         dist_coeffs.empty() ? nullptr : dist_coeffs.data(), (int)dist_coeffs.size(), iters, reinterpret_cast<double*>(out.data()));
+    if (rc != 0) return R::Err(from_status(rc));
+    return R::Ok(std::move(out));
+}
+
+/// cv::undistort: the image an ideal camera new_camera_matrix (nullopt: camera_matrix) would have taken; T = uint8_t, Vec3b, Vec4b;
+/// fixed-point bilinear as warp_image_perspective, border value 0.
+template <class T>
+inline Result<Cmat<T>, MatError> undistort_image(const Cmat<T>& src, const Cmat<double>& camera_matrix, const std::vector<double>& dist_coeffs,
+                                                 std::optional<Cmat<double>> new_camera_matrix = std::nullopt) {
+    using R = Result<Cmat<T>, MatError>;
+    static_assert(std::is_same_v<T, uint8_t> || std::is_same_v<T, Vec3b> || std::is_same_v<T, Vec4b>, "undistort_image: u8 elements with 1, 3 or 4 channels");
+    if (camera_matrix.mat.rows != 3 || camera_matrix.mat.cols != 3 || (new_camera_matrix && (new_camera_matrix->mat.rows != 3 || new_camera_matrix->mat.cols != 3)))
+        return R::Err(MatError::opencv(Error{APDS_ERR_ASSERT, "camera matrices must be 3x3"}));
+    Mat<T> out(src.mat.rows, src.mat.cols);
+    const int rc = apds_undistort_image(reinterpret_cast<const uint8_t*>(src.mat.data.data()), src.mat.rows, src.mat.cols, (int)sizeof(T),
+                                        camera_matrix.mat.data.data(), dist_coeffs.empty() ? nullptr : dist_coeffs.data(), (int)dist_coeffs.size(),
+                                        new_camera_matrix ? new_camera_matrix->mat.data.data() : nullptr, reinterpret_cast<uint8_t*>(out.data.data()));
+    if (rc != 0) return R::Err(from_status(rc));
+    return Cmat<T>::new_(std::move(out));
 }
 
 }  // namespace homographier

@@ -171,6 +171,20 @@ impl FramePipeline {
         Ok(())
     }
 
+    /// Gives the pipeline the camera's lens; before the first `submit`. `camera_intrinsic` row major 3x3, `dist_coeffs` as the
+    /// calibrator computes them (calibrator/src/main.rs:59-73; OpenCV's order, 4, 5 or 8 values; empty: no distortion), `iters` steps of
+    /// cv::undistortPoints' iteration (<= 0: 5). The image side of every frame's matches is undistorted on the device in front of the
+    /// homography and the pose; `reproj_threshold` / `reproj_thres` are then in undistorted pixels. `camera_intrinsic` is expected to be
+    /// the matrix `enable_pose` was given.
+    pub fn set_lens(&self, camera_intrinsic: [f64; 9], dist_coeffs: &[f64], iters: i32) -> Result<(), String> {
+        let dist = if dist_coeffs.is_empty() { ptr::null() } else { dist_coeffs.as_ptr() };
+        let rc = unsafe { apds_sys::apds_pipeline_set_lens(self.pipe, camera_intrinsic.as_ptr(), dist, dist_coeffs.len() as i32, iters) };
+        if rc != 0 {
+            return Err(err(rc));
+        }
+        Ok(())
+    }
+
     /// `poll` with the frame's pose (all zero, `found == false`, when the pose stage is off). A failed pose does not fail the frame: it is
     /// in `FramePose::status`.
     pub fn poll_pose(&self, wait: bool) -> Result<Option<(FrameResult, FramePose)>, String> {
