@@ -61,30 +61,42 @@ struct Batch {
     size_t stride = 0, img_stride = 0;
 };
 
-// akaze_filters.hip
+// (akaze_strip.h: the device-only helpers the filter files share - border indexing, lane shifts, the register-strip formulas)
+
+// akaze_base.hip: gray conversion, Gaussians, the contrast factor, and all of them in one pass on register strips
 void launch_gray(const void* img, int rows, int cols, int channels, size_t stride, float* out, hipStream_t s, const Batch& b);
 void launch_gauss(const float* src, float* dst, int w, int h, const GaussTaps& taps, int radius, hipStream_t s, const Batch& b);
-// strips: the interior on register strips and the frame around it on LDS tiles (two launches), else LDS tiles throughout
-void launch_smooth_flow(const float* src, float* smooth, float* flow, int w, int h, const GaussTaps& taps, const float* kptr, hipStream_t s, const Batch& b,
-                        bool strips);
 void launch_kcontrast(const float* smooth, float* modg_tmp, int w, int h, unsigned int* hmax_bits, int* hist, float* k_oct, int n_oct, hipStream_t s,
                       const Batch& b, bool gradient_done = false);
 void launch_base_strips(const void* img, int rows, int cols, int channels, size_t stride, const GaussTaps& g16, const GaussTaps& g10, float* Lt0, float* modg,
                         unsigned int* hmax_bits, bool want_modg, hipStream_t s, const Batch& b);
+
+// akaze_smooth_flow.hip
+// strips: the interior on register strips and the frame around it on LDS tiles (two launches), else LDS tiles throughout
+void launch_smooth_flow(const float* src, float* smooth, float* flow, int w, int h, const GaussTaps& taps, const float* kptr, hipStream_t s, const Batch& b,
+                        bool strips);
+
+// akaze_fed.hip
 // `nsteps` FED steps in one pass: register strips (1 .. 4 steps; half_out, optional: the 2 x 2 area means of Lnew as well, the next
 // octave's start image) or LDS tiles (1 .. 8 steps)
 void launch_nld_strips(const float* Lt, const float* Lf, float* Lnew, int w, int h, const float* step_sizes, int nsteps, hipStream_t s, const Batch& b,
                        float* half_out = nullptr);
 void launch_nld_tiles(const float* Lt, const float* Lf, float* Lnew, int w, int h, const float* step_sizes, int nsteps, hipStream_t s, const Batch& b);
+
+// akaze_level_strips.hip, akaze_level_stream.hip, akaze_level_fused.hip: a whole level step (smoothing, conductivity, FED steps) in one launch
 void launch_level_strips(const float* src, float* smooth, float* flow_out, float* Lnew, int w, int h, const GaussTaps& taps, const float* kptr,
                          const float* step_sizes, int nsteps, hipStream_t s, const Batch& b);
 void launch_level_stream(const float* src, float* smooth, float* flow_out, float* Lnew, int w, int h, const GaussTaps& taps, const float* kptr,
                          const float* step_sizes, int nsteps, hipStream_t s, const Batch& b, float* half_out = nullptr);
 void launch_level_fused(const float* src, float* smooth, float* flow_out, const float* flow_in, float* Lnew, int w, int h, const GaussTaps& taps,
                         const float* kptr, const float* step_sizes, int nsteps, hipStream_t s, const Batch& b, float* half_out = nullptr);
+
+// akaze_resize.hip
 void launch_half_sample(const float* src, int sw, float* dst, int dw, int dh, hipStream_t s, const Batch& b);
 void launch_area_resize(const float* src, int sw, float* dst, int dw, int dh, const int* xofs, const float* xw, const int* xcnt, const int* yofs,
                         const float* yw, const int* ycnt, hipStream_t s, const Batch& b);
+
+// akaze_doh_tiles.hip: determinant of the Hessian and 3x3 extrema on LDS tiles
 void launch_doh_fused(const float* Lsmooth, float2* Lxy, float* Ldet, int w, int h, int sc, float kside, float kmid, int border, float thr, uint8_t* mask,
                       uint32_t* list, int* list_count, hipStream_t s, const Batch& b);
 

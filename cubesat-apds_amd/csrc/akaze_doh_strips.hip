@@ -1,6 +1,6 @@
 // csrc/akaze_doh_strips.hip — a1.5 + a1.6 (determinant of the Hessian + 3x3 extrema) as a STREAMING kernel for the large levels.
 //
-// Replaces, for levels of at least 64 x 64 pixels, the LDS-tile kernel doh_fused_kernel (akaze_filters.hip), whose four phases walk
+// Replaces, for levels of at least 64 x 64 pixels, the LDS-tile kernel doh_fused_kernel (akaze_doh_tiles.hip), whose four phases walk
 // 2-D tiles with per-item index arithmetic: ~160 VALU instructions and ~38 LDS reads per pixel. Same values, bit for bit
 // (OpenCV's Compute_Determinant_Hessian_Response / Find_Scale_Space_Extrema behind feature_extraction/src/lib.rs:64-79; restated in
 // oracle/akaze_oracle.cpp): the filter is separable, so a wave that owns 64 columns (one per lane) and walks DOWN the rows needs its
@@ -27,22 +27,18 @@
 #include <mutex>
 
 #include "akaze.h"
+#include "akaze_strip.h"
 #include "config.h"
 
 namespace apds {
 
 namespace {
 
+// reflect101 (akaze_strip.h) without its n == 1 case - levels here are at least 64 x 64 - kept local: with the shared one the kernel
+// bodies change (profiles/filters_split/README.md)
 __device__ __forceinline__ int reflect101i(int i, int n) {
     while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
     return i;
-}
-// (lanes 63 / 0 have no source lane and keep whatever the destination register held: they are halo lanes)
-__device__ __forceinline__ float lane_next(float v) {   // lane i <- lane i + 1 (wave_shl:1)
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float lane_prev(float v) {   // lane i <- lane i - 1 (wave_shr:1)
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
 }
 
 // maxNum of finite-or-NaN floats as ONE instruction each: fmaxf() makes the compiler quiet every operand first (a v_max_f32 x, x per
@@ -192,7 +188,7 @@ __device__ __forceinline__ void doh_strip_rows(const DohStripArgs& a, uint32_t* 
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, d2), r_det, xo4, __builtin_amdgcn_readfirstlane(ok ? z * w * 4 : 0), 0);
             }
             // ---- extrema of row y = z - 1: strictly above the threshold and above its eight neighbours (rows z - 2, z - 1, z)
-            const float hs2 = vmax(lane_prev(d2), lane_next(d2));
+            const float hs2 = vmax(lane_prev_any(d2), lane_next_any(d2));
             const float hm2 = vmax(hs2, d2);
             {
                 // "v <= thr or v <= some neighbour" is "v <= max(thr, neighbours)"; a NaN neighbour drops out of the maximum exactly as its

@@ -1,5 +1,5 @@
 // csrc/akaze_extract.hip — the AKAZE extraction driver: one call = one batch of equal-sized device images through the plan of
-// akaze_plan.h, the filter launchers (akaze_filters.hip and the strip / stream files) and the keypoint launchers (akaze_suppress.hip,
+// akaze_plan.h, the filter launchers (the stage files akaze_base / _smooth_flow / _fed / _level_* / _resize / _doh_* .hip) and the keypoint launchers (akaze_suppress.hip,
 // akaze_compact.hip, akaze_describe.hip).
 //
 // Replaces cv::AKAZE::detectAndCompute (AKAZEFeatures::Create_Nonlinear_Scale_Space, Feature_Detection, Compute_Descriptors) behind

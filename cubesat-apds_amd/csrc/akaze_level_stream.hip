@@ -14,24 +14,17 @@
 //                     t_S(u-3-S) -> the level's new Lt (stored)
 //
 // so a band of R rows costs R + 2 (S + 3) row steps instead of R x 1.75. Same operations in the same order as level_strip /
-// smooth_flow_kernel / nld_point (the float contract of akaze_filters.hip): bit-identical planes. Borders as there: the Gaussian
+// smooth_flow_kernel / nld_point (the float contract of akaze_strip.h): bit-identical planes. Borders as there: the Gaussian
 // replicates (clamped loads), the Scharr pass reflects (lane selects at x = 0 / w - 1, the other row at y = 0 / h - 1), a flux across
 // the image edge is +0 and the four corner pixels keep their value. Reference: OpenCV's Create_Nonlinear_Scale_Space behind
 // feature_extraction/src/lib.rs:64-79 (restated in oracle/akaze_oracle.cpp).
 #include "akaze.h"
+#include "akaze_strip.h"
 #include "config.h"
 
 namespace apds {
 
 namespace {
-
-__device__ __forceinline__ int clampi_(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
-__device__ __forceinline__ float lane_next(float v) {   // lane i <- lane i + 1 (wave_shl:1; lane 63 keeps garbage: a halo lane)
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float lane_prev(float v) {   // lane i <- lane i - 1 (wave_shr:1)
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
-}
 
 struct StreamSteps {
     float v[4];
@@ -58,12 +51,14 @@ __device__ __forceinline__ void level_stream_rows(const LevelStreamArgs& a, int 
     const int gx = strip * VW - H + lane;
     const int y0 = band * a.rb, y1 = min(y0 + a.rb, h);
     const bool mine = lane >= H && lane < 64 - H && gx < w;   // (gx >= 0 for these lanes)
+    // (the per-point formulas of akaze_strip.h - gauss5, scharr_row_terms, pm_g2_strip - stand written out in the row loop below: taking
+    // them changed these kernels' bodies and registers, profiles/filters_split/README.md; clampi and the lane shifts are the header's)
     const float k0 = a.taps.k[0], k1 = a.taps.k[1], k2 = a.taps.k[2];
     const float kc = *a.kptr;
     const float k2inv = 1.0f / (kc * kc);
     const int plane_bytes = w * h * 4;
     const __amdgpu_buffer_rsrc_t r_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.src), 0, plane_bytes, 0x00020000);
-    const int cx4 = 4 * (XEDGE ? clampi_(gx, w) : gx);            // replicate in x: what the Gaussian wants
+    const int cx4 = 4 * (XEDGE ? clampi(gx, w) : gx);             // replicate in x: what the Gaussian wants
     constexpr int DROP = (int)0x80000000;                          // stores of lanes without an output column fall outside every plane
     const int xo4 = mine ? 4 * gx : DROP;
     const bool at_x0 = gx == 0, at_x1 = gx == w - 1;
@@ -72,7 +67,7 @@ __device__ __forceinline__ void level_stream_rows(const LevelStreamArgs& a, int 
     const int u0 = y0 - H;                                          // first source row of the walk
     const int T = (y1 - y0) + 2 * H;                                // row steps: the last one finishes output row y1 - 1
     auto load_row = [&](int u) -> float {
-        const int r = YEDGE ? clampi_(u, h) : min(u, h - 1);       // replicate in y (interior bands never leave the image upwards)
+        const int r = YEDGE ? clampi(u, h) : min(u, h - 1);        // replicate in y (interior bands never leave the image upwards)
         return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_src, cx4, __builtin_amdgcn_readfirstlane(r * w * 4), 0));
     };
     // a store of a row outside [y0, y1) goes through a zero-length descriptor at offset 0: dropped (see akaze_doh_strips.hip)
@@ -94,8 +89,8 @@ __device__ __forceinline__ void level_stream_rows(const LevelStreamArgs& a, int 
     float hprev = 0.0f;
     auto store_half = [&](float out, int row) {
         // rows row - 1 (hprev) and row; stored when row is odd and both lie in [y0, y1) (y0 is even, so row - 1 >= y0 whenever row > y0)
-        const float top = hprev + lane_next(hprev);
-        const float bot = out + lane_next(out);
+        const float top = hprev + lane_next_any(hprev);
+        const float bot = out + lane_next_any(out);
         const bool ok = (row & 1) && row > y0 && row < y1;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.half, 0, ok ? half_bytes : 0, 0x00020000);
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, (top + bot) * 0.25f), rs, hx4, __builtin_amdgcn_readfirstlane(ok ? (row >> 1) * hw * 4 : 0), 0);
@@ -121,8 +116,8 @@ __device__ __forceinline__ void level_stream_rows(const LevelStreamArgs& a, int 
             const float v = cur[j];
             P[j & 7] = v;
             {
-                const float l1 = lane_prev(v), r1 = lane_next(v);
-                const float l2 = lane_prev(l1), r2 = lane_next(r1);
+                const float l1 = lane_prev_any(v), r1 = lane_next_any(v);
+                const float l2 = lane_prev_any(l1), r2 = lane_next_any(r1);
                 float acc = k0 * v;
                 acc += k1 * (l1 + r1);
                 acc += k2 * (l2 + r2);
@@ -135,7 +130,7 @@ __device__ __forceinline__ void level_stream_rows(const LevelStreamArgs& a, int 
             store_row(a.smooth, ls, u - 2);
             // ---- stage C: Scharr row terms of Lsmooth(u - 2)
             {
-                float l = lane_prev(ls), rr = lane_next(ls);
+                float l = lane_prev_any(ls), rr = lane_next_any(ls);
                 if (XEDGE) {                  // reflect-101 in x
                     const float l0 = l;
                     l = at_x0 ? rr : l;
@@ -166,7 +161,7 @@ __device__ __forceinline__ void level_stream_rows(const LevelStreamArgs& a, int 
                 const float f = 1.0f / (1.0f + ((ax * ax + ay * ay) * k2inv));
                 F[(j - 3) & 7] = f;
                 if (FLOW_OUT) store_row(a.flow_out, f, vr);
-                FX[(j - 3) & 7] = f + lane_next(f);                 // the x pair sum of the FED steps: (f[x] + f[x+1])
+                FX[(j - 3) & 7] = f + lane_next_any(f);                 // the x pair sum of the FED steps: (f[x] + f[x+1])
                 FY[(j - 4) & 7] = F[(j - 4) & 7] + f;               // the y pair sum of row u - 4: (f[r] + f[r+1])
             }
             // ---- FED steps: step s finishes row u - 3 - s from t_(s-1) of that row and the next one
@@ -175,12 +170,12 @@ __device__ __forceinline__ void level_stream_rows(const LevelStreamArgs& a, int 
                 const int lag = 3 + s, rho = u - lag;
                 const float tc = s == 1 ? P[(j - lag) & 7] : TT[s - 2][(j - lag) & 1];
                 const float tn = s == 1 ? P[(j - lag + 1) & 7] : TT[s - 2][(j - lag + 1) & 1];   // row rho + 1 (step s - 1 made it in this row step)
-                const float d = lane_next(tc) - tc;
+                const float d = lane_next_any(tc) - tc;
                 float px = FX[(j - lag) & 7] * d;
                 if (XEDGE && !flux_x_inside) px = 0.0f;
                 float q = FY[(j - lag) & 7] * (tn - tc);
                 if (YEDGE && !(rho >= 0 && rho + 1 <= h - 1)) q = 0.0f;
-                float sum = px - lane_prev(px);
+                float sum = px - lane_prev_any(px);
                 sum = sum + q;
                 sum = sum - qprev[s - 1];
                 float out = tc + sum * a.steps.v[s - 1];

@@ -1,24 +1,15 @@
 // csrc/akaze_level_strips.hip — one AKAZE evolution level step on register strips (a translation unit of its own: the sixteen
-// fully unrolled variants take minutes to compile, beside akaze_filters.hip instead of inside it).
+// fully unrolled variants take minutes to compile).
 //
 // Replaces the OpenCV work behind /root/reference/feature_extraction/src/lib.rs:64-79 (AKAZE::create(...).detect_and_compute) for
 // the large levels of the nonlinear scale space: Gaussian smoothing, Scharr derivatives, Perona-Malik g2 conductivity and the first
-// FED steps of a level in one pass. Float contract as in akaze_filters.hip (one IEEE binary32 operation per source operation,
-// -ffp-contract=off).
+// FED steps of a level in one pass. Float contract as in akaze_strip.h (one IEEE binary32 operation per source operation,
+// -ffp-contract=off), whose strip formulas every stage here is made of.
 #include "akaze.h"
+#include "akaze_strip.h"
 
 namespace apds {
 
-__device__ __forceinline__ int clampi(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
-#define APDS_BOFS(p) p = bofs(p, bstride)
-__device__ __forceinline__ float dpp_next(float v) {   // lane i <- lane i + 1
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float dpp_prev(float v) {   // lane i <- lane i - 1
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float dpp_from_next_lane(float v) { return dpp_next(v); }   // wave_shl:1 (lane 63: unspecified, a halo lane)
-__device__ __forceinline__ float dpp_from_prev_lane(float v) { return dpp_prev(v); }   // wave_shr:1 (lane 0: unspecified, a halo lane)
 #ifndef APDS_STRIP_WIDE_FROM
 #define APDS_STRIP_WIDE_FROM 3   // level_strip_kernel<S> with S >= this may use up to 168 VGPRs (three waves per SIMD) instead of spilling at 128
 #endif
@@ -57,15 +48,7 @@ __device__ __forceinline__ void level_strip(const float* __restrict__ src, float
 #pragma unroll
     for (int r = 0; r < RF; r++) t[r] = sr[r + 3];
 #pragma unroll
-    for (int r = 0; r < R; r++) {         // Gaussian rows, in place
-        const float v = sr[r];
-        const float l1 = dpp_prev(v), r1 = dpp_next(v);
-        const float l2 = dpp_prev(l1), r2 = dpp_next(r1);
-        float acc = taps.k[0] * v;
-        acc += taps.k[1] * (l1 + r1);
-        acc += taps.k[2] * (l2 + r2);
-        sr[r] = acc;
-    }
+    for (int r = 0; r < R; r++) sr[r] = gauss5_row(taps, sr[r]);   // Gaussian rows, in place
     const bool mine = lane >= H && lane < 64 - H && gx < w;   // (gx >= 0 for these lanes: gx0 >= -H)
     float rd[RS], rs[RS];
     {
@@ -73,23 +56,12 @@ __device__ __forceinline__ void level_strip(const float* __restrict__ src, float
 #pragma unroll
         for (int q = 0; q < RS; q++) {    // Gaussian columns -> Lsmooth row q; its Scharr row terms
             const int r = q + 2;
-            float acc = taps.k[0] * sr[r];
-            acc += taps.k[1] * (sr[r - 1] + sr[r + 1]);
-            acc += taps.k[2] * (sr[r - 2] + sr[r + 2]);
+            const float acc = gauss5(taps, sr[r], sr[r - 1], sr[r + 1], sr[r - 2], sr[r + 2]);
             if (q >= S + 1 && q < S + 1 + RB) {
                 const int gy = y0 + q - (S + 1);
                 if (mine && (!BORDER || gy < h)) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, acc), rs_sm, 4 * gx, gy * w * 4, 0);
             }
-            float l = dpp_prev(acc), rr = dpp_next(acc);
-            if (BORDER) {                 // reflect-101 in x
-                const float l0 = l;
-                l = gx == 0 ? rr : l;
-                rr = gx == w - 1 ? l0 : rr;
-            }
-            rd[q] = rr - l;
-            float a = 10.0f * acc;
-            a += 3.0f * (l + rr);
-            rs[q] = a;
+            scharr_row_terms<BORDER>(acc, gx, w, rd[q], rs[q]);   // reflect-101 in x
         }
     }
     float f[RF];
@@ -108,10 +80,7 @@ __device__ __forceinline__ void level_strip(const float* __restrict__ src, float
                 rsd = rs[q - 1];
             }
         }
-        float ax = 10.0f * rd[q];
-        ax += 3.0f * (rdu + rdd);
-        const float ay = rsd - rsu;
-        f[r] = 1.0f / (1.0f + ((ax * ax + ay * ay) * k2inv));
+        f[r] = pm_g2_strip(rdu, rd[q], rdd, rsu, rsd, k2inv);
     }
     if (FLOW_OUT) {
         const __amdgpu_buffer_rsrc_t rs_fl = __builtin_amdgcn_make_buffer_rsrc(flow_out, 0, plane_bytes, 0x00020000);
@@ -121,7 +90,7 @@ __device__ __forceinline__ void level_strip(const float* __restrict__ src, float
             if (mine && (!BORDER || gy < h)) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, f[r]), rs_fl, 4 * gx, gy * w * 4, 0);
         }
     }
-    // FED steps: nld_strip on the rows / lanes that are left (strip row 3 is row 0 here)
+    // FED steps: nld_strip's loop (akaze_fed.hip, where its exactness argument stands) on the rows / lanes that are left (strip row 3 is row 0 here)
     const int yf = y0 - S;
     const bool flux_x_inside = gx >= 0 && gx + 1 <= w - 1;
     const bool edge_col = gx == 0 || gx == w - 1;
@@ -133,12 +102,12 @@ __device__ __forceinline__ void level_strip(const float* __restrict__ src, float
 #pragma unroll
         for (int r = j; r < RF - j; r++) {
             const float tc = t[r];
-            const float d = dpp_from_next_lane(tc) - tc;
-            float P = (f[r] + dpp_from_next_lane(f[r])) * d;
+            const float d = lane_next(tc) - tc;
+            float P = (f[r] + lane_next(f[r])) * d;
             if (BORDER && !flux_x_inside) P = 0.0f;
             float q = (f[r] + f[r + 1]) * (t[r + 1] - tc);
             if (BORDER && !(yf + r >= 0 && yf + r + 1 <= h - 1)) q = 0.0f;
-            float sum = P - dpp_from_prev_lane(P);
+            float sum = P - lane_prev(P);
             sum = sum + q;
             sum = sum - qprev;
             float out = tc + sum * tau;

@@ -177,7 +177,7 @@ struct PlanSwitches {
     bool fork = false;
 };
 
-static constexpr int LEVEL_FUSED_MAX_STEPS = 29;      // level_fused_kernel's capacity (akaze_filters.hip asserts its LF_MAX_STEPS against it)
+static constexpr int LEVEL_FUSED_MAX_STEPS = 29;      // level_fused_kernel's capacity (akaze_level_fused.hip asserts its LF_MAX_STEPS against it)
 static constexpr int SF_TILE_W = 64, SF_TILE_H = 32;  // smooth_flow_kernel's tile
 
 enum class Head { None, Stream, Strips, Fused };      // pass 0 with the smoothing in it: level_stream / level_strip / level_fused_kernel

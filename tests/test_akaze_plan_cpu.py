@@ -41,7 +41,7 @@ def plan(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def LF_MAX_STEPS(plan):
-    return plan.akaze_plan_fused_max_steps()   # level_fused_kernel's capacity (csrc/akaze_plan.h; akaze_filters.hip asserts its own against it)
+    return plan.akaze_plan_fused_max_steps()   # level_fused_kernel's capacity (csrc/akaze_plan.h; akaze_level_fused.hip asserts its own against it)
 
 
 def plan_levels(plan, w, h):
