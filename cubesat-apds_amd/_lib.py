@@ -50,6 +50,8 @@ SYMBOLS = [
     "apds_db_ids", "apds_db_read_keypoint_from_id", "apds_db_delete_where", "apds_db_delete_ids",
     "apds_distort_points", "apds_undistort_points", "apds_dev_undistort_points", "apds_undistort_image", "apds_dev_undistort_image",
     "apds_pnp_solver_ransac_dist", "apds_pipeline_set_lens",
+    "apds_akaze_extract_float", "apds_akaze_extract_float_batch", "apds_dev_akaze_extract_float", "apds_dev_akaze_extract_float_batch",
+    "apds_dev_akaze_describe_float",
 ]
 
 RESAMPLE_NEAREST, RESAMPLE_LANCZOS = 0, 1
@@ -57,6 +59,9 @@ RESAMPLE_MODES = {"nearest": RESAMPLE_NEAREST, "lanczos": RESAMPLE_LANCZOS}
 TILE_MASK_NONE, TILE_MASK_ALPHA = 0, 1     # APDS_TILE_MASK_*: the mask_mode of the apds_*tile_extract*_ex calls
 TILE_MASK_ALPHA_SUPPORT = 3                # the alpha mask with MASK_SUPPORT_DESCRIPTOR
 MASK_SUPPORT_DESCRIPTOR = 15               # APDS_MASK_SUPPORT_DESCRIPTOR: the mask support that covers the descriptor lattice at any orientation
+AKAZE_DESCRIPTOR_KAZE, AKAZE_DESCRIPTOR_MLDB = 3, 5   # APDS_AKAZE_DESCRIPTOR_*: OpenCV's enum values
+AKAZE_DESCRIPTORS = {"kaze": AKAZE_DESCRIPTOR_KAZE, "mldb": AKAZE_DESCRIPTOR_MLDB}
+DESC_FLOAT_DIM = 64                        # APDS_DESC_FLOAT_DIM: floats per row of the "kaze" descriptor
 
 
 def resample_mode(name):
@@ -313,6 +318,11 @@ def lib():
             "apds_dev_undistort_image": (i, [vp, i, i, i, vp, vp, i, vp, vp, vp]),
             "apds_pnp_solver_ransac_dist": (i, [vp, vp, i, vp, i, f, d, i, vp, i, vp, vp, vp, ip, ip]),
             "apds_pipeline_set_lens": (i, [vp, vp, vp, i, i]),
+            "apds_akaze_extract_float": (i, [vp, i, i, i, sz, vp, sz, i, i, pp, pp, ip, ip]),
+            "apds_akaze_extract_float_batch": (i, [vp, i, sz, i, i, i, sz, vp, sz, i, i, pp, pp, ip, ip]),
+            "apds_dev_akaze_extract_float": (i, [vp, i, i, i, sz, vp, sz, i, i, vp, vp, i, ip, vp]),
+            "apds_dev_akaze_extract_float_batch": (i, [vp, i, sz, i, i, i, sz, vp, sz, sz, i, i, vp, vp, i, ip, vp]),
+            "apds_dev_akaze_describe_float": (i, [vp, i, i, vp, i, vp, vp]),
         }
         for name, (rt, at) in sig.items():
             fn = getattr(L, name)

@@ -142,9 +142,18 @@ void compact_strongest(const LevelTable& Tb, const SlabLayout& sl, size_t slab_b
 
 // akaze_describe.hip: main orientation + M-LDB descriptor of keypoints [range[0], min(range[1], n_cap)) of every image (range: two ints of
 // image 0's slab) or, range == nullptr, of keypoints [0, n_cap). `blocks`: grid width (the kernels stride over the keypoints).
-void describe_keypoints(const LevelTable& T, apds_keypoint* kps, const int* range, int n_cap, size_t kp_bstride, uint8_t* desc64, size_t desc_bstride,
-                        int blocks, int batch, int xcd_ranges, hipStream_t s);
+// descriptor: APDS_AKAZE_DESCRIPTOR_MLDB - rows of 64 bytes at desc; APDS_AKAZE_DESCRIPTOR_KAZE - rows of 64 floats (akaze_describe_msurf.hip runs
+// behind the orientation kernel instead of the M-LDB kernel). desc_bstride: bytes between the images' row blocks.
+void describe_keypoints(const LevelTable& T, apds_keypoint* kps, const int* range, int n_cap, size_t kp_bstride, uint8_t* desc, size_t desc_bstride,
+                        int blocks, int batch, int xcd_ranges, hipStream_t s, int descriptor = APDS_AKAZE_DESCRIPTOR_MLDB);
 void pack_desc61_device(const uint8_t* d64, int n, uint8_t* d61, hipStream_t s);
+
+// akaze_describe_msurf.hip: the 64-float M-SURF descriptor of the same keypoint ranges (their angles are final: the orientation kernel has run).
+// plane_level >= 0: all keypoints are described on that level of T whatever their class_id.
+void launch_msurf(const LevelTable& T, const apds_keypoint* kps, const int* range, int n_cap, size_t kp_bstride, float* desc, size_t desc_bstride, int blocks,
+                  int batch, int xcd_ranges, int plane_level, hipStream_t s);
+// ... of n keypoints [0, n) on one h x w plane of interleaved (Lx, Ly)
+void msurf_describe_plane_device(const float2* lxy, int w, int h, const apds_keypoint* kps, int n, float* desc, hipStream_t s);
 
 // akaze_extract.hip (host driver: kernels.h declares akaze_extract_device)
 // Test hook: when armed (per thread) the next akaze_extract_device copies one intermediate plane to the host.

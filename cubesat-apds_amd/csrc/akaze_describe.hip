@@ -2,6 +2,7 @@
 //
 // Replaces OpenCV AKAZEFeatures::Compute_Main_Orientation and MLDB_Full_Descriptor_Invoker behind feature_extraction/src/lib.rs:79.
 #include "akaze.h"
+#include "akaze_describe.h"
 #include "config.h"
 
 namespace apds {
@@ -55,29 +56,6 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
     if (y < 0) a = 360.f - a;
     return a;
 }
-
-// The per-keypoint kernels below give every wave its own slices of the block's LDS arrays: what one phase writes, only the same wave reads in
-// the next. The LDS unit executes a wave's instructions in issue order, so a later read sees an earlier write without any wait; all that is
-// needed between two phases is that the compiler does not move LDS accesses across the boundary. (Round 2 used __syncthreads() here: three
-// block-wide rendezvous per keypoint in the descriptor kernel and seven in the orientation kernel tied four independent waves together.
-// Same time either way - the descriptor kernel waits for HBM, see below - but nothing is left that needs the block to move in step.)
-__device__ __forceinline__ void wave_lds_phase() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// Keypoints [range[0], min(range[1], n_cap)) of this image (range: two consecutive ints of the image's slab, written by the stage's
-// scan; nullptr: [0, n_cap)): the counts stay on the device, and the blocks stride over the range, so the grid need not match it.
-// Which groups of four keypoints a block takes. Plain: block b takes groups b, b + gridDim.x, ... XCD-aware (xcd_ranges): workgroups are
-// dealt round-robin over the 8 XCDs, so block b runs on XCD b % 8; that XCD gets ONE contiguous eighth of the groups and its blocks walk
-// it in order. Keypoints are in level-major, row-major order: neighbours in the list are neighbours in the image, their sample patches
-// overlap, and one XCD's L2 then serves both instead of two L2s fetching the same lines.
-#define KP_GROUP_LOOP(kb, begin, n, xcd_ranges)                                                                                          \
-    const int kp_groups_ = ((n) - (begin) + 3) >> 2, kp_nbx_ = ((int)gridDim.x + 7) >> 3;                                               \
-    const int kp_x_ = (int)blockIdx.x & 7, kp_lo_ = (int)((long long)kp_groups_ * kp_x_ >> 3), kp_hi_ = (int)((long long)kp_groups_ * (kp_x_ + 1) >> 3); \
-    const int kp_first_ = (xcd_ranges) ? kp_lo_ + ((int)blockIdx.x >> 3) : (int)blockIdx.x, kp_end_ = (xcd_ranges) ? kp_hi_ : kp_groups_; \
-    const int kp_stride_ = (xcd_ranges) ? kp_nbx_ : (int)gridDim.x;                                                                       \
-    for (int kg_ = kp_first_, kb = (begin) + 4 * kg_; kg_ < kp_end_; kg_ += kp_stride_, kb = (begin) + 4 * kg_)
 
 __global__ __launch_bounds__(256) void orientation_kernel(LevelTable T, apds_keypoint* __restrict__ kps, const int* __restrict__ range, int n_cap, size_t kp_bstride,
                                                           float ang_step, int nkeys, int xcd_ranges) {
@@ -220,38 +198,6 @@ __global__ __launch_bounds__(256) void orientation_kernel(LevelTable T, apds_key
 }
 
 // ---- a1.9 M-LDB 486-bit descriptor: one wave per keypoint ----------------------------------------------------------
-// deterministic double sin/cos on [0, 2pi] (Cody-Waite reduction + Taylor/Horner; same arithmetic as the oracle)
-__device__ __forceinline__ void det_sincos(double a, double& s, double& c) {
-    const double two_over_pi = 0.63661977236758134308;
-    const double pio2_hi = 1.57079632673412561417e+00, pio2_lo = 6.07710050650619224932e-11;
-    const int k = (int)(a * two_over_pi + 0.5);
-    const double r = (a - k * pio2_hi) - k * pio2_lo;
-    const double r2 = r * r;
-    double ps = -7.6471637318198164759e-13;          // -1/15!
-    ps = ps * r2 + 1.6059043836821614599e-10;        //  1/13!
-    ps = ps * r2 + -2.5052108385441718775e-08;       // -1/11!
-    ps = ps * r2 + 2.7557319223985890653e-06;        //  1/9!
-    ps = ps * r2 + -1.9841269841269841270e-04;       // -1/7!
-    ps = ps * r2 + 8.3333333333333333333e-03;        //  1/5!
-    ps = ps * r2 + -1.6666666666666666667e-01;       // -1/3!
-    const double sr = r + r * (r2 * ps);
-    double pc = 4.7794773323873852974e-14;           //  1/16!
-    pc = pc * r2 + -1.1470745597729724714e-11;       // -1/14!
-    pc = pc * r2 + 2.0876756987868098979e-09;        //  1/12!
-    pc = pc * r2 + -2.7557319223985890653e-07;       // -1/10!
-    pc = pc * r2 + 2.4801587301587301587e-05;        //  1/8!
-    pc = pc * r2 + -1.3888888888888888889e-03;       // -1/6!
-    pc = pc * r2 + 4.1666666666666666667e-02;        //  1/4!
-    pc = pc * r2 + -0.5;
-    const double cr = 1.0 + r2 * pc;
-    switch (k & 3) {
-        case 0: s = sr; c = cr; break;
-        case 1: s = cr; c = -sr; break;
-        case 2: s = -sr; c = -cr; break;
-        default: s = -cr; c = sr; break;
-    }
-}
-
 struct MldbLut {
     uint8_t a[488], b[488];
 };
@@ -445,12 +391,16 @@ void pack_desc61_device(const uint8_t* d64, int n, uint8_t* d61, hipStream_t s) 
     hipLaunchKernelGGL(pack_desc61_kernel, dim3(ceil_div((long long)n * 61, 256)), dim3(256), 0, s, d64, n, d61);
 }
 
-void describe_keypoints(const LevelTable& T, apds_keypoint* kps, const int* range, int n_cap, size_t kp_bstride, uint8_t* desc64, size_t desc_bstride,
-                        int blocks, int batch, int xcd_ranges, hipStream_t s) {
+void describe_keypoints(const LevelTable& T, apds_keypoint* kps, const int* range, int n_cap, size_t kp_bstride, uint8_t* desc, size_t desc_bstride,
+                        int blocks, int batch, int xcd_ranges, hipStream_t s, int descriptor) {
     const float ang_step = (float)(2.0 * M_PI / 42);
     const int nkeys = (int)((float)(2.0 * M_PI) / ang_step);
     hipLaunchKernelGGL(orientation_kernel, dim3(blocks, 1, batch), dim3(256), 0, s, T, kps, range, n_cap, kp_bstride, ang_step, nkeys, xcd_ranges);
+    if (descriptor == APDS_AKAZE_DESCRIPTOR_KAZE) {
+        launch_msurf(T, kps, range, n_cap, kp_bstride, reinterpret_cast<float*>(desc), desc_bstride, blocks, batch, xcd_ranges, -1, s);
+        return;
+    }
     hipLaunchKernelGGL(mldb_kernel, dim3(blocks, 1, batch), dim3(256), 0, s, T, (const apds_keypoint*)kps, range, n_cap, kp_bstride,
-                       reinterpret_cast<uint32_t*>(desc64), desc_bstride, xcd_ranges);
+                       reinterpret_cast<uint32_t*>(desc), desc_bstride, xcd_ranges);
 }
 }  // namespace apds

@@ -353,7 +353,8 @@ void report_host_time(int every, std::chrono::steady_clock::time_point t0, const
 
 // Some image has more keypoints than max_points (rare): those images again, through the rank selection (response descending, ties by
 // detection order) over ALL their K[bi] keypoints; the tables of image bi are image 0's shifted by bi slabs.
-void select_strongest(const Frame& f, const LevelTable& T, const int* K, const int* counts, int max_points, apds_keypoint* kps_out, uint8_t* desc64_out, int capacity) {
+void select_strongest(const Frame& f, const LevelTable& T, const int* K, const int* counts, int max_points, apds_keypoint* kps_out, uint8_t* desc_out, int capacity,
+                      int descriptor, size_t row_bytes) {
     const size_t slab = f.bt.stride;
     for (int bi = 0; bi < f.bt.n; bi++) {
         if (K[bi] <= max_points) continue;
@@ -368,7 +369,7 @@ void select_strongest(const Frame& f, const LevelTable& T, const int* K, const i
         const int keep = counts[bi];
         apds_keypoint* kp_b = kps_out + (size_t)bi * capacity;
         compact_strongest(Tb, f.sl, slab, bi, K[bi], keep, kp_b, f.s);
-        describe_keypoints(Tb, kp_b, nullptr, keep, 0, desc64_out + (size_t)bi * capacity * 64, 0, ceil_div(keep, 4), 1, 0, f.s);
+        describe_keypoints(Tb, kp_b, nullptr, keep, 0, desc_out + (size_t)bi * capacity * row_bytes, 0, ceil_div(keep, 4), 1, 0, f.s, descriptor);
     }
     HIP_CHECK(hipGetLastError());
     // these kernels read the calling thread's workspace (kps_all, masks, planes): the same thread's NEXT call, possibly on another
@@ -380,13 +381,17 @@ void select_strongest(const Frame& f, const LevelTable& T, const int* K, const i
 
 // feature_extraction/src/lib.rs:61-92 on `n_img` device images of one size (a batch goes through every kernel's grid together:
 // gridDim.z = n_img; a single image is a batch of one). Image i starts `img_bstride` bytes after image i-1; its keypoints go to
-// kps_out + i * capacity, its descriptors to desc64_out + i * capacity * 64, its count to counts[i] (host). Returns the largest count.
+// kps_out + i * capacity, its descriptors to desc_out + i * capacity rows (64 bytes each, or 64 floats for APDS_AKAZE_DESCRIPTOR_KAZE), its
+// count to counts[i] (host). Returns the largest count.
 // pmask: the detection mask (a null base = none): keypoints whose refined position rounds onto a zero byte are dropped before the count,
 // so max_points and `capacity` are about the survivors. mask_support > 0: any zero byte within mask_support units of the keypoint's level
 // (akaze_plan.h: mask_support_unit) of that position drops it; the mask's summed-area table is built in the workspace for that.
 int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, int rows, int cols, int channels, size_t stride, const PixelMask& pmask,
-                               int mask_support, int max_points, apds_keypoint* kps_out, uint8_t* desc64_out, int capacity, int* counts, hipStream_t s) {
+                               int mask_support, int max_points, apds_keypoint* kps_out, uint8_t* desc_out, int capacity, int* counts, hipStream_t s,
+                               int descriptor) {
     APDS_REQUIRE(img != nullptr, APDS_ERR_BAD_ARG, "null image");
+    APDS_REQUIRE(descriptor == APDS_AKAZE_DESCRIPTOR_MLDB || descriptor == APDS_AKAZE_DESCRIPTOR_KAZE, APDS_ERR_BAD_ARG, "unknown descriptor kind");
+    const size_t row_bytes = descriptor == APDS_AKAZE_DESCRIPTOR_KAZE ? APDS_DESC_FLOAT_DIM * sizeof(float) : 64;
     APDS_REQUIRE(n_img >= 1 && n_img <= 4096, APDS_ERR_BAD_ARG, "batch must hold 1 .. 4096 images");
     APDS_REQUIRE(channels == 1 || channels == 3 || channels == 4, APDS_ERR_ASSERT, "image must have 1, 3 or 4 channels");
     APDS_REQUIRE(rows > 2 && cols > 2, APDS_ERR_ASSERT, "image must be larger than 2x2");   // AKAZE CV_Assert(img_height > 2 && img_width > 2)
@@ -461,8 +466,8 @@ int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, i
     // ---- a1.8 / a1.9 over the image's keypoints [kp_base[0], kp_base[1]), capped at the output capacity. The per-keypoint kernels stride over
     // them: the grid only has to be of the right order (this thread's last image)
     const int kp_blocks = (std::min(16384, std::max(256, ceil_div((long long)(c.akaze_kp_estimate > 0 ? c.akaze_kp_estimate : 32768) * 5 / 4, 4))) + 7) & ~7;
-    describe_keypoints(T, kps_out, f.sl.kp_base, std::min(capacity, max_points), (size_t)capacity * sizeof(apds_keypoint), desc64_out, (size_t)capacity * 64,
-                       kp_blocks, B, config().kp_xcd ? 1 : 0, s);
+    describe_keypoints(T, kps_out, f.sl.kp_base, std::min(capacity, max_points), (size_t)capacity * sizeof(apds_keypoint), desc_out, (size_t)capacity * row_bytes,
+                       kp_blocks, B, config().kp_xcd ? 1 : 0, s, descriptor);
     HIP_CHECK(hipGetLastError());
 
     copy_debug_plane(f, dbg);
@@ -487,14 +492,14 @@ int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, i
         APDS_REQUIRE(counts[bi] <= capacity, APDS_ERR_ASSERT, "output capacity smaller than the keypoint count");
     }
     c.akaze_kp_estimate = kmax;
-    if (over) select_strongest(f, T, K, counts, max_points, kps_out, desc64_out, capacity);
+    if (over) select_strongest(f, T, K, counts, max_points, kps_out, desc_out, capacity, descriptor, row_bytes);
     return kmax;
 }
 
 int akaze_extract_device(const void* img, int rows, int cols, int channels, size_t stride, const PixelMask& pmask, int mask_support, int max_points,
-                         apds_keypoint* kps_out, uint8_t* desc64_out, int capacity, hipStream_t s) {
+                         apds_keypoint* kps_out, uint8_t* desc_out, int capacity, hipStream_t s, int descriptor) {
     int count = 0;
-    akaze_extract_batch_device(img, 1, 0, rows, cols, channels, stride, pmask, mask_support, max_points, kps_out, desc64_out, capacity, &count, s);
+    akaze_extract_batch_device(img, 1, 0, rows, cols, channels, stride, pmask, mask_support, max_points, kps_out, desc_out, capacity, &count, s, descriptor);
     return count;
 }
 

@@ -45,16 +45,21 @@ static PixelMask plane_mask(const void* mask_dev, size_t row_stride, size_t img_
     return m;
 }
 
-// device image -> host keypoints + 61-byte descriptors (malloc'ed, the caller frees them with apds_free)
+// bytes of a descriptor row on the device / in the host arrays the calls hand out: M-LDB 64 (one line) / 61 packed; float 256 / 256
+static size_t device_row_bytes(int descriptor) { return descriptor == APDS_AKAZE_DESCRIPTOR_KAZE ? APDS_DESC_FLOAT_DIM * sizeof(float) : APDS_DESC_STRIDE; }
+static size_t host_row_bytes(int descriptor) { return descriptor == APDS_AKAZE_DESCRIPTOR_KAZE ? APDS_DESC_FLOAT_DIM * sizeof(float) : APDS_DESC_BYTES; }
+
+// device image -> host keypoints + 61-byte descriptors, or rows of 64 floats (malloc'ed, the caller frees them with apds_free)
 static void extract_to_host(ThreadCtx& c, hipStream_t s, const uint8_t* dimg, int rows, int cols, int channels, size_t dstride, const PixelMask& pmask,
-                            int mask_support, int max_points, apds_keypoint** kps, uint8_t** desc, int* n) {
+                            int mask_support, int max_points, apds_keypoint** kps, uint8_t** desc, int* n, int descriptor = APDS_AKAZE_DESCRIPTOR_MLDB) {
     // strict 3x3 maxima are never adjacent: at most ceil(w/2)*ceil(h/2) per level, and the cap is max_points
     const int capacity = max_points;
+    const size_t row_dev = device_row_bytes(descriptor), row_host = host_row_bytes(descriptor);
     apds_keypoint* dk = c.alloc_n<apds_keypoint>(capacity);
-    uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * 64);
-    const int K = akaze_extract_device(dimg, rows, cols, channels, dstride, pmask, mask_support, max_points, dk, dd, capacity, s);
+    uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * row_dev);
+    const int K = akaze_extract_device(dimg, rows, cols, channels, dstride, pmask, mask_support, max_points, dk, dd, capacity, s, descriptor);
     apds_keypoint* hk = static_cast<apds_keypoint*>(std::malloc(std::max<size_t>(1, (size_t)K * sizeof(apds_keypoint))));
-    uint8_t* hd = static_cast<uint8_t*>(std::malloc(std::max<size_t>(1, (size_t)K * APDS_DESC_BYTES)));
+    uint8_t* hd = static_cast<uint8_t*>(std::malloc(std::max<size_t>(1, (size_t)K * row_host)));
     if (!hk || !hd) {
         std::free(hk);
         std::free(hd);
@@ -62,10 +67,14 @@ static void extract_to_host(ThreadCtx& c, hipStream_t s, const uint8_t* dimg, in
     }
     try {
         if (K) {
-            uint8_t* d61 = c.alloc_n<uint8_t>((size_t)K * APDS_DESC_BYTES);
-            pack_desc61_device(dd, K, d61, s);
+            const uint8_t* rows_dev = dd;   // float rows are packed as they are
+            if (descriptor == APDS_AKAZE_DESCRIPTOR_MLDB) {
+                uint8_t* d61 = c.alloc_n<uint8_t>((size_t)K * APDS_DESC_BYTES);
+                pack_desc61_device(dd, K, d61, s);
+                rows_dev = d61;
+            }
             HIP_CHECK(hipMemcpyAsync(hk, dk, (size_t)K * sizeof(apds_keypoint), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipMemcpyAsync(hd, d61, (size_t)K * APDS_DESC_BYTES, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(hd, rows_dev, (size_t)K * row_host, hipMemcpyDeviceToHost, s));
         }
         HIP_CHECK(hipStreamSynchronize(s));
     } catch (...) {
@@ -79,14 +88,14 @@ static void extract_to_host(ThreadCtx& c, hipStream_t s, const uint8_t* dimg, in
 }
 
 static int akaze_extract_host(const uint8_t* img, int rows, int cols, int channels, size_t stride, const uint8_t* mask, size_t mask_stride, int mask_support,
-                              int max_points, apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes) {
+                              int max_points, apds_keypoint** kps, uint8_t** desc, int* n, int* desc_bytes, int descriptor = APDS_AKAZE_DESCRIPTOR_MLDB) {
     return guarded([&] {
         APDS_REQUIRE(kps && desc && n && desc_bytes, APDS_ERR_BAD_ARG, "null output");
         check_mask_support(mask_support);
         *kps = nullptr;
         *desc = nullptr;
         *n = 0;
-        *desc_bytes = APDS_DESC_BYTES;
+        *desc_bytes = descriptor == APDS_AKAZE_DESCRIPTOR_KAZE ? APDS_DESC_FLOAT_DIM : APDS_DESC_BYTES;   // (the float calls: floats per row)
         APDS_REQUIRE(img != nullptr && rows > 0 && cols > 0, APDS_ERR_ASSERT, "empty image");   // CV_Assert(!image.empty())
         APDS_REQUIRE(channels == 1 || channels == 3 || channels == 4, APDS_ERR_ASSERT, "image must have 1, 3 or 4 channels");
         APDS_REQUIRE(stride >= (size_t)cols * channels, APDS_ERR_ASSERT, "row stride smaller than a row");
@@ -104,7 +113,7 @@ static int akaze_extract_host(const uint8_t* img, int rows, int cols, int channe
             dmask = c.alloc_n<uint8_t>((size_t)rows * cols);
             HIP_CHECK(hipMemcpy2DAsync(dmask, cols, mask, mask_stride, cols, rows, hipMemcpyHostToDevice, s));
         }
-        extract_to_host(c, s, dimg, rows, cols, channels, dstride, plane_mask(dmask, cols, 0, rows, cols), mask_support, max_points, kps, desc, n);
+        extract_to_host(c, s, dimg, rows, cols, channels, dstride, plane_mask(dmask, cols, 0, rows, cols), mask_support, max_points, kps, desc, n, descriptor);
     });
 }
 
@@ -193,27 +202,30 @@ static int batch_capacity(int rows, int cols, int max_points) {
 
 // device results of a batch (capacity rows per image) -> malloc'ed host arrays holding the images' rows back to back
 static void batch_results_to_host(ThreadCtx& c, hipStream_t s, const apds_keypoint* dk, const uint8_t* dd, int capacity, int n_images, const int* counts,
-                                  apds_keypoint** kps, uint8_t** desc) {
+                                  apds_keypoint** kps, uint8_t** desc, int descriptor = APDS_AKAZE_DESCRIPTOR_MLDB) {
     size_t total = 0;
     for (int i = 0; i < n_images; i++) total += (size_t)counts[i];
+    const size_t row_dev = device_row_bytes(descriptor), row_host = host_row_bytes(descriptor);
     apds_keypoint* hk = static_cast<apds_keypoint*>(std::malloc(std::max<size_t>(1, total * sizeof(apds_keypoint))));
-    uint8_t* hd = static_cast<uint8_t*>(std::malloc(std::max<size_t>(1, total * APDS_DESC_BYTES)));
+    uint8_t* hd = static_cast<uint8_t*>(std::malloc(std::max<size_t>(1, total * row_host)));
     if (!hk || !hd) {
         std::free(hk);
         std::free(hd);
         throw std::bad_alloc();
     }
     try {
-        uint8_t* d61 = c.alloc_n<uint8_t>(std::max<size_t>(1, total * APDS_DESC_BYTES));
+        const bool pack = descriptor == APDS_AKAZE_DESCRIPTOR_MLDB;   // float rows are packed as they are: straight from the images' blocks
+        uint8_t* d61 = pack ? c.alloc_n<uint8_t>(std::max<size_t>(1, total * APDS_DESC_BYTES)) : nullptr;
         size_t off = 0;
         for (int i = 0; i < n_images; i++) {
             const int K = counts[i];
             if (!K) continue;
-            pack_desc61_device(dd + (size_t)i * capacity * 64, K, d61 + off * APDS_DESC_BYTES, s);
+            if (pack) pack_desc61_device(dd + (size_t)i * capacity * row_dev, K, d61 + off * APDS_DESC_BYTES, s);
+            else HIP_CHECK(hipMemcpyAsync(hd + off * row_host, dd + (size_t)i * capacity * row_dev, (size_t)K * row_host, hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipMemcpyAsync(hk + off, dk + (size_t)i * capacity, (size_t)K * sizeof(apds_keypoint), hipMemcpyDeviceToHost, s));
             off += (size_t)K;
         }
-        if (total) HIP_CHECK(hipMemcpyAsync(hd, d61, total * APDS_DESC_BYTES, hipMemcpyDeviceToHost, s));
+        if (total && pack) HIP_CHECK(hipMemcpyAsync(hd, d61, total * APDS_DESC_BYTES, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
     } catch (...) {
         std::free(hk);
@@ -387,13 +399,13 @@ int apds_mosaic_tile_extract_batch(void* mosaic, const int32_t* xy0, int n_tiles
 // Outputs: concatenated keypoints / 61-byte descriptors (image 0's rows first), counts[i] rows per image.
 static int akaze_extract_batch_host(const uint8_t* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride,
                                     const uint8_t* const* masks, size_t mask_stride, int mask_support, int max_points, apds_keypoint** kps, uint8_t** desc,
-                                    int* counts, int* desc_bytes) {
+                                    int* counts, int* desc_bytes, int descriptor = APDS_AKAZE_DESCRIPTOR_MLDB) {
     return guarded([&] {
         APDS_REQUIRE(kps && desc && counts && desc_bytes, APDS_ERR_BAD_ARG, "null output");
         check_mask_support(mask_support);
         *kps = nullptr;
         *desc = nullptr;
-        *desc_bytes = APDS_DESC_BYTES;
+        *desc_bytes = descriptor == APDS_AKAZE_DESCRIPTOR_KAZE ? APDS_DESC_FLOAT_DIM : APDS_DESC_BYTES;
         APDS_REQUIRE(imgs != nullptr && rows > 0 && cols > 0, APDS_ERR_ASSERT, "empty image");
         APDS_REQUIRE(n_images >= 1 && n_images <= 4096, APDS_ERR_BAD_ARG, "batch must hold 1 .. 4096 images");
         APDS_REQUIRE(channels == 1 || channels == 3 || channels == 4, APDS_ERR_ASSERT, "image must have 1, 3 or 4 channels");
@@ -414,7 +426,7 @@ static int akaze_extract_batch_host(const uint8_t* imgs, int n_images, size_t im
         }
         const int capacity = batch_capacity(rows, cols, max_points);
         apds_keypoint* dk = c.alloc_n<apds_keypoint>((size_t)capacity * n_images);
-        uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * 64 * n_images);
+        uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * device_row_bytes(descriptor) * n_images);
         // the masks go into one device buffer, a plane per image; an image without one gets all ones
         uint8_t* dmask = nullptr;
         const size_t mpx = (size_t)rows * cols;
@@ -429,8 +441,8 @@ static int akaze_extract_batch_host(const uint8_t* imgs, int n_images, size_t im
             }
         }
         akaze_extract_batch_device(dimg, n_images, dimg_bytes, rows, cols, channels, dstride, plane_mask(dmask, cols, mpx, rows, cols), mask_support, max_points, dk, dd,
-                                   capacity, counts, s);
-        batch_results_to_host(c, s, dk, dd, capacity, n_images, counts, kps, desc);
+                                   capacity, counts, s, descriptor);
+        batch_results_to_host(c, s, dk, dd, capacity, n_images, counts, kps, desc, descriptor);
     });
 }
 
@@ -497,6 +509,61 @@ int apds_dev_akaze_extract_masked_support(const void* img, int rows, int cols, i
 int apds_dev_akaze_extract_masked(const void* img, int rows, int cols, int channels, size_t stride, const void* mask_dev, size_t mask_stride, int max_points,
                                   void* kps, void* desc64, int capacity, int* n, void* stream) {
     return apds_dev_akaze_extract_masked_support(img, rows, cols, channels, stride, mask_dev, mask_stride, 0, max_points, kps, desc64, capacity, n, stream);
+}
+
+// ---- AKAZE's float descriptor (APDS_AKAZE_DESCRIPTOR_KAZE: akaze_describe_msurf.hip); not in the reference, the producer of the L2 matcher's input
+int apds_akaze_extract_float(const uint8_t* img, int rows, int cols, int channels, size_t stride, const uint8_t* mask, size_t mask_stride, int mask_support,
+                             int max_points, apds_keypoint** kps, float** desc, int* n, int* desc_dim) {
+    APDS_RANGE("apds_akaze_extract_float");
+    return akaze_extract_host(img, rows, cols, channels, stride, mask, mask_stride, mask_support, max_points, kps, reinterpret_cast<uint8_t**>(desc), n, desc_dim,
+                              APDS_AKAZE_DESCRIPTOR_KAZE);
+}
+
+int apds_akaze_extract_float_batch(const uint8_t* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride,
+                                   const uint8_t* const* masks, size_t mask_stride, int mask_support, int max_points, apds_keypoint** kps, float** desc, int* counts,
+                                   int* desc_dim) {
+    APDS_RANGE("apds_akaze_extract_float_batch");
+    return akaze_extract_batch_host(imgs, n_images, image_stride, rows, cols, channels, stride, masks, mask_stride, mask_support, max_points, kps,
+                                    reinterpret_cast<uint8_t**>(desc), counts, desc_dim, APDS_AKAZE_DESCRIPTOR_KAZE);
+}
+
+int apds_dev_akaze_extract_float(const void* img, int rows, int cols, int channels, size_t stride, const void* mask_dev, size_t mask_stride, int mask_support,
+                                 int max_points, void* kps, void* desc_f32, int capacity, int* n, void* stream) {
+    APDS_RANGE("apds_dev_akaze_extract_float");
+    return guarded([&] {
+        APDS_REQUIRE(n && kps && desc_f32, APDS_ERR_BAD_ARG, "null output");
+        check_mask_support(mask_support);
+        ctx().ws_reset(pick_stream(stream));
+        *n = akaze_extract_device(img, rows, cols, channels, stride, plane_mask(mask_dev, mask_stride, 0, rows, cols), mask_support, max_points,
+                                  static_cast<apds_keypoint*>(kps), static_cast<uint8_t*>(desc_f32), capacity, pick_stream(stream), APDS_AKAZE_DESCRIPTOR_KAZE);
+    });
+}
+
+int apds_dev_akaze_extract_float_batch(const void* imgs, int n_images, size_t image_stride, int rows, int cols, int channels, size_t stride, const void* mask_dev,
+                                       size_t mask_stride, size_t mask_image_stride, int mask_support, int max_points, void* kps, void* desc_f32, int capacity,
+                                       int* counts, void* stream) {
+    APDS_RANGE("apds_dev_akaze_extract_float_batch");
+    return guarded([&] {
+        APDS_REQUIRE(counts && kps && desc_f32, APDS_ERR_BAD_ARG, "null output");
+        check_mask_support(mask_support);
+        ctx().ws_reset(pick_stream(stream));
+        akaze_extract_batch_device(imgs, n_images, image_stride, rows, cols, channels, stride, plane_mask(mask_dev, mask_stride, mask_image_stride, rows, cols),
+                                   mask_support, max_points, static_cast<apds_keypoint*>(kps), static_cast<uint8_t*>(desc_f32), capacity, counts,
+                                   pick_stream(stream), APDS_AKAZE_DESCRIPTOR_KAZE);
+    });
+}
+
+// the float describe stage alone on one plane of the caller's (the hook the kernel's tests stand on)
+int apds_dev_akaze_describe_float(const void* lxy_dev, int w, int h, const void* kps_dev, int n, void* desc_f32_dev, void* stream) {
+    APDS_RANGE("apds_dev_akaze_describe_float");
+    return guarded([&] {
+        APDS_REQUIRE(n >= 0, APDS_ERR_BAD_ARG, "negative keypoint count");
+        if (n == 0) return;
+        APDS_REQUIRE(lxy_dev && kps_dev && desc_f32_dev, APDS_ERR_BAD_ARG, "null argument");
+        APDS_REQUIRE(w >= 1 && h >= 1 && w < 65536 && h < 65536, APDS_ERR_ASSERT, "plane sides must be 1 .. 65535");
+        msurf_describe_plane_device(static_cast<const float2*>(lxy_dev), w, h, static_cast<const apds_keypoint*>(kps_dev), n, static_cast<float*>(desc_f32_dev),
+                                    pick_stream(stream));
+    });
 }
 
 // The zero-count summed-area table of a device mask on its own (what the mask support builds in its workspace): out[y][x], (rows + 1) x

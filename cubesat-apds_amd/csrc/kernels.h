@@ -67,10 +67,12 @@ void valu_peak_device(int mode, int waves_per_simd, double* lane_ops_per_s, doub
 
 // akaze_extract.hip (the launchers of its stages: akaze.h). pmask: the detection mask (common.h; a null base = none)
 // mask_support (>= 0): the mask is consulted on the square of mask_support descriptor units around the keypoint (0: its own pixel)
+// descriptor: APDS_AKAZE_DESCRIPTOR_MLDB (rows of 64 bytes at `desc`) or APDS_AKAZE_DESCRIPTOR_KAZE (rows of 64 floats = 256 bytes)
 int akaze_extract_device(const void* img, int rows, int cols, int channels, size_t stride, const PixelMask& pmask, int mask_support, int max_points,
-                         apds_keypoint* kps, uint8_t* desc64, int capacity, hipStream_t s);
+                         apds_keypoint* kps, uint8_t* desc, int capacity, hipStream_t s, int descriptor = APDS_AKAZE_DESCRIPTOR_MLDB);
 int akaze_extract_batch_device(const void* img, int n_img, size_t img_bstride, int rows, int cols, int channels, size_t stride, const PixelMask& pmask,
-                               int mask_support, int max_points, apds_keypoint* kps, uint8_t* desc64, int capacity, int* counts, hipStream_t s);
+                               int mask_support, int max_points, apds_keypoint* kps, uint8_t* desc, int capacity, int* counts, hipStream_t s,
+                               int descriptor = APDS_AKAZE_DESCRIPTOR_MLDB);
 
 // misc.hip
 void points_from_matches_device(const apds_keypoint* kp1, int n1, const apds_keypoint* kp2, int n2, const apds_dmatch* m, int nm,

@@ -29,8 +29,8 @@ class DbKeypoints:
 
 
 class ExtractedKeyPoint:
-    """lib.rs:15-18 — keypoints (K x cv::KeyPoint) and descriptors (K x 61 u8). Fields are private in the
-    reference; `to_db_type` is the only way out there, so both spellings are offered here."""
+    """lib.rs:15-18 — keypoints (K x cv::KeyPoint) and descriptors (K x 61 u8; K x 64 float32 from an extraction with descriptor="kaze").
+    Fields are private in the reference; `to_db_type` is the only way out there, so both spellings are offered here."""
 
     def __init__(self, keypoints, descriptors):
         self._keypoints = keypoints
@@ -95,14 +95,38 @@ def _mask_support(mask_support):
     return s
 
 
-def akaze_keypoint_descriptor_extraction(img, mask=None, max_points=None, mask_support=0):
+def _descriptor_kind(descriptor):
+    """"mldb" (the reference's 486-bit M-LDB, lib.rs:64-73) | "kaze" (AKAZE's 64-float M-SURF descriptor) -> APDS_AKAZE_DESCRIPTOR_*"""
+    try:
+        return _lib.AKAZE_DESCRIPTORS[descriptor]
+    except (KeyError, TypeError):
+        raise ApdsError(_lib.ERR_BAD_ARG, f"unknown descriptor {descriptor!r}: 'mldb' or 'kaze'") from None
+
+
+def _float_rows(desc, total, dim):
+    return take(desc, total * dim, np.float32).reshape(total, dim)
+
+
+def akaze_keypoint_descriptor_extraction(img, mask=None, max_points=None, mask_support=0, descriptor="mldb"):
     """The same call with the mask argument lib.rs:75-79 leaves empty (`&Mat::default()`): detection runs unmasked, then a keypoint goes iff
     mask[int(y + 0.5), int(x + 0.5)] == 0 (f32, truncation; x, y the refined full-resolution position), and max_points cuts what is left.
     mask: uint8 HxW, non-zero = keep; None = akaze_keypoint_descriptor_extraction_def.
     mask_support n > 0: the keypoint goes iff ANY mask byte is zero within n * scale * 2^octave pixels of that position on either axis
     (scale = rint(0.5 * size / 2^octave), the unit of the descriptor's lattice; the square is clipped to the image).
-    _lib.MASK_SUPPORT_DESCRIPTOR (15) covers the descriptor at any orientation."""
+    _lib.MASK_SUPPORT_DESCRIPTOR (15) covers the descriptor at any orientation.
+    descriptor "kaze": the same keypoints, bit for bit, with AKAZE's float descriptor (DESCRIPTOR_KAZE: 64 float32 of unit length per
+    keypoint, zeros for a flat patch) - what l2_knn_match and get_knn_matches_l2 compare."""
     support = _mask_support(mask_support)
+    if _descriptor_kind(descriptor) == _lib.AKAZE_DESCRIPTOR_KAZE:
+        img = _image(img)
+        m = None if mask is None else _mask_plane(mask, img.shape[0], img.shape[1])
+        ch = 1 if img.ndim == 2 else img.shape[2]
+        kps, desc = C.c_void_p(), C.c_void_p()
+        n, dim = C.c_int(0), C.c_int(0)
+        check(lib().apds_akaze_extract_float(ptr(img), img.shape[0], img.shape[1], ch, img.strides[0], None if m is None else ptr(m),
+                                             0 if m is None else m.strides[0], support, MAX_POINTS if max_points is None else int(max_points),
+                                             C.byref(kps), C.byref(desc), C.byref(n), C.byref(dim)))
+        return ExtractedKeyPoint(take(kps, n.value, KEYPOINT_DTYPE), _float_rows(desc, n.value, dim.value))
     if mask is None:
         return akaze_keypoint_descriptor_extraction_def(img, max_points)
     img = _image(img)
@@ -122,13 +146,15 @@ def akaze_keypoint_descriptor_extraction(img, mask=None, max_points=None, mask_s
     return ExtractedKeyPoint(k, d)
 
 
-def akaze_keypoint_descriptor_extraction_batch(imgs, max_points=None, mask=None, mask_support=0):
+def akaze_keypoint_descriptor_extraction_batch(imgs, max_points=None, mask=None, mask_support=0, descriptor="mldb"):
     """lib.rs:61-92 for a batch of equal-sized images (array [B, H, W] or [B, H, W, C] uint8, or a list of such images) in ONE library
     call: the batch goes through every kernel's grid together. Returns a list of ExtractedKeyPoint, each exactly what
     akaze_keypoint_descriptor_extraction_def returns for that image. This is how a caller that extracts one tile per task
     (preprocessor/src/main.rs:227-245,277) should hand its tiles over: a single small tile is launch-latency-bound.
-    mask: None, or one entry per image, each None or a mask as akaze_keypoint_descriptor_extraction takes it; mask_support: as there."""
+    mask: None, or one entry per image, each None or a mask as akaze_keypoint_descriptor_extraction takes it; mask_support, descriptor: as
+    there."""
     support = _mask_support(mask_support)
+    kind = _descriptor_kind(descriptor)
     a = np.ascontiguousarray(np.stack([np.asarray(i) for i in imgs]) if isinstance(imgs, (list, tuple)) else np.asarray(imgs))
     if a.dtype != np.uint8 or a.ndim not in (3, 4) or a.size == 0:
         raise ApdsError(_lib.ERR_ASSERT, "images must be a non-empty uint8 [B, H, W[, C]] array")
@@ -137,11 +163,23 @@ def akaze_keypoint_descriptor_extraction_batch(imgs, max_points=None, mask=None,
     kps, desc = C.c_void_p(), C.c_void_p()
     counts, nb = (C.c_int * b)(), C.c_int(0)
     mp = MAX_POINTS if max_points is None else int(max_points)
+    if mask is not None and len(mask) != b:
+        raise ApdsError(_lib.ERR_ASSERT, "one mask (or None) per image")
+    if kind == _lib.AKAZE_DESCRIPTOR_KAZE:
+        planes = None if mask is None else [None if m is None else np.ascontiguousarray(_mask_plane(m, h, w)) for m in mask]
+        mptrs = None if planes is None else (C.c_void_p * b)(*[None if m is None else m.ctypes.data for m in planes])
+        check(lib().apds_akaze_extract_float_batch(ptr(a), b, a.strides[0], h, w, ch, a.strides[1], mptrs, w, support, mp, C.byref(kps), C.byref(desc), counts,
+                                                   C.byref(nb)))
+        total = sum(counts)
+        k, d = take(kps, total, KEYPOINT_DTYPE), _float_rows(desc, total, nb.value)
+        out, off = [], 0
+        for c in counts:
+            out.append(ExtractedKeyPoint(k[off:off + c].copy(), d[off:off + c].copy()))
+            off += c
+        return out
     if mask is None:
         check(lib().apds_akaze_extract_batch(ptr(a), b, a.strides[0], h, w, ch, a.strides[1], mp, C.byref(kps), C.byref(desc), counts, C.byref(nb)))
     else:
-        if len(mask) != b:
-            raise ApdsError(_lib.ERR_ASSERT, "one mask (or None) per image")
         planes = [None if m is None else np.ascontiguousarray(_mask_plane(m, h, w)) for m in mask]      # one row stride for all: packed
         mptrs = (C.c_void_p * b)(*[None if m is None else m.ctypes.data for m in planes])
         if support == 0:
@@ -349,3 +387,25 @@ def l2_knn_match(query_desc, train_desc, k):
     dist = np.zeros((q.shape[0], k), np.float32)
     check(lib().apds_l2_knn_match(ptr(q), q.shape[0], ptr(t), t.shape[0], q.shape[1], int(k), ptr(idx), ptr(dist)))
     return idx, dist
+
+
+def get_knn_matches_l2(origin_desc, target_desc, k, filter_strength):
+    """get_knn_matches (lib.rs:94-114) for float descriptors: BFMatcher(NORM_L2).knnMatch(origin -> target) through l2_knn_match, then the
+    ratio test of lib.rs:107-111 on its two nearest - m[0] is kept iff m[0].distance < m[1].distance * filter_strength (f32). The same
+    errors as get_knn_matches: k < 1 is an assertion, a query without a second neighbour (k < 2 or fewer than two target rows) is out of
+    range, an empty side gives no matches. The distances come from the device; the comparison of the two columns is all that happens here."""
+    q = np.ascontiguousarray(origin_desc, np.float32)
+    t = np.ascontiguousarray(target_desc, np.float32)
+    if q.ndim != 2 or t.ndim != 2 or (q.shape[0] and t.shape[0] and q.shape[1] != t.shape[1]):
+        raise ApdsError(_lib.ERR_ASSERT, "descriptor matrices must be 2-D float32 with equal row length")
+    if int(k) < 1:
+        raise ApdsError(_lib.ERR_ASSERT, "k must be >= 1")
+    if q.shape[0] == 0 or t.shape[0] == 0:
+        return np.zeros(0, DMATCH_DTYPE)
+    if int(k) < 2 or t.shape[0] < 2:      # lib.rs:108 `i.get(1)?`
+        raise ApdsError(_lib.ERR_OUT_OF_RANGE, "fewer than 2 neighbours per query (k < 2 or target rows < 2)")
+    idx, dist = l2_knn_match(q, t, 2)    # only the two nearest are ever read
+    keep = np.flatnonzero(dist[:, 0] < dist[:, 1] * np.float32(filter_strength))
+    out = np.zeros(len(keep), DMATCH_DTYPE)
+    out["query_idx"], out["train_idx"], out["distance"] = keep, idx[keep, 0], dist[keep, 0]
+    return out

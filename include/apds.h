@@ -115,6 +115,27 @@ int apds_akaze_extract_batch_masked_support(const uint8_t* imgs, int n_images, s
                                             const uint8_t* const* masks, size_t mask_stride_bytes, int mask_support, int max_points, apds_keypoint** kps,
                                             uint8_t** desc, int* counts, int* desc_bytes);
 
+/* AKAZE's float descriptor. NOT in the reference, which fixes DESCRIPTOR_MLDB (lib.rs:64-73): cv::AKAZE::DESCRIPTOR_KAZE, the 64-float M-SURF
+ * descriptor of OpenCV 4.8 MSURF_Descriptor_64_Invoker (restated from memory: DESIGN.md section 2), unit length, compared with NORM_L2 - the
+ * input of apds_l2_knn_match and apds_dev_l2_topk. Same detector, same keypoints, same orientation: the keypoints of a float extraction are
+ * those of the M-LDB call with the same arguments, field for field and bit for bit; only the describe kernel differs. Per keypoint, on the
+ * (Lx, Ly) planes of its level (class_id): ratio = 2^octave, scale = rint(0.5f * size / ratio) (f32, half to even), 4 x 4 cells of 9 x 9
+ * samples scale apart on a lattice rotated by the keypoint's angle, every sample the bilinear blend of the four pixels around it (indices
+ * clamped to the plane), rotated into the keypoint's frame and weighted by a Gaussian around its cell's centre; a cell gives (sum dx, sum dy,
+ * sum |dx|, sum |dy|) times a Gaussian over the cells; the 64 values are divided by their Euclidean length.
+ * One deliberate departure from OpenCV: a row whose length is 0 (a flat patch) is 64 zeros - OpenCV divides by zero and writes NaN, which
+ * would poison every distance of the L2 matcher.
+ * The values are OpenCV's enum values; MLDB is what every other extraction call of this header computes. */
+enum { APDS_AKAZE_DESCRIPTOR_KAZE = 3, APDS_AKAZE_DESCRIPTOR_MLDB = 5 };
+#define APDS_DESC_FLOAT_DIM 64       /* floats per row, packed: 256 bytes */
+/* The masked_support calls with float rows: *desc = n x 64 f32 (apds_free), *desc_dim = 64. A NULL mask with mask_support 0 is the plain
+ * call; the argument rules and error codes are those of the masked_support calls above. */
+int apds_akaze_extract_float(const uint8_t* img, int rows, int cols, int channels, size_t stride_bytes, const uint8_t* mask, size_t mask_stride_bytes,
+                             int mask_support, int max_points, apds_keypoint** kps, float** desc, int* n, int* desc_dim);
+int apds_akaze_extract_float_batch(const uint8_t* imgs, int n_images, size_t image_stride_bytes, int rows, int cols, int channels, size_t stride_bytes,
+                                   const uint8_t* const* masks, size_t mask_stride_bytes, int mask_support, int max_points, apds_keypoint** kps, float** desc,
+                                   int* counts, int* desc_dim);
+
 /* lib.rs:94-114  get_knn_matches(origin_desc, target_desc, k, filter_strength) -> Vector<DMatch>
  * Hamming k-NN of each origin (query) row over the target (train) rows, then keep m[0] iff
  * m[0].distance < m[1].distance * filter_strength. Returns APDS_ERR_OUT_OF_RANGE when a query has fewer
@@ -781,6 +802,17 @@ int apds_dev_akaze_extract_masked_support(const void* img, int rows, int cols, i
 int apds_dev_akaze_extract_batch_masked_support(const void* imgs, int n_images, size_t image_stride_bytes, int rows, int cols, int channels, size_t stride_bytes,
                                                 const void* mask_dev, size_t mask_stride_bytes, size_t mask_image_stride_bytes, int mask_support, int max_points,
                                                 void* kps, void* desc64, int capacity, int* counts, void* stream);
+/* The two calls above with float descriptors (APDS_AKAZE_DESCRIPTOR_KAZE: see apds_akaze_extract_float): desc_f32 = capacity rows of 64
+ * packed floats (256 bytes) per image, which is what apds_dev_l2_topk takes with dim = 64. kps, counts, capacity, mask and stream as above. */
+int apds_dev_akaze_extract_float(const void* img, int rows, int cols, int channels, size_t stride_bytes, const void* mask_dev, size_t mask_stride_bytes,
+                                 int mask_support, int max_points, void* kps, void* desc_f32, int capacity, int* n, void* stream);
+int apds_dev_akaze_extract_float_batch(const void* imgs, int n_images, size_t image_stride_bytes, int rows, int cols, int channels, size_t stride_bytes,
+                                       const void* mask_dev, size_t mask_stride_bytes, size_t mask_image_stride_bytes, int mask_support, int max_points,
+                                       void* kps, void* desc_f32, int capacity, int* counts, void* stream);
+/* The float describe stage alone, on a caller-supplied plane (what the tests of the kernel stand on): lxy_dev = h x w interleaved (Lx, Ly)
+ * f32, one level; kps_dev: n apds_keypoint whose class_id is ignored (the plane IS the level), octave / size / angle / x / y used as
+ * described at apds_akaze_extract_float; desc_f32_dev: n x 64 floats. n == 0 is a no-op; asynchronous on `stream`. */
+int apds_dev_akaze_describe_float(const void* lxy_dev, int w, int h, const void* kps_dev, int n, void* desc_f32_dev, void* stream);
 /* The table behind the mask support, on its own: out_u32_dev[y][x], (rows + 1) x (cols + 1) u32, = the number of zero mask bytes in rows < y
  * and columns < x (exact). mask_dev: rows x cols bytes, row_stride_bytes between rows and pix_stride_bytes between the pixels of a row (1: a
  * plane; 4 with mask_dev = image + 3: the alpha of a BGRA image, read as the aligned 4-byte words that hold the bytes). Sides 1 .. 65535. */

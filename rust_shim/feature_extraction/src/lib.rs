@@ -112,6 +112,45 @@ pub fn akaze_keypoint_descriptor_extraction(img: &Mat, mask: &Mat, max_points: O
     Ok(ExtractedKeyPoint { keypoints, descriptors })
 }
 
+/// NOT in the reference (lib.rs:64-73 fixes DESCRIPTOR_MLDB): the same extraction with AKAZE's float descriptor (DESCRIPTOR_KAZE, M-SURF):
+/// the keypoints of `akaze_keypoint_descriptor_extraction`, bit for bit, and a CV_32F descriptor matrix of n x 64 unit-length rows (zeros for
+/// a flat patch), what BFMatcher(NORM_L2) compares. An empty mask is the unmasked call; mask_support as in apds_akaze_extract_masked_support.
+pub fn akaze_keypoint_descriptor_extraction_float(img: &Mat, mask: &Mat, mask_support: i32, max_points: Option<i32>) -> Result<ExtractedKeyPoint, Error> {
+    let (mut kps, mut desc, mut n, mut dim) = (ptr::null_mut(), ptr::null_mut(), 0i32, 0i32);
+    let stride = img.step1(0)? * img.elem_size1();
+    let (mask_ptr, mask_stride) = if mask.empty() {
+        (ptr::null(), 0)
+    } else {
+        if mask.typ() != CV_8U || mask.rows() != img.rows() || mask.cols() != img.cols() {
+            return Err(Error::new(-215, "mask must be CV_8U of the image's size"));
+        }
+        (mask.data(), mask.step1(0)? * mask.elem_size1())
+    };
+    let rc = unsafe {
+        apds_sys::apds_akaze_extract_float(img.data(), img.rows(), img.cols(), img.channels(), stride, mask_ptr, mask_stride, mask_support,
+                                           max_points.unwrap_or(MAX_POINTS), &mut kps, &mut desc, &mut n, &mut dim)
+    };
+    if rc != 0 {
+        return Err(apds_err(rc));
+    }
+    let mut keypoints = Vector::<KeyPoint>::with_capacity(n as usize);
+    let raw = unsafe { std::slice::from_raw_parts(kps, n as usize) };
+    for k in raw {
+        keypoints.push(KeyPoint::new_point(Point2f::new(k.x, k.y), k.size, k.angle, k.response, k.octave, k.class_id)?);
+    }
+    let descriptors = if n > 0 {
+        let rows: &[f32] = unsafe { std::slice::from_raw_parts(desc, (n * dim) as usize) };
+        Mat::from_slice_rows_cols(rows, n as usize, dim as usize)? // copies
+    } else {
+        Mat::default()
+    };
+    unsafe {
+        apds_sys::apds_free(kps as *mut _);
+        apds_sys::apds_free(desc as *mut _);
+    }
+    Ok(ExtractedKeyPoint { keypoints, descriptors })
+}
+
 fn take_matches(p: *mut apds_sys::apds_dmatch, n: i32) -> Vector<DMatch> {
     let mut v = Vector::<DMatch>::with_capacity(n as usize);
     for m in unsafe { std::slice::from_raw_parts(p, n as usize) } {
