@@ -18,7 +18,10 @@ assert KEYPOINT_DTYPE.itemsize == 28 and DMATCH_DTYPE.itemsize == 16
 ERR_INTERNAL, ERR_NOMEM, ERR_BAD_ARG, ERR_NO_DEVICE, ERR_OUT_OF_RANGE, ERR_ASSERT, ERR_EMPTY = -2, -4, -5, -216, -211, -215, -1000
 ERR_NOT_IMPLEMENTED = -213
 PIPELINE_MATCH_RATIO, PIPELINE_MATCH_CROSSCHECK = 0, 1   # apds_pipeline_set_matcher
-PIPELINE_MATCHERS = {"ratio": PIPELINE_MATCH_RATIO, "crosscheck": PIPELINE_MATCH_CROSSCHECK}
+PIPELINE_MATCH_L2_RATIO = 2                              # a float pipeline's matcher (apds_pipeline_create_float), from birth
+PIPELINE_MATCHERS = {"ratio": PIPELINE_MATCH_RATIO, "crosscheck": PIPELINE_MATCH_CROSSCHECK, "l2": PIPELINE_MATCH_L2_RATIO}
+L2_EXACT, L2_SCREEN = 0, 1                               # APDS_L2_*: the arithmetic of the float top-2
+L2_MODES = {"exact": L2_EXACT, "screen": L2_SCREEN}
 ERR_NOT_IMPLEMENTED = -213
 
 # every symbol include/apds.h declares (checked by tests/test_abi.py)
@@ -52,6 +55,8 @@ SYMBOLS = [
     "apds_pnp_solver_ransac_dist", "apds_pipeline_set_lens",
     "apds_akaze_extract_float", "apds_akaze_extract_float_batch", "apds_dev_akaze_extract_float", "apds_dev_akaze_extract_float_batch",
     "apds_dev_akaze_describe_float",
+    "apds_l2_train_create", "apds_l2_train_destroy", "apds_l2_train_info", "apds_dev_l2_train_top2", "apds_dev_l2_ratio_filter", "apds_pipeline_create_float",
+    "apds_workspace_info",
 ]
 
 RESAMPLE_NEAREST, RESAMPLE_LANCZOS = 0, 1
@@ -230,6 +235,13 @@ def lib():
             "apds_l2_knn_match": (i, [vp, i, vp, i, i, i, vp, vp]),
             "apds_dev_l2_topk": (i, [vp, i, vp, i64, i, u32, i, vp, vp]),
             "apds_dev_l2_topk_ex": (i, [vp, i, vp, i64, i, u32, i, i, vp, vp, ip, C.POINTER(d)]),
+            "apds_workspace_info": (i, [C.POINTER(i64), C.POINTER(i64)]),
+            "apds_l2_train_create": (i, [pp, vp, i64, i, u32]),
+            "apds_l2_train_destroy": (i, [vp]),
+            "apds_l2_train_info": (i, [vp, C.POINTER(i64), ip, ip]),
+            "apds_dev_l2_train_top2": (i, [vp, vp, i, i, vp, vp, ip, C.POINTER(d)]),
+            "apds_dev_l2_ratio_filter": (i, [vp, i, i, f, vp, ip, vp]),
+            "apds_pipeline_create_float": (i, [pp, vp, i64, u32, vp, i64, C.POINTER(PipelineParams)]),
             "apds_db_create": (i, [pp, i64]),
             "apds_db_destroy": (i, [vp]),
             "apds_db_rows": (i64, [vp]),
@@ -359,6 +371,13 @@ def take(pointer, count, dtype, shape=None):
             C.memmove(ptr(out), pointer, out.nbytes)
         lib().apds_free(pointer)
     return out
+
+
+def workspace_info():
+    """(bytes held by every thread's device workspace and the slab cache, device allocations made for them so far): apds_workspace_info"""
+    b, n = C.c_int64(0), C.c_int64(0)
+    check(lib().apds_workspace_info(C.byref(b), C.byref(n)))
+    return b.value, n.value
 
 
 def kernel_ms(name):

@@ -262,6 +262,17 @@ int apds_dev_ratio_filter(const void* keys, int nq, int k, float fs, void* out_m
     });
 }
 
+int apds_dev_l2_ratio_filter(const void* keys, int nq, int k, float fs, void* out_matches, int* n_matches, void* stream) {
+    APDS_RANGE("apds_dev_l2_ratio_filter");
+    return guarded([&] {
+        APDS_REQUIRE(k >= 2, APDS_ERR_OUT_OF_RANGE, "ratio test needs two neighbours");
+        APDS_REQUIRE(n_matches, APDS_ERR_BAD_ARG, "null output");
+        hipStream_t s = pick_stream(stream);
+        ctx().ws_reset(s);
+        *n_matches = l2_ratio_filter_device(static_cast<const uint64_t*>(keys), nq, k, fs, static_cast<apds_dmatch*>(out_matches), s);
+    });
+}
+
 int apds_dev_cross_check(const void* train_best, int64_t n_train, int nq, void* out_matches, int* n_matches, void* stream) {
     return guarded([&] {
         APDS_REQUIRE(n_matches, APDS_ERR_BAD_ARG, "null output");

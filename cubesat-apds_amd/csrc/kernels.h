@@ -125,6 +125,27 @@ void l2_row_norms_device(const float* x, long long n, int dim, float* out, hipSt
 void l2_topk_device(const float* q, int nq, const float* t, long long nt, int dim, uint32_t index_base, int k, uint64_t* out, hipStream_t s);
 bool l2_topk_screen_device(const float* q, int nq, const float* t, long long nt, int dim, uint32_t index_base, int k, uint64_t* out, hipStream_t s,
                            double* candidates_per_query);
+// a resident L2 train set (apds_l2_train_*): the rows are borrowed; the norms, the bf16 copy scaled by -2 and the largest norm are made
+// once at create and owned by the handle (the bf16 copy and the largest norm only where the screen applies: screen_ready)
+struct L2Train {
+    int device = 0;
+    const float* rows = nullptr;
+    long long n = 0;
+    int dim = 0;
+    uint32_t index_base = 0;
+    bool screen_ready = false;
+    float* norms = nullptr;          // n floats: row_norms_kernel's values
+    uint16_t* rows_bf = nullptr;     // n x dim bf16 of -2 * row (screen_ready)
+    unsigned int* tmax_bits = nullptr;   // bits of the largest |t|^2 (screen_ready)
+};
+L2Train* l2_train_create(const float* t, long long nt, int dim, uint32_t index_base, hipStream_t s);   // synchronises s
+void l2_train_destroy(L2Train* set);
+// both: top-2 keys of q against the set; the exact one is l2_topk_device's launch on the handle's norms. The screen returns false where
+// it could not be used (handle not screen_ready, misaligned q, candidate overflow): the caller resets the workspace and runs the exact one
+void l2_train_top2_exact_device(const L2Train* set, const float* q, int nq, uint64_t* out, hipStream_t s);
+bool l2_train_top2_screen_device(const L2Train* set, const float* q, int nq, uint64_t* out, hipStream_t s, double* candidates_per_query);
+// match_filter.hip: the ratio test on L2 keys (distances sqrtf(d^2), compared in f32), compacted in query order
+int l2_ratio_filter_device(const uint64_t* keys, int nq, int k, float fs, apds_dmatch* out, hipStream_t s);
 
 // homography_rho.hip
 int find_homography_rho_device(const float* src, const float* dst, int n, double thr, int max_iters, double confidence, double* H_host, uint8_t* mask_dev,

@@ -277,7 +277,9 @@ void l2_row_norms_device(const float* x, long long n, int dim, float* out, hipSt
     if (n > 0) hipLaunchKernelGGL(row_norms_kernel, dim3(ceil_div(n, 4)), dim3(256), 0, s, x, n, dim, out);
 }
 
-void l2_topk_device(const float* q, int nq, const float* t, long long nt, int dim, uint32_t index_base, int k, uint64_t* out, hipStream_t s) {
+// tn_ready: the train rows' norms where the caller keeps them (a resident train set: row_norms_kernel's values, made once); null: computed here
+static void l2_topk_launch(const float* q, int nq, const float* t, long long nt, int dim, uint32_t index_base, int k, uint64_t* out, hipStream_t s,
+                           const float* tn_ready) {
     APDS_REQUIRE(k == 1 || k == 2, APDS_ERR_ASSERT, "L2 top-k supports k in {1,2}");
     APDS_REQUIRE(dim >= 1 && dim <= L2_KMAX, APDS_ERR_ASSERT, "float descriptor length must be 1..128");
     APDS_REQUIRE(nt < (1ll << 31), APDS_ERR_ASSERT, "train set too large for one call; shard it");
@@ -288,9 +290,13 @@ void l2_topk_device(const float* q, int nq, const float* t, long long nt, int di
     }
     ThreadCtx& c = ctx();
     float* qn = c.alloc_n<float>(nq);
-    float* tn = c.alloc_n<float>(nt);
+    const float* tn = tn_ready;
     hipLaunchKernelGGL(row_norms_kernel, dim3(ceil_div(nq, 4)), dim3(256), 0, s, q, (long long)nq, dim, qn);
-    hipLaunchKernelGGL(row_norms_kernel, dim3(ceil_div(nt, 4)), dim3(256), 0, s, t, nt, dim, tn);
+    if (!tn_ready) {
+        float* own = c.alloc_n<float>(nt);
+        hipLaunchKernelGGL(row_norms_kernel, dim3(ceil_div(nt, 4)), dim3(256), 0, s, t, nt, dim, own);
+        tn = own;
+    }
     const int kp = dim <= 64 ? 64 : 128;
     const int q_tiles = ceil_div(nq, L2_TN), t_tiles = ceil_div(nt, L2_TM);
     // enough blocks for every CU, but keep each block streaming many train tiles
@@ -306,7 +312,7 @@ void l2_topk_device(const float* q, int nq, const float* t, long long nt, int di
 #define L2_LAUNCH(KK, FF, PP)                                                                                                                            \
     do {                                                                                                                                                 \
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&l2_topk_kernel<KK, FF, PP>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024)); \
-        hipLaunchKernelGGL((l2_topk_kernel<KK, FF, PP>), dim3(q_tiles, splits), dim3(512), lds, s, t, (const float*)tn, (int)nt, q, (const float*)qn, nq, \
+        hipLaunchKernelGGL((l2_topk_kernel<KK, FF, PP>), dim3(q_tiles, splits), dim3(512), lds, s, t, tn, (int)nt, q, (const float*)qn, nq, \
                            dim, tiles_per_split, index_base, parts);                                                                                     \
     } while (0)
 #define L2_LAUNCH_K(KK)                       \
@@ -326,6 +332,14 @@ void l2_topk_device(const float* q, int nq, const float* t, long long nt, int di
     }
     HIP_CHECK(hipGetLastError());
     if (splits > 1) merge_topk_device(parts, splits, nq, k, out, s);
+}
+
+void l2_topk_device(const float* q, int nq, const float* t, long long nt, int dim, uint32_t index_base, int k, uint64_t* out, hipStream_t s) {
+    l2_topk_launch(q, nq, t, nt, dim, index_base, k, out, s, nullptr);
+}
+
+void l2_train_top2_exact_device(const L2Train* set, const float* q, int nq, uint64_t* out, hipStream_t s) {
+    l2_topk_launch(q, nq, set->rows, set->n, set->dim, set->index_base, 2, out, s, set->norms);
 }
 
 }  // namespace apds
@@ -358,6 +372,51 @@ int apds_dev_l2_topk(const void* q, int nq, const void* t, int64_t nt, int dim, 
         APDS_REQUIRE(nq >= 0 && nt >= 0, APDS_ERR_ASSERT, "negative row count");
         QueuedWorkspaceCall call(pick_stream(stream));
         l2_topk_device(static_cast<const float*>(q), nq, static_cast<const float*>(t), nt, dim, index_base, k, static_cast<uint64_t*>(out_keys), call.s);
+    });
+}
+
+int apds_l2_train_create(void** set, const void* train, int64_t nt, int dim, uint32_t index_base) {
+    return guarded([&] {
+        APDS_REQUIRE(set, APDS_ERR_BAD_ARG, "null output");
+        *set = nullptr;
+        ThreadCtx& c = ctx();
+        c.ws_reset();
+        *set = l2_train_create(static_cast<const float*>(train), nt, dim, index_base, c.stream);
+    });
+}
+
+int apds_l2_train_destroy(void* set) {
+    return guarded([&] { l2_train_destroy(static_cast<L2Train*>(set)); });
+}
+
+int apds_l2_train_info(const void* set, int64_t* n_train, int* dim, int* screen_ready) {
+    return guarded([&] {
+        APDS_REQUIRE(set, APDS_ERR_BAD_ARG, "null train set");
+        const L2Train* t = static_cast<const L2Train*>(set);
+        if (n_train) *n_train = t->n;
+        if (dim) *dim = t->dim;
+        if (screen_ready) *screen_ready = t->screen_ready ? 1 : 0;
+    });
+}
+
+int apds_dev_l2_train_top2(void* set, const void* q, int nq, int mode, void* out_keys, void* stream, int* mode_used, double* candidates_per_query) {
+    APDS_RANGE("apds_dev_l2_train_top2");
+    return guarded([&] {
+        APDS_REQUIRE(set, APDS_ERR_BAD_ARG, "null train set");
+        APDS_REQUIRE(nq >= 0, APDS_ERR_ASSERT, "negative row count");
+        APDS_REQUIRE(mode == APDS_L2_EXACT || mode == APDS_L2_SCREEN, APDS_ERR_BAD_ARG, "mode must be APDS_L2_EXACT or APDS_L2_SCREEN");
+        const L2Train* t = static_cast<const L2Train*>(set);
+        APDS_REQUIRE(t->device == ctx().device, APDS_ERR_BAD_ARG, "the train set lives on another device than the calling thread's");
+        QueuedWorkspaceCall call(pick_stream(stream));
+        hipStream_t s = call.s;
+        if (mode_used) *mode_used = APDS_L2_EXACT;
+        if (candidates_per_query) *candidates_per_query = 0;
+        if (mode == APDS_L2_SCREEN && l2_train_top2_screen_device(t, static_cast<const float*>(q), nq, static_cast<uint64_t*>(out_keys), s, candidates_per_query)) {
+            if (mode_used) *mode_used = APDS_L2_SCREEN;
+            return;
+        }
+        ctx().ws_reset(s);   // the screen does not apply (handle, alignment, candidate overflow): the exact kernel
+        l2_train_top2_exact_device(t, static_cast<const float*>(q), nq, static_cast<uint64_t*>(out_keys), s);
     });
 }
 

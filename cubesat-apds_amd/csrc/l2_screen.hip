@@ -16,6 +16,9 @@
 //   the f32 accumulations on either side and the few f32 operations around them add at most 2^-13 (|q|^2 + |t|^2) (K = 128 terms
 //   at 2^-24 relative each is 2^-17 |q| |t|; the slack is generous on purpose). Hence |F - S| <= eps(q) with
 //   eps(q) = 2 (2u + u^2) |q| Tmax + 2^-13 (|q|^2 + Tmax^2),   Tmax = the largest row norm of the train set.
+//   The bound is kept as it is for rows of 64 elements (the train set's second length): every term of the derivation is a sum over the
+//   K elements of a row, bounded through |q| |t| and |q|^2 + |t|^2, which do not depend on K, and the accumulation term (K 2^-24
+//   relative) halves at K = 64, so the 2^-13 slack holds a fortiori. Nothing was tightened, and nothing tuned against a test.
 // Two rows (of the sample, hence of the set) have S <= s2, hence F <= s2 + eps, so the second smallest F over the whole set is
 // <= s2 + eps; every row of the exact top-2 (ties included) has F <= that, hence S <= s2 + 2 eps: it is a candidate. (A looser s2
 // only admits more candidates: a sample of 1/12 of the rows admits ~2 * 12 * 2.5 = 60 per query on BASELINE config 3, ~5 with the
@@ -36,6 +39,8 @@
 // keys identical, 108 instead of 122 VGPRs, 231 ms per step instead of 225.5 (0.506 against 0.519): this kernel's gaps are not where the
 // staging instructions are. The wave-priority change is kept: 0.514 -> 0.519. profiles/r04/l2_prio_ab.txt, l2_glds.txt.)
 #include <cmath>
+#include <memory>
+#include <vector>
 
 #include "config.h"
 #include "kernels.h"
@@ -50,10 +55,28 @@ static constexpr int SC_TM = 128;            // train rows per tile
 #ifndef APDS_SC_NC
 #define APDS_SC_NC 3
 #endif
-static constexpr int SC_NC = APDS_SC_NC;     // 16-query column blocks per wave (each A read from LDS feeds SC_NC MFMAs)
-static constexpr int SC_Q = 8 * 16 * SC_NC;  // queries per block (8 waves)
-static constexpr int SC_D = 128;             // descriptor length (the screen is built for it)
-static constexpr int SC_PITCH = 272;         // bytes per staged train row (256 + 16)
+static constexpr int SC_NC = APDS_SC_NC;     // 16-query column blocks per wave at D = 128 (each A read from LDS feeds NC MFMAs; a block = 8 waves = 128 NC queries)
+// The descriptor length D is a template parameter of the kernels: 128 (the one-shot entry and the train set) or 64 (M-SURF rows; the train
+// set only). At 64 a row is 128 B of bf16: a tile is 128 rows x 8 pieces of 16 B (two per thread), a row block takes two k-steps of 32, and
+// a wave's query operands are B[NC][2] - 24 VGPRs less than at 128, which is why the column blocks per wave (NC) are a parameter there.
+// LDS row pitch. The A read is a ds_read_b128 at row (lane & 15), 16-byte piece (lane >> 4) of a k-step; its bank is (a / 4) mod 64 and
+// the hardware serves it in four groups of 16 lanes, {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32: a group mixes eight rows
+// of piece p with the eight OTHER rows of piece p + 1. In units of 16 B a pitch of m puts lane (row, piece) on slot (m row + piece) mod 16:
+//   D = 128: 272 B, m = 17: as measured in round 4 (rows 11 / piece 1 and 12 / piece 0 share a slot: 2-way on one pair per group);
+//   D = 64:  160 B, m = 10: rows {0-3, 12-15} -> the eight even slots, rows {4-11} + 1 -> the eight odd ones: every group touches 16
+//            distinct slots, conflict-free. (144 B, m = 9, the smallest padded pitch, separates the 16 ROWS of one piece but not the mixed
+//            groups: rows 13 / piece 0 and 4 / piece 1 collide, 2-way. 160 B costs 4 KB more LDS per block, 42 KB: still 3 blocks per CU.)
+// Commits are ds_write_b128 by 8 contiguous lanes per row at both lengths (a contiguous 128 B: conflict-free on the 32-bank write path).
+template <int D>
+struct ScShape {
+    static_assert(D == 64 || D == 128, "the screen is built for 64 and 128 elements per row");
+    static constexpr int PITCH = D == 128 ? 272 : 160;   // bytes per staged train row
+    static constexpr int KSTEPS = D / 32;                // MFMA k-steps per row block
+    static constexpr int PIECES = D / 32;                // 16-byte pieces per thread per tile (128 rows x D / 8 pieces over 512 threads)
+    static constexpr int GROUPS = D / 8;                 // 16-byte pieces per row
+    static constexpr int ROWS_PER_PASS = 512 / GROUPS;   // rows one piece index of all threads covers (32 / 64)
+    static constexpr size_t LDS = (size_t)2 * SC_TM * PITCH + 2 * SC_TM * sizeof(float);
+};
 
 __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
     uint32_t x = __float_as_uint(f);
@@ -63,10 +86,11 @@ __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
 }
 
 // rows of f32 -> bf16 (scaled by `scale`, a power of two: exact), and |row|^2 in f32 exactly as row_norms_kernel of l2_match.hip
-__global__ void to_bf16_rows_kernel(const float* __restrict__ x, long long n, float scale, uint16_t* __restrict__ out) {
+// (n_elems = rows x dim, a multiple of 4)
+__global__ void to_bf16_rows_kernel(const float* __restrict__ x, long long n_elems, float scale, uint16_t* __restrict__ out) {
     APDS_RAISE_WAVE_PRIORITY();
     const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i >= n * SC_D) return;
+    if (i >= n_elems) return;
     const float4 v = *reinterpret_cast<const float4*>(x + i);
     uint2 o;
     o.x = (uint32_t)f32_to_bf16_rne(v.x * scale) | ((uint32_t)f32_to_bf16_rne(v.y * scale) << 16);
@@ -106,7 +130,7 @@ __device__ __forceinline__ uint64_t sc_key(float d, uint32_t idx) { return idx =
 //         block, position from an LDS counter: one global counter for all blocks serialised at ~12 ns per append, 0.65 s for the
 //         54 M candidates of config 3); the block's count goes to cand_count[block] (entries past the region are dropped and show
 //         in the count: the host checks it).
-template <int PASS, bool PRIO>
+template <int PASS, bool PRIO, int D, int NC>
 __global__ __launch_bounds__(512) void l2_screen_kernel(const uint16_t* __restrict__ train_bf, const float* __restrict__ tnorm, int n_train,
                                                         const uint16_t* __restrict__ query_bf, const float* __restrict__ qnorm, int nq, int tiles_per_split,
                                                         uint32_t index_base, uint64_t* __restrict__ out, const float* __restrict__ theta,
@@ -116,6 +140,8 @@ __global__ __launch_bounds__(512) void l2_screen_kernel(const uint16_t* __restri
     // 16-byte aligned: the static LDS word below would otherwise push this array to offset 4 and turn every ds_read_b128 /
     // ds_write_b128 of the tiles into misaligned accesses (measured: 209 -> 1185 ms per pass)
     extern __shared__ __attribute__((aligned(128))) unsigned char sc_lds[];
+    using Shape = ScShape<D>;
+    constexpr int SC_PITCH = Shape::PITCH, SC_NC = NC, SC_Q = 8 * 16 * NC, SC_D = D;
     auto tile_lds = [&](int buf) { return sc_lds + buf * (SC_TM * SC_PITCH); };
     auto norm_lds = [&](int buf) { return reinterpret_cast<float*>(sc_lds + 2 * SC_TM * SC_PITCH) + buf * SC_TM; };
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -131,14 +157,14 @@ __global__ __launch_bounds__(512) void l2_screen_kernel(const uint16_t* __restri
     }
     const int col = lane & 15, kq = lane >> 4;                     // accumulator column / k chunk (operands) / row group (accumulators)
 
-    // B operands: query (q0 + 16 c + col), k = 32 s + 8 kq .. + 7, for c = 0, 1 and the four k steps s
-    bf16x8 B[SC_NC][4];
+    // B operands: query (q0 + 16 c + col), k = 32 s + 8 kq .. + 7, for the wave's column blocks c and the D / 32 k steps s
+    bf16x8 B[SC_NC][Shape::KSTEPS];
     float qq[SC_NC], th[SC_NC];
 #pragma unroll
     for (int c = 0; c < SC_NC; c++) {
         const int qi = min(q0 + 16 * c + col, nq - 1);
 #pragma unroll
-        for (int s = 0; s < 4; s++) B[c][s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(query_bf + (size_t)qi * SC_D + 32 * s + 8 * kq));
+        for (int s = 0; s < Shape::KSTEPS; s++) B[c][s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(query_bf + (size_t)qi * SC_D + 32 * s + 8 * kq));
         qq[c] = qnorm[qi];
         th[c] = PASS == 1 ? theta[qi] : 0.f;
     }
@@ -149,17 +175,20 @@ __global__ __launch_bounds__(512) void l2_screen_kernel(const uint16_t* __restri
         best[c].i0 = best[c].i1 = 0xFFFFFFFFu;
     }
 
-    // staging: the tile is 128 rows x 256 B = 2048 pieces of 16 B, four per thread; rows past the end re-read the last row and get
-    // a norm of +inf, so they never rank
-    uint4 pre0, pre1, pre2, pre3;   // (separate variables: as an array indexed inside the lambdas they went to scratch)
+    // staging: the tile is 128 rows x 2 D bytes = 2048 (D = 128) or 1024 (D = 64) pieces of 16 B, four or two per thread; rows past the
+    // end re-read the last row and get a norm of +inf, so they never rank
+    uint4 pre0, pre1, pre2, pre3;   // (separate variables: as an array indexed inside the lambdas they went to scratch; D = 64 uses two)
     float pre_norm = INFINITY;
-    const int pr = tid >> 4, pg = tid & 15;   // piece p of this thread: row 32 p + pr, 16-byte group pg
+    constexpr int RP = Shape::ROWS_PER_PASS;
+    const int pr = tid / Shape::GROUPS, pg = tid % Shape::GROUPS;   // piece p of this thread: row RP p + pr, 16-byte group pg
     auto load_tile = [&](int tile) {
         const int r0 = tile * SC_TM + pr;
         pre0 = *reinterpret_cast<const uint4*>(train_bf + (size_t)min(r0, n_train - 1) * SC_D + 8 * pg);
-        pre1 = *reinterpret_cast<const uint4*>(train_bf + (size_t)min(r0 + 32, n_train - 1) * SC_D + 8 * pg);
-        pre2 = *reinterpret_cast<const uint4*>(train_bf + (size_t)min(r0 + 64, n_train - 1) * SC_D + 8 * pg);
-        pre3 = *reinterpret_cast<const uint4*>(train_bf + (size_t)min(r0 + 96, n_train - 1) * SC_D + 8 * pg);
+        pre1 = *reinterpret_cast<const uint4*>(train_bf + (size_t)min(r0 + RP, n_train - 1) * SC_D + 8 * pg);
+        if (Shape::PIECES == 4) {
+            pre2 = *reinterpret_cast<const uint4*>(train_bf + (size_t)min(r0 + 2 * RP, n_train - 1) * SC_D + 8 * pg);
+            pre3 = *reinterpret_cast<const uint4*>(train_bf + (size_t)min(r0 + 3 * RP, n_train - 1) * SC_D + 8 * pg);
+        }
         if (tid < SC_TM) {
             const int row = tile * SC_TM + tid;
             pre_norm = row < n_train ? tnorm[row] : INFINITY;
@@ -168,9 +197,11 @@ __global__ __launch_bounds__(512) void l2_screen_kernel(const uint16_t* __restri
     auto commit = [&](int buf) {
         unsigned char* d = tile_lds(buf) + pr * SC_PITCH + 16 * pg;
         *reinterpret_cast<uint4*>(d) = pre0;
-        *reinterpret_cast<uint4*>(d + 32 * SC_PITCH) = pre1;
-        *reinterpret_cast<uint4*>(d + 64 * SC_PITCH) = pre2;
-        *reinterpret_cast<uint4*>(d + 96 * SC_PITCH) = pre3;
+        *reinterpret_cast<uint4*>(d + RP * SC_PITCH) = pre1;
+        if (Shape::PIECES == 4) {
+            *reinterpret_cast<uint4*>(d + 2 * RP * SC_PITCH) = pre2;
+            *reinterpret_cast<uint4*>(d + 3 * RP * SC_PITCH) = pre3;
+        }
         if (tid < SC_TM) norm_lds(buf)[tid] = pre_norm;
     };
     load_tile(tile_begin);
@@ -193,7 +224,7 @@ __global__ __launch_bounds__(512) void l2_screen_kernel(const uint16_t* __restri
             // (round 4, from the Hamming matcher: a wave about to feed the matrix pipe goes ahead of the SIMD's waves that are in their epilogue)
             if (PRIO) __builtin_amdgcn_s_setprio(2);
 #pragma unroll
-            for (int s = 0; s < 4; s++) {
+            for (int s = 0; s < Shape::KSTEPS; s++) {
                 const bf16x8 A = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(arow + 64 * s));
 #pragma unroll
                 for (int c = 0; c < SC_NC; c++) acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B[c][s], acc[c], 0, 0, 0);
@@ -291,7 +322,10 @@ __global__ void screen_theta_kernel(const uint64_t* __restrict__ top2, const flo
 // exact keys of the candidates: the binary32 arithmetic of l2_topk_kernel (fmaf chain over k ascending from 0, u = fmaf(-2, dot, |t|^2),
 // d^2 = max(|q|^2 + u, 0)); STEP 0: atomic min into best[q]; STEP 1: atomic min into second[q] of the keys != best[q]
 // grid.y = the screen kernel's blocks (one candidate region each), grid.x strides over the region's entries
-template <int STEP>
+// D = 64 is the KP = 64 instantiation of l2_topk_kernel: its accumulator starts from an inline zero and takes k = 0 .. 63 in ascending
+// order, four per v_mfma_f32_16x16x4_f32 step (k = 16 g + 4 i + kc, kc the lane's k class, steps i = x, y, z, w of group g) - the same
+// single chain as at 128 stopped after 64 terms, with no padding terms behind it (dim == KP), which is the loop below.
+template <int STEP, int D>
 __global__ void screen_rerank_kernel(const unsigned long long* __restrict__ cand, const unsigned long long* __restrict__ counts, unsigned long long region,
                                      const float* __restrict__ q, const float* __restrict__ qnorm, const float* __restrict__ t, const float* __restrict__ tnorm,
                                      uint32_t index_base, unsigned long long* __restrict__ keys, unsigned long long* __restrict__ out) {
@@ -303,11 +337,11 @@ __global__ void screen_rerank_kernel(const unsigned long long* __restrict__ cand
     const uint32_t qi = (uint32_t)(c >> 32), row = (uint32_t)c;
     unsigned long long key;
     if (STEP == 0) {
-        const float4* a = reinterpret_cast<const float4*>(t + (size_t)(row - index_base) * SC_D);
-        const float4* b = reinterpret_cast<const float4*>(q + (size_t)qi * SC_D);
+        const float4* a = reinterpret_cast<const float4*>(t + (size_t)(row - index_base) * D);
+        const float4* b = reinterpret_cast<const float4*>(q + (size_t)qi * D);
         float dot = 0.0f;
 #pragma unroll 8
-        for (int k = 0; k < SC_D / 4; k++) {
+        for (int k = 0; k < D / 4; k++) {
             const float4 x = a[k], y = b[k];
             dot = __builtin_fmaf(x.x, y.x, dot);
             dot = __builtin_fmaf(x.y, y.y, dot);
@@ -326,24 +360,36 @@ __global__ void screen_rerank_kernel(const unsigned long long* __restrict__ cand
     }
 }
 
-// returns false if the screen could not be used (shape, alignment, candidate overflow): the caller falls back to the f32 kernel
-bool l2_topk_screen_device(const float* q, int nq, const float* t, long long nt, int dim, uint32_t index_base, int k, uint64_t* out, hipStream_t s,
-                           double* candidates_per_query) {
-    if (dim != SC_D || k != 2 || nt < 2 || nq < 1) return false;
-    if (((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(t)) & 15) != 0) return false;
+// the train side of a screen as the passes read it: the rows, their norms, their bf16 copy scaled by -2 and the bits of the largest norm
+struct ScTrainSide {
+    const float* t;
+    long long nt;
+    uint32_t index_base;
+    const float* tn;
+    const uint16_t* tb;
+    const unsigned int* tmax;
+};
+
+// the train side from the rows (the one-shot entry does this per call in the workspace, a train set once into memory of its own)
+static void sc_prepare_train(const float* t, long long nt, int dim, float* tn, uint16_t* tb, unsigned int* tmax, hipStream_t s) {
+    HIP_CHECK(hipMemsetAsync(tmax, 0, 16, s));
+    l2_row_norms_device(t, nt, dim, tn, s);
+    hipLaunchKernelGGL(to_bf16_rows_kernel, dim3(ceil_div(nt * dim / 4, 256)), dim3(256), 0, s, t, nt * dim, -2.0f, tb);
+    hipLaunchKernelGGL(max_norm_kernel, dim3(256), dim3(256), 0, s, (const float*)tn, nt, tmax);
+    HIP_CHECK(hipGetLastError());
+}
+
+// the query side, the three passes and the overflow check for one (D, NC). false: candidate overflow (the caller falls back)
+template <int D, int NC>
+static bool sc_run(const ScTrainSide& T, const float* q, int nq, uint64_t* out, hipStream_t s, double* candidates_per_query) {
+    constexpr int Q = 8 * 16 * NC;
+    const long long nt = T.nt;
     ThreadCtx& c = ctx();
     float* qn = c.alloc_n<float>(nq);
-    float* tn = c.alloc_n<float>(nt);
-    uint16_t* qb = c.alloc_n<uint16_t>((size_t)nq * SC_D);
-    uint16_t* tb = c.alloc_n<uint16_t>((size_t)nt * SC_D);
-    unsigned int* tmax = c.alloc_n<unsigned int>(4);
-    HIP_CHECK(hipMemsetAsync(tmax, 0, 16, s));
-    l2_row_norms_device(q, nq, dim, qn, s);
-    l2_row_norms_device(t, nt, dim, tn, s);
-    hipLaunchKernelGGL(to_bf16_rows_kernel, dim3(ceil_div((long long)nq * SC_D / 4, 256)), dim3(256), 0, s, q, (long long)nq, 1.0f, qb);
-    hipLaunchKernelGGL(to_bf16_rows_kernel, dim3(ceil_div(nt * SC_D / 4, 256)), dim3(256), 0, s, t, nt, -2.0f, tb);
-    hipLaunchKernelGGL(max_norm_kernel, dim3(256), dim3(256), 0, s, (const float*)tn, nt, tmax);
-    const int q_tiles = ceil_div(nq, SC_Q), t_tiles = ceil_div(nt, SC_TM);
+    uint16_t* qb = c.alloc_n<uint16_t>((size_t)nq * D);
+    l2_row_norms_device(q, nq, D, qn, s);
+    hipLaunchKernelGGL(to_bf16_rows_kernel, dim3(ceil_div((long long)nq * D / 4, 256)), dim3(256), 0, s, q, (long long)nq * D, 1.0f, qb);
+    const int q_tiles = ceil_div(nq, Q), t_tiles = ceil_div(nt, SC_TM);
     int splits = std::max(1, std::min(t_tiles, ceil_div(256 * 2, q_tiles)));
     const int tiles_per_split = ceil_div(t_tiles, splits);
     splits = ceil_div(t_tiles, tiles_per_split);
@@ -359,32 +405,31 @@ bool l2_topk_screen_device(const float* q, int nq, const float* t, long long nt,
     uint64_t* parts = c.alloc_n<uint64_t>((size_t)s_splits * nq * 2);
     uint64_t* top2 = s_splits == 1 ? parts : c.alloc_n<uint64_t>((size_t)nq * 2);
     float* theta = c.alloc_n<float>(nq);
-    // candidate regions: one per block of pass B, `region` entries each (256 queries x 256 candidates: 4x what config 3 needs)
+    // candidate regions: one per block of pass B, `region` entries each (192 candidates per query of the block: 4x what config 3 needs)
     const int n_blocks = q_tiles * splits;
-    const unsigned long long region = (unsigned long long)SC_Q * 192;
+    const unsigned long long region = (unsigned long long)Q * 192;
     if ((unsigned long long)n_blocks * region > (1ull << 29)) return false;
     unsigned long long* cand = c.alloc_n<unsigned long long>((size_t)n_blocks * region);
     unsigned long long* keys = c.alloc_n<unsigned long long>((size_t)n_blocks * region);
     unsigned long long* counts = c.alloc_n<unsigned long long>(n_blocks);
-    const size_t lds = (size_t)2 * SC_TM * SC_PITCH + 2 * SC_TM * sizeof(float);
+    const size_t lds = ScShape<D>::LDS;
     const bool prio = config().l2_prio != 0;
-    for (const void* kf : {reinterpret_cast<const void*>(&l2_screen_kernel<0, false>), reinterpret_cast<const void*>(&l2_screen_kernel<1, false>),
-                           reinterpret_cast<const void*>(&l2_screen_kernel<0, true>), reinterpret_cast<const void*>(&l2_screen_kernel<1, true>)})
+    for (const void* kf : {reinterpret_cast<const void*>(&l2_screen_kernel<0, false, D, NC>), reinterpret_cast<const void*>(&l2_screen_kernel<1, false, D, NC>),
+                           reinterpret_cast<const void*>(&l2_screen_kernel<0, true, D, NC>), reinterpret_cast<const void*>(&l2_screen_kernel<1, true, D, NC>)})
         HIP_CHECK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     {
         KernelTimer timer("l2_screen", s);
-        auto k0 = prio ? &l2_screen_kernel<0, true> : &l2_screen_kernel<0, false>;
-        hipLaunchKernelGGL(k0, dim3(q_tiles, s_splits), dim3(512), lds, s, (const uint16_t*)tb, (const float*)tn, (int)n_sample,
-                           (const uint16_t*)qb, (const float*)qn, nq, s_tiles_per_split, index_base, parts, (const float*)nullptr, (unsigned long long*)nullptr, 0ull,
-                           (unsigned long long*)nullptr);
+        auto k0 = prio ? &l2_screen_kernel<0, true, D, NC> : &l2_screen_kernel<0, false, D, NC>;
+        hipLaunchKernelGGL(k0, dim3(q_tiles, s_splits), dim3(512), lds, s, T.tb, T.tn, (int)n_sample, (const uint16_t*)qb, (const float*)qn, nq, s_tiles_per_split,
+                           T.index_base, parts, (const float*)nullptr, (unsigned long long*)nullptr, 0ull, (unsigned long long*)nullptr);
     }
     if (s_splits > 1) merge_topk_device(parts, s_splits, nq, 2, top2, s);
-    hipLaunchKernelGGL(screen_theta_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, s, (const uint64_t*)top2, (const float*)qn, nq, (const unsigned int*)tmax, theta);
+    hipLaunchKernelGGL(screen_theta_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, s, (const uint64_t*)top2, (const float*)qn, nq, T.tmax, theta);
     {
         KernelTimer timer("l2_screen", s);
-        auto k1 = prio ? &l2_screen_kernel<1, true> : &l2_screen_kernel<1, false>;
-        hipLaunchKernelGGL(k1, dim3(q_tiles, splits), dim3(512), lds, s, (const uint16_t*)tb, (const float*)tn, (int)nt, (const uint16_t*)qb,
-                           (const float*)qn, nq, tiles_per_split, index_base, (uint64_t*)nullptr, (const float*)theta, cand, region, counts);
+        auto k1 = prio ? &l2_screen_kernel<1, true, D, NC> : &l2_screen_kernel<1, false, D, NC>;
+        hipLaunchKernelGGL(k1, dim3(q_tiles, splits), dim3(512), lds, s, T.tb, T.tn, (int)nt, (const uint16_t*)qb, (const float*)qn, nq, tiles_per_split,
+                           T.index_base, (uint64_t*)nullptr, (const float*)theta, cand, region, counts);
     }
     std::vector<unsigned long long> hc(n_blocks);
     HIP_CHECK(hipMemcpyAsync(hc.data(), counts, (size_t)n_blocks * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
@@ -400,13 +445,79 @@ bool l2_topk_screen_device(const float* q, int nq, const float* t, long long nt,
     if (n_cand) {
         const dim3 grid((unsigned int)std::max<unsigned long long>(1, std::min<unsigned long long>(64, (largest + 255) / 256)), n_blocks);
         KernelTimer timer("l2_rerank", s);
-        hipLaunchKernelGGL((screen_rerank_kernel<0>), grid, dim3(256), 0, s, (const unsigned long long*)cand, (const unsigned long long*)counts, region, q,
-                           (const float*)qn, t, (const float*)tn, index_base, keys, reinterpret_cast<unsigned long long*>(out));
-        hipLaunchKernelGGL((screen_rerank_kernel<1>), grid, dim3(256), 0, s, (const unsigned long long*)cand, (const unsigned long long*)counts, region, q,
-                           (const float*)qn, t, (const float*)tn, index_base, keys, reinterpret_cast<unsigned long long*>(out));
+        hipLaunchKernelGGL((screen_rerank_kernel<0, D>), grid, dim3(256), 0, s, (const unsigned long long*)cand, (const unsigned long long*)counts, region, q,
+                           (const float*)qn, T.t, T.tn, T.index_base, keys, reinterpret_cast<unsigned long long*>(out));
+        hipLaunchKernelGGL((screen_rerank_kernel<1, D>), grid, dim3(256), 0, s, (const unsigned long long*)cand, (const unsigned long long*)counts, region, q,
+                           (const float*)qn, T.t, T.tn, T.index_base, keys, reinterpret_cast<unsigned long long*>(out));
     }
     HIP_CHECK(hipGetLastError());
     return true;
+}
+
+// returns false if the screen could not be used (shape, alignment, candidate overflow): the caller falls back to the f32 kernel
+// (the one-shot entry: dim 128 only, the train side prepared per call in the workspace)
+bool l2_topk_screen_device(const float* q, int nq, const float* t, long long nt, int dim, uint32_t index_base, int k, uint64_t* out, hipStream_t s,
+                           double* candidates_per_query) {
+    if (dim != 128 || k != 2 || nt < 2 || nq < 1) return false;
+    if (((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(t)) & 15) != 0) return false;
+    ThreadCtx& c = ctx();
+    float* tn = c.alloc_n<float>(nt);
+    uint16_t* tb = c.alloc_n<uint16_t>((size_t)nt * 128);
+    unsigned int* tmax = c.alloc_n<unsigned int>(4);
+    sc_prepare_train(t, nt, 128, tn, tb, tmax, s);
+    return sc_run<128, SC_NC>(ScTrainSide{t, nt, index_base, tn, tb, tmax}, q, nq, out, s, candidates_per_query);
+}
+
+// ---- the resident train set (apds_l2_train_*) ------------------------------------------------------------------------------------------
+// Query column blocks per wave at D = 64: three (384 queries per block), as at 128. Four (512 queries: the 24 VGPRs the shorter query
+// operands free hold a fourth block's operands and accumulators) were built and measured at 35 312 x 983 616 x 64, whole call: 6.23 ms
+// with three, 6.79 ms with four (84 - 88 against 104 - 106 VGPRs; profiles/pipeline_float/match_synth_nc3.jsonl, match_synth_nc4.jsonl),
+// and taken out again. NC stays a template parameter.
+static constexpr int SC_NC64 = 3;
+
+L2Train* l2_train_create(const float* t, long long nt, int dim, uint32_t index_base, hipStream_t s) {
+    APDS_REQUIRE(t || nt == 0, APDS_ERR_BAD_ARG, "null train rows");
+    APDS_REQUIRE(nt >= 0 && nt < (1ll << 31), APDS_ERR_ASSERT, "train set too large for one handle; shard it");
+    APDS_REQUIRE(dim >= 1 && dim <= 128, APDS_ERR_ASSERT, "float descriptor length must be 1..128");
+    std::unique_ptr<L2Train, void (*)(L2Train*)> set(new L2Train(), l2_train_destroy);
+    set->device = ctx().device;
+    set->rows = t;
+    set->n = nt;
+    set->dim = dim;
+    set->index_base = index_base;
+    set->screen_ready = (dim == 64 || dim == 128) && nt >= 2 && (reinterpret_cast<uintptr_t>(t) & 15) == 0;
+    if (nt > 0) {
+        HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&set->norms), (size_t)nt * sizeof(float)));
+        if (set->screen_ready) {
+            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&set->rows_bf), (size_t)nt * dim * sizeof(uint16_t)));
+            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&set->tmax_bits), 16));
+            sc_prepare_train(t, nt, dim, set->norms, set->rows_bf, set->tmax_bits, s);
+        } else {
+            l2_row_norms_device(t, nt, dim, set->norms, s);
+            HIP_CHECK(hipGetLastError());
+        }
+        HIP_CHECK(hipStreamSynchronize(s));
+    }
+    return set.release();
+}
+
+void l2_train_destroy(L2Train* set) {
+    if (!set) return;
+    int previous = -1;
+    if (hipGetDevice(&previous) != hipSuccess) previous = -1;
+    (void)hipSetDevice(set->device);
+    for (void* p : {(void*)set->norms, (void*)set->rows_bf, (void*)set->tmax_bits})
+        if (p) (void)hipFree(p);
+    if (previous >= 0 && previous != set->device) (void)hipSetDevice(previous);
+    delete set;
+}
+
+bool l2_train_top2_screen_device(const L2Train* set, const float* q, int nq, uint64_t* out, hipStream_t s, double* candidates_per_query) {
+    if (!set->screen_ready || nq < 1) return false;
+    if ((reinterpret_cast<uintptr_t>(q) & 15) != 0) return false;
+    const ScTrainSide T{set->rows, set->n, set->index_base, set->norms, set->rows_bf, set->tmax_bits};
+    if (set->dim == 128) return sc_run<128, SC_NC>(T, q, nq, out, s, candidates_per_query);
+    return sc_run<64, SC_NC64>(T, q, nq, out, s, candidates_per_query);
 }
 
 }  // namespace apds

@@ -137,6 +137,55 @@ int ratio_filter_device(const uint64_t* keys, int nq, int k, float fs, apds_dmat
     return emit_flagged_device(keys, nq, k, flags, out, s);
 }
 
+// ---- the ratio test on L2 keys (f32 bits of d^2 << 32 | row: l2_match.hip, l2_screen.hip) ----------------------------------------------
+// The distance of a key is sqrtf(d^2), correctly rounded: the value apds_l2_knn_match computes on the host from the same bits and
+// get_knn_matches_l2 compares. It is taken in binary64 and rounded once more: a square root of a binary32 value is never within 2^-49
+// (relative) of the midpoint of two binary32 numbers, so the second rounding of a binary64 root, even one that is an ulp off, gives the
+// correctly rounded binary32 root (53 >= 2 * 24 + 2). (__fsqrt_rn is NOT that root here: unless the HIP math header is compiled
+// with OCML_BASIC_ROUNDED_OPERATIONS it is __ocml_native_sqrt_f32, the hardware's v_sqrt_f32 of 1 ulp, whatever the build's flags; it
+// measured one ulp below the host's root on 2 of 500 distances.) d1 * fs is one f32 product (no contraction: nothing is added to it), the test a strict f32 `<`.
+__device__ __forceinline__ float l2_key_distance(uint64_t key) { return (float)sqrt((double)__uint_as_float((uint32_t)(key >> 32))); }
+
+__global__ void l2_ratio_flag_kernel(const uint64_t* __restrict__ keys, int nq, int K, float fs, uint8_t* __restrict__ flags) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const int qi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (qi >= nq) return;
+    const uint64_t k0 = keys[(size_t)qi * K], k1 = keys[(size_t)qi * K + 1];
+    const float d0 = l2_key_distance(k0), d1 = l2_key_distance(k1);
+    flags[qi] = (k0 != EMPTY_KEY && k1 != EMPTY_KEY && d0 < d1 * fs) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(SCAN_BLOCK) void emit_l2_ratio_matches_kernel(const uint64_t* __restrict__ keys, int nq, int K, const uint8_t* __restrict__ flags,
+                                                                           const int* __restrict__ block_offsets, apds_dmatch* __restrict__ out) {
+    APDS_RAISE_WAVE_PRIORITY();
+    const int i = blockIdx.x * SCAN_BLOCK + threadIdx.x;
+    const int f = i < nq ? (flags[i] != 0) : 0;
+    const int pos = block_exclusive_pos(f, block_offsets[blockIdx.x]);
+    if (f) {
+        const uint64_t k0 = keys[(size_t)i * K];
+        apds_dmatch m;
+        m.query_idx = i;
+        m.train_idx = (int32_t)(uint32_t)k0;
+        m.img_idx = 0;
+        m.distance = l2_key_distance(k0);
+        out[pos] = m;
+    }
+}
+
+int l2_ratio_filter_device(const uint64_t* keys, int nq, int k, float fs, apds_dmatch* out, hipStream_t s) {
+    if (nq <= 0) return 0;
+    uint8_t* flags = ctx().alloc_n<uint8_t>(nq);
+    hipLaunchKernelGGL(l2_ratio_flag_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, s, keys, nq, k, fs, flags);
+    int* total_dev = nullptr;
+    int* offs = scan_flags_device(flags, nq, &total_dev, s);
+    hipLaunchKernelGGL(emit_l2_ratio_matches_kernel, dim3(ceil_div(nq, SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, s, keys, nq, k, (const uint8_t*)flags, (const int*)offs, out);
+    HIP_CHECK(hipGetLastError());
+    int total = 0;
+    HIP_CHECK(hipMemcpyAsync(&total, total_dev, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return total;
+}
+
 int cross_check_device(const uint64_t* train_best, long long n_train, int nq, apds_dmatch* out, hipStream_t s) {
     if (nq <= 0 || n_train <= 0) return 0;
     ThreadCtx& c = ctx();

@@ -19,6 +19,11 @@
 // with the matrix-core matcher the resident expanded copy of the DB is its searching side as it is - and the ratio filter by the
 // cross-check's scatter / flags / ordered compaction; everything behind the matches is unchanged.
 //
+// A float pipeline (apds_pipeline_create_float) runs the same stages over M-SURF rows (64 x f32): the extraction workers call the float
+// extraction into slot buffers of 256 bytes per row, the match worker calls the resident L2 train set's top-2 (l2_screen.hip: bf16 screen +
+// exact re-rank, or the exact kernel) on the single-stream branch, and the homography stage builds its matches with the L2 ratio filter;
+// everything behind the matches is unchanged. The split scan, the expanded copy, the starvation watch and the LDS cap are the Hamming scan's.
+//
 // Every worker owns a HIP stream and a device workspace (the per-thread context every entry point uses), stages hand frames over
 // through HIP events, results leave in frame order. The reference only chains these steps inside unit tests
 // (feature_extraction/src/lib.rs:197-249) and never calls find_homography_mat on the result; this is the composed path the
@@ -149,6 +154,8 @@ struct Pipeline {
     hipStream_t st_pose = nullptr;
     std::atomic<bool> pose_on{false};   // set once, before the first submit
     std::atomic<int> matcher{APDS_PIPELINE_MATCH_RATIO};   // set before the first submit (apds_pipeline_set_matcher)
+    bool float_rows = false;        // apds_pipeline_create_float: M-SURF rows (256 bytes), the L2 matcher (matcher == APDS_PIPELINE_MATCH_L2_RATIO for life)
+    L2Train* l2_train = nullptr;    // ... its resident train set, made at create
     float* db_plain_pc = nullptr;   // cross-check mode on the expanded copy: the train rows' popcounts as the swapped scan's column side takes them
     int view_capacity = 0;
     apds_pipeline_pose_params pose{};
@@ -273,7 +280,8 @@ struct Pipeline {
                 img = s->frame_dev;
             }
             int n = 0;
-            const int rc = apds_dev_akaze_extract(img, p.rows, p.cols, p.channels, s->stride, cap, s->kps, s->desc, cap, &n, st);
+            const int rc = float_rows ? apds_dev_akaze_extract_float(img, p.rows, p.cols, p.channels, s->stride, nullptr, 0, 0, cap, s->kps, s->desc, cap, &n, st)
+                                      : apds_dev_akaze_extract(img, p.rows, p.cols, p.channels, s->stride, cap, s->kps, s->desc, cap, &n, st);
             if (rc != APDS_OK) {   // this frame fails, the pipeline goes on (a sharded run contributes zero queries for it)
                 s->status = rc;
                 s->error = apds_last_error();
@@ -297,7 +305,7 @@ struct Pipeline {
     // other matchers of the process are not touched and nothing has to be restored.
     void match_worker() {
         bool watch = adaptive_cap;
-        if (p.match_lds_cap > 0) set_thread_scan_cap(p.match_lds_cap), watch = false;   // the caller asked for a cap from the first frame on
+        if (p.match_lds_cap > 0 && !float_rows) set_thread_scan_cap(p.match_lds_cap), watch = false;   // the caller asked for a cap from the first frame on
         std::deque<std::pair<Slot*, Slot*>> pending;   // (previous frame, this frame): gap = prev.ev_mend -> this.ev_mstart
         std::vector<float> recent;
         Slot* prev = nullptr;
@@ -355,7 +363,9 @@ struct Pipeline {
             } else {
                 HIP_CHECK(hipStreamWaitEvent(st_match, s->ev_extract, 0));
                 HIP_CHECK(hipEventRecord(s->ev_mstart, st_match));
-                if (K > 0 && crosscheck && db_expanded) {   // the resident expanded copy as the searching side: only the frame's rows are expanded
+                if (K > 0 && float_rows) {   // the resident L2 train set, screen mode: 3.1 ms against 16.0 ms exact on M-SURF rows (the screen reads its candidate counts back: this thread waits for the frame's passes)
+                    PIPE_OK(apds_dev_l2_train_top2(l2_train, s->desc, K, APDS_L2_SCREEN, s->keys, st_match, nullptr, nullptr));
+                } else if (K > 0 && crosscheck && db_expanded) {   // the resident expanded copy as the searching side: only the frame's rows are expanded
                     PIPE_OK(guarded([&] {
                         QueuedWorkspaceCall call(st_match);
                         hamming_mfma_swapped_top1_device(s->desc, K, db_expanded, db_plain_pc, s->train_best, st_match);
@@ -482,6 +492,8 @@ struct Pipeline {
                         ctx().ws_reset(st);
                         M = cross_check_base_device(s->train_best, table ? (long long)s->n_view : (long long)n_rows, s->K, table ? 0u : index_base, s->matches, st);
                     }));
+                } else if (matched && float_rows) {
+                    PIPE_OK(apds_dev_l2_ratio_filter(s->keys, s->K, 2, p.filter_strength, s->matches, &M, st));
                 } else if (matched) {
                     PIPE_OK(apds_dev_ratio_filter(s->keys, s->K, 2, p.filter_strength, s->matches, &M, st));
                 }
@@ -584,6 +596,8 @@ void destroy_pipeline(Pipeline* P) {
     }
     if (P->db_expanded) hm_train_destroy(P->db_expanded);
     P->db_expanded = nullptr;
+    l2_train_destroy(P->l2_train);
+    P->l2_train = nullptr;
     if (P->db_plain_pc) (void)hipFree(P->db_plain_pc);
     P->db_plain_pc = nullptr;
     if (!P->own_match_stream) P->st_match = nullptr;
@@ -609,8 +623,9 @@ extern "C" {
 namespace {
 
 // table != null: the train set is a per-frame view of that keypoint table (view_capacity rows at most); the rows arguments are unused
+// float_rows: db_rows64_dev are rows of 64 floats (apds_pipeline_create_float; no shard, no table)
 int create_pipeline(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint32_t index_base, void* shard, const void* db_kps_dev, int64_t n_db_total,
-                    void* table, int view_capacity, const apds_pipeline_params* params) {
+                    void* table, int view_capacity, const apds_pipeline_params* params, bool float_rows = false) {
     return guarded([&] {
         APDS_REQUIRE(pipe && params, APDS_ERR_BAD_ARG, "null argument");
         *pipe = nullptr;
@@ -620,6 +635,8 @@ int create_pipeline(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint
             APDS_REQUIRE(shard || (db_rows64_dev && n_rows >= 2), APDS_ERR_ASSERT, "a train set of at least two rows (or a shard handle) is required");
             APDS_REQUIRE(db_kps_dev && n_db_total > 0 && n_db_total < (1ll << 31), APDS_ERR_ASSERT, "the train rows' keypoints are required (n_db_total x 28 bytes)");
         }
+        APDS_REQUIRE(!float_rows || (n_rows < (1ll << 31) && (reinterpret_cast<uintptr_t>(db_rows64_dev) & 15) == 0), APDS_ERR_ASSERT,
+                     "float train rows: 16-byte aligned, fewer than 2^31 of them");
         ThreadCtx& c = ctx();
         APDS_REQUIRE(!table || table_device(table) == c.device, APDS_ERR_BAD_ARG, "the table lives on another device than the calling thread's");
         std::unique_ptr<Pipeline, void (*)(Pipeline*)> P(new Pipeline(), destroy_pipeline);
@@ -633,6 +650,8 @@ int create_pipeline(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint
         P->shard = shard;
         P->db_kps = static_cast<const apds_keypoint*>(db_kps_dev);
         P->n_db_total = n_db_total;
+        P->float_rows = float_rows;
+        if (float_rows) P->matcher = APDS_PIPELINE_MATCH_L2_RATIO;
         const Config& cfg = config();
         if (shard) {
             int w = 1;
@@ -651,7 +670,7 @@ int create_pipeline(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint
         // merge are 0.8 ms of small kernels per frame). The matrix-core matcher has one main launch and two tiny ones: on one stream 131.6
         // frames/s, split over three 126.8 (profiles/r04/ab_bench_env.txt); APDS_MATCH_SPLIT=2 forces the split for it as well.
         // (a table pipeline matches each frame against another view: one stream, the one-call matcher, no expanded copy of a resident train set)
-        P->split = P->world == 1 && !shard && !table && (cfg.match_mfma ? cfg.pipe_match_split == 2 : cfg.pipe_match_split != 0);
+        P->split = P->world == 1 && !shard && !table && !float_rows && (cfg.match_mfma ? cfg.pipe_match_split == 2 : cfg.pipe_match_split != 0);
         // (the starvation watch caps hamming_topk_kernel's occupancy: the matrix-core matcher has no such knob and is not watched)
         P->adaptive_cap = cfg.pipe_adaptive_cap != 0 && P->split && in.match_lds_cap == 0 && !cfg.match_mfma;
         P->extract_delay_s = in.debug_extract_delay_ms > 0 ? in.debug_extract_delay_ms * 1e-3 : 0.0;
@@ -673,13 +692,14 @@ int create_pipeline(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint
             HIP_CHECK(hipStreamCreateWithPriority(&P->st_gather, hipStreamNonBlocking, hp));
             HIP_CHECK(hipStreamCreateWithPriority(&P->st_counts, hipStreamNonBlocking, hp));
         }
-        if (P->world == 1 && !shard && !table && cfg.match_mfma) P->db_expanded = hm_train_create(P->db_rows, P->n_rows, P->st_match);
+        if (float_rows) P->l2_train = l2_train_create(static_cast<const float*>(db_rows64_dev), n_rows, 64, index_base, P->st_match);
+        if (P->world == 1 && !shard && !table && !float_rows && cfg.match_mfma) P->db_expanded = hm_train_create(P->db_rows, P->n_rows, P->st_match);
         const size_t cap = (size_t)P->cap;
         for (int i = 0; i < n_slots; i++) {
             auto s = std::make_unique<Slot>();
             s->owner = i % P->E;
             HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->kps), cap * sizeof(apds_keypoint)));
-            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->desc), cap * 64));
+            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->desc), cap * (float_rows ? 256 : 64)));
             HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->keys), cap * 2 * 8));
             HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->matches), cap * sizeof(apds_dmatch)));
             HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->p1), cap * 8));
@@ -770,6 +790,11 @@ extern "C" {
 int apds_pipeline_create(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint32_t index_base, void* shard, const void* db_kps_dev, int64_t n_db_total,
                          const apds_pipeline_params* params) {
     return create_pipeline(pipe, db_rows64_dev, n_rows, index_base, shard, db_kps_dev, n_db_total, nullptr, 0, params);
+}
+
+int apds_pipeline_create_float(void** pipe, const void* db_rows_f32_dev, int64_t n_rows, uint32_t index_base, const void* db_kps_dev, int64_t n_db_total,
+                               const apds_pipeline_params* params) {
+    return create_pipeline(pipe, db_rows_f32_dev, n_rows, index_base, nullptr, db_kps_dev, n_db_total, nullptr, 0, params, true);
 }
 
 int apds_pipeline_create_table(void** pipe, void* db, int view_capacity, const apds_pipeline_params* params) {
@@ -869,9 +894,11 @@ int apds_pipeline_enable_pose(void* pipe, const apds_pipeline_pose_params* pose)
 int apds_pipeline_set_matcher(void* pipe, int matcher) {
     return guarded([&] {
         // the three contract checks first, before any device work
-        APDS_REQUIRE(matcher == APDS_PIPELINE_MATCH_RATIO || matcher == APDS_PIPELINE_MATCH_CROSSCHECK, APDS_ERR_BAD_ARG,
-                     "matcher: APDS_PIPELINE_MATCH_RATIO (0) or APDS_PIPELINE_MATCH_CROSSCHECK (1)");
+        APDS_REQUIRE(matcher == APDS_PIPELINE_MATCH_RATIO || matcher == APDS_PIPELINE_MATCH_CROSSCHECK || matcher == APDS_PIPELINE_MATCH_L2_RATIO, APDS_ERR_BAD_ARG,
+                     "matcher: APDS_PIPELINE_MATCH_RATIO (0), APDS_PIPELINE_MATCH_CROSSCHECK (1) or, on a float pipeline, APDS_PIPELINE_MATCH_L2_RATIO (2)");
         Pipeline* P = pipe_handle(pipe);
+        APDS_REQUIRE(P->float_rows == (matcher == APDS_PIPELINE_MATCH_L2_RATIO), APDS_ERR_BAD_ARG,
+                     P->float_rows ? "a float pipeline's matcher is APDS_PIPELINE_MATCH_L2_RATIO for life" : "APDS_PIPELINE_MATCH_L2_RATIO needs a float pipeline (apds_pipeline_create_float)");
         APDS_REQUIRE(matcher == APDS_PIPELINE_MATCH_RATIO || !(P->shard || P->world > 1), APDS_ERR_NOT_IMPLEMENTED,
                      "the cross-check over a row-sharded train set (the per-query minimum across shards) is not built");
         std::lock_guard<std::mutex> one(P->submit_m);

@@ -217,6 +217,19 @@ hipEvent_t ThreadCtx::fork_event(size_t i) {
 // up as sporadic stalls of 0.1 - 0.5 s inside timed regions. A new slab request is served from here first, largest slab first (the
 // first threads to ask are the extraction workers, which are also the ones that grew the largest workspaces).
 namespace {
+// every slab of every thread's workspace and of the cache is made and released here: apds_workspace_info reports the bytes held and the
+// number of allocations, which is how the tests see growth without reading the device's free memory (that figure also moves with the
+// runtime's own pools and with whoever else uses the device)
+std::atomic<long long> g_slab_bytes{0}, g_slab_allocations{0};
+hipError_t slab_malloc(char** p, size_t bytes) {
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(p), bytes);
+    if (e == hipSuccess) g_slab_bytes += (long long)bytes, g_slab_allocations++;
+    return e;
+}
+void slab_free(const std::pair<char*, size_t>& s) {
+    (void)hipFree(s.first);
+    g_slab_bytes -= (long long)s.second;
+}
 struct SlabCache {
     std::mutex m;
     std::vector<std::pair<int, std::pair<char*, size_t>>> free;   // (device, (pointer, bytes))
@@ -257,7 +270,7 @@ void* ThreadCtx::alloc(size_t bytes) {
             slabs.push_back(got);
         } else {
             char* p = nullptr;
-            HIP_CHECK(hipMalloc(&p, want));
+            HIP_CHECK(slab_malloc(&p, want));
             slabs.emplace_back(p, want);
         }
         slab_used = 0;
@@ -305,13 +318,13 @@ void ThreadCtx::ws_reset(hipStream_t for_stream) {
         const std::pair<char*, size_t> keep = slabs[big];
         const bool fits = keep.second >= total;   // the usual case: the slab opened for the call's one large request
         for (size_t i = 0; i < slabs.size(); i++)
-            if (!fits || i != big) (void)hipFree(slabs[i].first);
+            if (!fits || i != big) slab_free(slabs[i]);
         slabs.clear();
         if (fits) {
             slabs.push_back(keep);
         } else {
             char* p = nullptr;
-            HIP_CHECK(hipMalloc(&p, total));
+            HIP_CHECK(slab_malloc(&p, total));
             slabs.emplace_back(p, total);
         }
     }
@@ -346,7 +359,7 @@ int apds_set_device(int ordinal) {
             HIP_CHECK(hipSetDevice(g_ctx.device));
             (void)hipDeviceSynchronize();   // apds_dev_* callers may have used the workspace on streams of their own
             g_ctx.drop_side();
-            for (auto& s : g_ctx.slabs) (void)hipFree(s.first);
+            for (auto& s : g_ctx.slabs) slab_free(s);
             g_ctx.slabs.clear();
             g_ctx.slab_used = 0;
             (void)hipStreamDestroy(g_ctx.stream);
@@ -430,13 +443,19 @@ int apds_release_cached_memory(void) {
         std::lock_guard<std::mutex> g(c.m);
         for (auto& e : c.free) {
             (void)hipSetDevice(e.first);
-            (void)hipFree(e.second.first);
+            slab_free(e.second);
         }
         c.free.clear();
     });
 }
 
 int apds_live_contexts(void) { return live_contexts().load(); }
+
+int apds_workspace_info(int64_t* slab_bytes, int64_t* slab_allocations) {
+    if (slab_bytes) *slab_bytes = g_slab_bytes.load();
+    if (slab_allocations) *slab_allocations = g_slab_allocations.load();
+    return APDS_OK;
+}
 
 int apds_thread_release(void) {
     return guarded([&] {
@@ -459,10 +478,10 @@ int apds_thread_release(void) {
         if (c.slabs.size() > 1) {
             size_t total = 0;
             for (auto& s : c.slabs) total += s.second;
-            for (auto& s : c.slabs) (void)hipFree(s.first);
+            for (auto& s : c.slabs) slab_free(s);
             c.slabs.clear();
             char* p = nullptr;
-            if (hipMalloc(&p, total) == hipSuccess) c.slabs.emplace_back(p, total);
+            if (slab_malloc(&p, total) == hipSuccess) c.slabs.emplace_back(p, total);
             else (void)hipGetLastError();
         }
         for (auto& s : c.slabs) cache_slab(c.device, s);

@@ -300,11 +300,67 @@ class ShardedMatcher:
 
 
 def _matcher_code(matcher):
-    """"ratio" | "crosscheck" -> APDS_PIPELINE_MATCH_*"""
+    """"ratio" | "crosscheck" | "l2" -> APDS_PIPELINE_MATCH_*"""
     try:
         return _lib.PIPELINE_MATCHERS[matcher]
     except (KeyError, TypeError):
-        raise ValueError('matcher: "ratio" (get_knn_matches, lib.rs:94-114) or "crosscheck" (get_bruteforce_matches, lib.rs:116-126)') from None
+        raise ValueError('matcher: "ratio" (get_knn_matches, lib.rs:94-114), "crosscheck" (get_bruteforce_matches, lib.rs:116-126) or "l2" '
+                         '(float descriptors: get_knn_matches_l2)') from None
+
+
+class L2TrainSet:
+    """A resident float train set (apds_l2_train_*): rows_f32 is a [N, dim] float32 device tensor, borrowed (and kept alive) until close()
+    and unchanged meanwhile. The norms, the bf16 copy and the largest norm the screen needs are made once, here. top2() gives the keys of
+    apds_dev_l2_topk(k = 2) on the same rows, bit for bit, in either mode."""
+
+    def __init__(self, rows_f32, index_base=0):
+        if rows_f32.dtype != torch.float32 or rows_f32.dim() != 2 or not rows_f32.is_contiguous():
+            raise ValueError("rows_f32: a contiguous [N, dim] float32 device tensor")
+        self.rows, self.index_base = rows_f32, int(index_base)
+        h = C.c_void_p()
+        n, dim = int(rows_f32.shape[0]), int(rows_f32.shape[1])
+        check(lib().apds_l2_train_create(C.byref(h), rows_f32.data_ptr() if n else None, n, dim, self.index_base))
+        self._h = h
+        self.mode_used, self.candidates_per_query = None, 0.0     # of the last top2()
+
+    def info(self):
+        """(n_train, dim, screen_ready)"""
+        n, dim, ready = C.c_int64(0), C.c_int(0), C.c_int(0)
+        check(lib().apds_l2_train_info(self._h, C.byref(n), C.byref(dim), C.byref(ready)))
+        return n.value, dim.value, bool(ready.value)
+
+    def top2(self, q, mode="screen", out=None):
+        """q: [Q, dim] float32 device tensor -> [Q, 2] int64 keys (f32 bits of d^2 << 32 | row + index_base) on the CURRENT stream. What ran
+        and the re-ranked rows per query are left in .mode_used ("exact" | "screen") and .candidates_per_query."""
+        nq = int(q.shape[0])
+        dst = out[:nq] if out is not None else torch.empty((nq, 2), dtype=torch.int64, device=q.device)
+        used, cpq = C.c_int(-1), C.c_double(0)
+        check(lib().apds_dev_l2_train_top2(self._h, q.data_ptr() if nq else None, nq, _lib.L2_MODES[mode], dst.data_ptr() if nq else None, torch_stream(),
+                                           C.byref(used), C.byref(cpq)))
+        self.mode_used, self.candidates_per_query = ("exact", "screen")[used.value], cpq.value
+        return dst
+
+    def close(self):
+        h, self._h = self._h, None
+        if h is not None:
+            check(lib().apds_l2_train_destroy(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # noqa: BLE001
+            pass
+
+
+def dev_l2_ratio_filter(keys, filter_strength, out=None):
+    """apds_dev_l2_ratio_filter on the CURRENT stream: keys [Q, k >= 2] int64 of an L2 matcher -> the matches of get_knn_matches_l2 as a
+    [M, 4] int32 device tensor (16-byte cv::DMatch rows: query, train, image, distance as f32 bits) in query order - a view of `out`
+    ([>= Q, 4] int32) when given."""
+    nq, k = int(keys.shape[0]), int(keys.shape[1])
+    dst = out if out is not None else torch.empty((max(nq, 1), 4), dtype=torch.int32, device=keys.device)
+    n = C.c_int(0)
+    check(lib().apds_dev_l2_ratio_filter(keys.data_ptr() if nq else None, nq, k, float(filter_strength), dst.data_ptr(), C.byref(n), torch_stream()))
+    return dst[:n.value]
 
 
 def dev_crosscheck_match(q_rows64, t_rows64, index_base=0, out=None):
@@ -401,7 +457,12 @@ class FramePipeline:
     def __init__(self, db_rows64, db_xy, index_base=0, group=None, max_points=(1 << 18) - 1, device="cuda:0"):
         self.dev = torch.device(device)
         self.stream = torch.cuda.Stream(self.dev)
+        # float rows ([N, 64] float32: step(.., matcher="l2")) are held as they are; the Hamming matcher's front takes byte rows only
+        self.float_rows = db_rows64.dtype == torch.float32
+        if self.float_rows and group is not None:
+            raise ValueError("float32 DB rows (the L2 matcher) are matched on one GPU: there is no sharded float matcher, group must be None")
         self.matcher = ShardedMatcher(db_rows64, index_base, group)
+        self.desc_f32 = None               # [cap, 64] float32, made by the first float step
         self.db_xy_all = db_xy                      # [N_total, 2] f32 on device (replicated: 8 B/row)
         self.cap = max_points
         self.kps = torch.empty((self.cap, 7), dtype=torch.float32, device=self.dev)       # 28-byte cv::KeyPoint rows
@@ -417,6 +478,8 @@ class FramePipeline:
         established path the streamed pose stage is compared against). matcher "crosscheck": get_bruteforce_matches instead of the ratio
         matcher (one GPU; filter_strength is then unused)."""
         code = _matcher_code(matcher)
+        if (code == _lib.PIPELINE_MATCH_L2_RATIO) != self.float_rows:
+            raise _lib.ApdsError(_lib.ERR_BAD_ARG, 'matcher "l2" goes with float32 DB rows, and only with them')
         if code == _lib.PIPELINE_MATCH_CROSSCHECK and self.matcher.handle is not None:
             raise _lib.ApdsError(_lib.ERR_NOT_IMPLEMENTED, "the cross-check over a row-sharded train set is not built")
         with torch.cuda.stream(self.stream):
@@ -433,11 +496,25 @@ class FramePipeline:
         h, w = frame.shape[0], frame.shape[1]
         ch = 1 if frame.dim() == 2 else frame.shape[2]
         n = C.c_int(0)
-        check(L.apds_dev_akaze_extract(frame.data_ptr(), h, w, ch, frame.stride(0), self.cap, self.kps.data_ptr(), self.desc.data_ptr(), self.cap,
-                                       C.byref(n), torch_stream()))
+        if matcher == _lib.PIPELINE_MATCH_L2_RATIO:
+            # the serial composition of the float pipeline: float extraction -> exact L2 top-2 -> L2 ratio filter
+            if self.desc_f32 is None:
+                self.desc_f32 = torch.empty((self.cap, 64), dtype=torch.float32, device=self.dev)
+            check(L.apds_dev_akaze_extract_float(frame.data_ptr(), h, w, ch, frame.stride(0), None, 0, 0, self.cap, self.kps.data_ptr(), self.desc_f32.data_ptr(),
+                                                 self.cap, C.byref(n), torch_stream()))
+        else:
+            check(L.apds_dev_akaze_extract(frame.data_ptr(), h, w, ch, frame.stride(0), self.cap, self.kps.data_ptr(), self.desc.data_ptr(), self.cap,
+                                           C.byref(n), torch_stream()))
         K = n.value
         out = dict(n_keypoints=K, n_matches=0, H=None, n_inliers=0)
-        if matcher == _lib.PIPELINE_MATCH_CROSSCHECK:
+        if matcher == _lib.PIPELINE_MATCH_L2_RATIO:
+            if K == 0:
+                return out
+            rows = self.matcher.rows
+            keys = torch.empty((K, 2), dtype=torch.int64, device=self.dev)
+            check(L.apds_dev_l2_topk(self.desc_f32.data_ptr(), K, rows.data_ptr(), int(rows.shape[0]), 64, self.matcher.index_base, 2, keys.data_ptr(), torch_stream()))
+            M = int(dev_l2_ratio_filter(keys, filter_strength, out=self.matches).shape[0])
+        elif matcher == _lib.PIPELINE_MATCH_CROSSCHECK:
             if K == 0:
                 return out
             M = int(dev_crosscheck_match(self.desc[:K], self.matcher.rows, self.matcher.index_base, out=self.matches).shape[0])
@@ -488,6 +565,11 @@ class StreamedFramePipeline:
         # front of the homography and the pose (K is expected to be the pose stage's camera matrix); None: no lens
         self.lens = None if lens is None else (_lib.lens_args(lens[0], lens[1]), int(lens[2]) if len(lens) > 2 else 5)
         self.matcher_mode = _matcher_code(matcher)   # "ratio" | "crosscheck" (apds_pipeline_set_matcher; one GPU and per-frame-view pipelines)
+        # "l2": the float pipeline (apds_pipeline_create_float) - db_rows64 is then [N, 64] float32; one GPU, a fixed train set
+        self.float_rows = self.matcher_mode == _lib.PIPELINE_MATCH_L2_RATIO
+        if self.float_rows and (per_frame_table is not None or group is not None or db_rows64 is None or db_rows64.dtype != torch.float32
+                                or db_rows64.dim() != 2 or db_rows64.shape[1] != 64 or not db_rows64.is_contiguous()):
+            raise ValueError('matcher "l2": a contiguous [N, 64] float32 device tensor of train rows, one GPU, no per-frame table')
         self.dev = torch.device(device)
         self.per_frame_table = per_frame_table     # a KeypointTable: the train set is selected from it per frame (from_table)
         self.view_capacity = int(view_capacity) if view_capacity else 0
@@ -563,10 +645,12 @@ class StreamedFramePipeline:
         check(lib().apds_set_device(self.dev.index or 0))
         if self.per_frame_table is not None:
             check(lib().apds_pipeline_create_table(C.byref(h), self.per_frame_table._h, self.view_capacity, C.byref(p)))
+        elif self.float_rows:
+            check(lib().apds_pipeline_create_float(C.byref(h), m.rows.data_ptr(), int(m.rows.shape[0]), m.index_base, self.db_kp.data_ptr(), self.n_db, C.byref(p)))
         else:
             check(lib().apds_pipeline_create(C.byref(h), m.rows.data_ptr(), int(m.rows.shape[0]), m.index_base, m.handle, self.db_kp.data_ptr(), self.n_db, C.byref(p)))
         self._pipe, self._key = h, key
-        if self.matcher_mode != _lib.PIPELINE_MATCH_RATIO:     # (a pipeline that never asks runs the ratio matcher)
+        if self.matcher_mode not in (_lib.PIPELINE_MATCH_RATIO, _lib.PIPELINE_MATCH_L2_RATIO):     # (a pipeline that never asks runs the ratio matcher)
             rc = lib().apds_pipeline_set_matcher(h, self.matcher_mode)
             if rc != 0:
                 why = lib().apds_last_error().decode("utf-8", "replace")

@@ -407,6 +407,20 @@ int apds_dev_l2_topk(const void* query, int n_query, const void* train, int64_t 
 enum { APDS_L2_EXACT = 0, APDS_L2_SCREEN = 1 };
 int apds_dev_l2_topk_ex(const void* query, int n_query, const void* train, int64_t n_train, int dim, uint32_t index_base, int k, int mode, void* out_keys,
                         void* stream, int* mode_used, double* candidates_per_query);
+/* A resident L2 train set: n_train rows of dim floats (dim 1..128) whose global indices start at index_base, BORROWED until
+ * apds_l2_train_destroy and unchanged meanwhile. What the screen derives from the rows is made once, here, and owned by the handle: |t|^2
+ * per row (the exact kernel's value), the bf16 copy pre-scaled by -2 and the largest norm. *screen_ready (apds_l2_train_info; every
+ * output may be NULL) = 1 iff dim is 64 or 128, the rows are 16-byte aligned and n_train >= 2: the bf16 screen exists for that handle.
+ * apds_dev_l2_train_top2: out_keys = the keys of apds_dev_l2_topk(query, n_query, rows, n_train, dim, index_base, k = 2), bit for bit, in
+ * either mode (APDS_L2_EXACT / APDS_L2_SCREEN); per call only the query side is prepared, and the scratch is the calling thread's workspace
+ * (nothing grows with the number of calls). A handle that is not screen_ready, a query pointer that is not 16-byte aligned and a candidate
+ * overflow run the exact kernel for that call: *mode_used says which ran, *candidates_per_query = re-ranked rows per query (both may be
+ * NULL). The handle lives on the calling thread's device; concurrent calls on one handle are allowed (it is read-only after create). */
+int apds_l2_train_create(void** set, const void* train_f32_dev, int64_t n_train, int dim, uint32_t index_base);
+int apds_l2_train_destroy(void* set);
+int apds_l2_train_info(const void* set, int64_t* n_train, int* dim, int* screen_ready);
+int apds_dev_l2_train_top2(void* set, const void* query_f32_dev, int n_query, int mode, void* out_keys, void* stream, int* mode_used,
+                           double* candidates_per_query);
 
 /* GPU-resident keypoint table: the reference's `keypoint` table and its access paths without Postgres.
  * insert: preprocessor/src/main.rs:296-324 (x,y lifted to level-of-detail-0 pixels: v * 2^lod + index * tile * 2^lod).
@@ -702,6 +716,18 @@ int apds_pipeline_submit_select(void* pipe, const void* frame, size_t stride_byt
 #define APDS_PIPELINE_MATCH_RATIO 0
 #define APDS_PIPELINE_MATCH_CROSSCHECK 1
 int apds_pipeline_set_matcher(void* pipe, int matcher);
+/* The float pipeline: the same stages over M-SURF descriptors (64 x f32, apds_dev_akaze_extract_float) and the L2 matcher. db_rows_f32_dev
+ * = n_rows x 64 floats (256-byte rows, 16-byte aligned, n_rows >= 2) whose global indices start at index_base; db_kps_dev / n_db_total
+ * as apds_pipeline_create takes them. The extraction workers fill slot buffers of 256 bytes per row, the match worker calls
+ * apds_dev_l2_train_top2 on a train set made here and released by apds_pipeline_destroy, the homography stage builds its matches with
+ * apds_dev_l2_ratio_filter (filter_strength on the distances, not their squares); matched points, homography, pose and lens are unchanged.
+ * Its matcher is APDS_PIPELINE_MATCH_L2_RATIO from birth: apds_pipeline_set_matcher with any other value on a float pipeline, and with
+ * this value on a byte-row pipeline, is APDS_ERR_BAD_ARG before any device work. One GPU, a fixed train set: there is no float constructor
+ * over a shard handle or a table. The starvation watch and the LDS cap belong to the Hamming scan and stay off. The match runs the
+ * bf16 screen (measured 5x faster than the exact kernel on M-SURF rows; the keys are the same). */
+#define APDS_PIPELINE_MATCH_L2_RATIO 2
+int apds_pipeline_create_float(void** pipe, const void* db_rows_f32_dev, int64_t n_rows, uint32_t index_base, const void* db_kps_dev, int64_t n_db_total,
+                               const apds_pipeline_params* params);
 /* The pipeline's lens (opt-in; a pipeline that never calls this, or calls it with no distortion, issues the launches it issued before).
  * The image-side matched points of every frame are undistorted on the device (apds_dev_undistort_points, stride 8, `iters` steps, <= 0: 5)
  * on the stage's own stream, with nothing more synchronised with the host: in the homography stage right after the matched-points gather
@@ -769,6 +795,10 @@ int apds_dev_hamming_topk_backend(const void* query_rows64, int n_query, const v
 int apds_dev_match_backend(int* matrix_cores);
 /* Lowe ratio filter on merged keys (k >= 2): writes compacted matches in query order, count to *n_matches (host). */
 int apds_dev_ratio_filter(const void* keys, int n_query, int k, float filter_strength, void* out_matches, int* n_matches, void* stream);
+/* The same on the keys of the L2 matchers (apds_dev_l2_topk, apds_dev_l2_train_top2: f32 bits of d^2 << 32 | row): the distances are
+ * sqrtf(d^2), the values apds_l2_knn_match returns; a query is kept iff both keys are present and d0 < d1 * filter_strength in f32;
+ * distance = d0, train_idx = the key's row. The matches of get_knn_matches_l2, record for record, in query order. */
+int apds_dev_l2_ratio_filter(const void* keys, int n_query, int k, float filter_strength, void* out_matches, int* n_matches, void* stream);
 /* Cross-check: given for every train row its best query key (from apds_dev_hamming_topk with roles swapped, k=1),
  * produce matches in query order. */
 int apds_dev_cross_check(const void* train_best_keys, int64_t n_train, int n_query, void* out_matches, int* n_matches, void* stream);
@@ -850,6 +880,10 @@ int apds_live_contexts(void);
 /* apds_thread_release keeps the thread's device workspace in a process-wide cache (a later thread reuses it instead of allocating);
  * this frees everything in that cache. */
 int apds_release_cached_memory(void);
+/* The device workspaces of the process: *slab_bytes = bytes held right now by every thread's workspace and by the cache above,
+ * *slab_allocations = device allocations made for them since the library was loaded (either may be NULL). A steady state allocates
+ * nothing: both figures stand still over any number of calls of the same shapes. Diagnostic; no device work. */
+int apds_workspace_info(int64_t* slab_bytes, int64_t* slab_allocations);
 
 /* Test hook: run apds_akaze_extract and copy one intermediate plane of evolution level `level` to out_plane
  * (which: 0 Lt, 2 Lx, 3 Ly, 4 Ldet as f32 w*h; 7 keypoint mask after cross-level suppression as u8 w*h; 8 contrast factor, 1 float). */

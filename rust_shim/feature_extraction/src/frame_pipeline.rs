@@ -75,6 +75,30 @@ impl FramePipeline {
         Ok(FramePipeline { pipe, stride: (cols * channels) as usize })
     }
 
+    /// The float pipeline (`apds_pipeline_create_float`): M-SURF descriptors (64 x f32), the L2 matcher on a resident train set and the L2
+    /// ratio filter; everything behind the matches as in `new`. `train_rows_f32_dev`: n x 64 floats on the device (16-byte aligned, n >= 2),
+    /// `train_kps_dev`: their n `KeyPoint`s; both stay borrowed until the pipeline is dropped. `filter_strength`: the ratio on the distances.
+    /// Its matcher is `APDS_PIPELINE_MATCH_L2_RATIO` for life: `set_matcher` on it is an error.
+    pub fn new_float(gpu: i32, rows: i32, cols: i32, channels: i32, train_rows_f32_dev: *const c_void, train_kps_dev: *const c_void, n: i64,
+                     filter_strength: f32, method: i32, reproj_threshold: f64) -> Result<Self, String> {
+        let params = apds_pipeline_params {
+            rows, cols, channels, max_points: 0, n_slots: 0, extract_workers: 0, filter_strength, homography_method: method, reproj_threshold,
+            max_iters: 0, confidence: 0.0, timing: 0, match_lds_cap: 0, match_stream: ptr::null_mut(), debug_extract_delay_ms: 0.0,
+        };
+        let mut pipe = ptr::null_mut();
+        unsafe {
+            let rc = apds_sys::apds_set_device(gpu);
+            if rc != 0 {
+                return Err(err(rc));
+            }
+            let rc = apds_sys::apds_pipeline_create_float(&mut pipe, train_rows_f32_dev, n, 0, train_kps_dev, n, &params);
+            if rc != 0 {
+                return Err(err(rc));
+            }
+        }
+        Ok(FramePipeline { pipe, stride: (cols * channels) as usize })
+    }
+
     /// Hands a frame in host memory over (the `Mat::data()` of a CV_8UC4 frame); returns its number. Blocks only while every slot is in
     /// flight. The pixels must stay valid until the frame's result has been polled.
     pub fn submit(&self, pixels: &[u8]) -> Result<i64, String> {
