@@ -64,8 +64,11 @@ __device__ __forceinline__ void top2_insert(Top2& b, float qq, float u, uint32_t
     }
 }
 
-__device__ __forceinline__ uint64_t l2_key(float d, uint32_t idx) {
-    return idx == 0xFFFFFFFFu ? EMPTY_KEY : ((uint64_t)__float_as_uint(d) << 32) | idx;   // d >= 0: bit pattern order == value order
+// The key of a list slot holding u: d^2 = max(|q|^2 + u, 0), the value the insertions ranked on (d >= 0: bit pattern order == value order).
+// An unfilled slot is told by its u = +inf - an inserted u is below the +inf it displaced - and not by its index: row + index_base takes
+// every u32 value, 0xFFFFFFFF included (index_base = 2^32 - 3 made row 2 an empty key: tests/test_l2_train_borders_gpu.py).
+__device__ __forceinline__ uint64_t l2_key(float qq, float u, uint32_t idx) {
+    return u == INFINITY ? EMPTY_KEY : ((uint64_t)__float_as_uint(l2_d2(qq, u)) << 32) | idx;
 }
 
 // grid: x = query tiles (128 queries), y = splits of the train tiles. out: [split][nq][K] keys
@@ -236,12 +239,6 @@ __global__ __launch_bounds__(512) void l2_topk_kernel(const float* __restrict__ 
         }
         if (more) commit();
     }
-    // d^2 = max(|q|^2 + u, 0): the value the insertions ranked on
-#pragma unroll
-    for (int n = 0; n < 8; n++) {
-        best[n].d0 = l2_d2(qq[n], best[n].d0);
-        best[n].d1 = l2_d2(qq[n], best[n].d1);
-    }
     // merge the 32 partial lists of every query (8 waves x 4 row classes) through LDS, source-major so that the final scan
     // reads conflict-free; the LDS is reused from its start, hence the barrier (slower waves may still read sQ)
     __syncthreads();
@@ -251,8 +248,8 @@ __global__ __launch_bounds__(512) void l2_topk_kernel(const float* __restrict__ 
 #pragma unroll
         for (int n = 0; n < 8; n++) {
             const int ql = n * 16 + (lane & 15);
-            cand[(src * 2 + 0) * L2_TN + ql] = l2_key(best[n].d0, best[n].i0);
-            cand[(src * 2 + 1) * L2_TN + ql] = l2_key(best[n].d1, best[n].i1);
+            cand[(src * 2 + 0) * L2_TN + ql] = l2_key(qq[n], best[n].d0, best[n].i0);
+            cand[(src * 2 + 1) * L2_TN + ql] = l2_key(qq[n], best[n].d1, best[n].i1);
         }
     }
     __syncthreads();

@@ -123,7 +123,8 @@ __device__ __forceinline__ void sc_insert(ScTop2& b, float d, uint32_t idx) {
         }
     }
 }
-__device__ __forceinline__ uint64_t sc_key(float d, uint32_t idx) { return idx == 0xFFFFFFFFu ? EMPTY_KEY : ((uint64_t)__float_as_uint(d) << 32) | idx; }
+// (an unfilled slot is told by its value, +inf, never by its index: row + index_base may be 0xFFFFFFFF)
+__device__ __forceinline__ uint64_t sc_key(float d, uint32_t idx) { return d == INFINITY ? EMPTY_KEY : ((uint64_t)__float_as_uint(d) << 32) | idx; }
 
 // PASS 0: running top-2 of the screen value per query -> out[split][nq][2] keys (d^2 = max(|q|^2 + u, 0) bits << 32 | row).
 // PASS 1: rows with u <= theta[q] are appended to the block's own region of cand (query << 32 | row; region = cand_cap entries per
@@ -275,7 +276,7 @@ __global__ __launch_bounds__(512) void l2_screen_kernel(const uint16_t* __restri
                 // merge two sorted pairs; equal values: lower row first
                 ScTop2 m = b;
                 auto ins = [&](float d, uint32_t i) {
-                    if (i == 0xFFFFFFFFu) return;
+                    if (d == INFINITY) return;   // an unfilled slot
                     if (d < m.d0 || (d == m.d0 && i < m.i0)) {
                         m.d1 = m.d0;
                         m.i1 = m.i0;

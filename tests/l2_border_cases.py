@@ -1,6 +1,7 @@
 """Inputs, float64 reference and acceptance check for the float L2 matchers (csrc/l2_match.hip, csrc/l2_screen.hip) at the borders of their
 tiles, wave slices, splits, dimensions and sample. Used by test_l2_border_inputs_cpu.py (which shows that every input sits on the border it
-names and that the check accepts an independent implementation and rejects six named mistakes) and by test_l2_borders_gpu.py.
+names and that the check accepts an independent implementation and rejects six named mistakes), by test_l2_borders_gpu.py (the one-shot
+entries) and by test_l2_train_borders_gpu.py (the resident train set). The screen's cases take the row length: 128 or 64.
 
 Reference. d2_64(q, t) = sum_i (q_i - t_i)^2 in numpy float64 on the float32 inputs: its own error (a few 2^-53 relative) is nothing beside
 the bound below.
@@ -43,7 +44,9 @@ L2_LANE_ROWS = 4             # rows of a wave's slice owned by one lane (k class
 L2_BLOCK_TARGET = 512        # blocks the split plan aims at
 SC_Q = 384                   # queries per block of l2_screen_kernel
 SC_TM = 128                  # train rows per tile of the screen
-SC_DIM = 128                 # the only descriptor length the screen takes
+SC_DIMS = (64, 128)          # the two descriptor lengths the screen is built for (128: the one-shot entry and the train set; 64: the train set)
+SC_ROWS_PER_PASS = {128: 32, 64: 64}   # rows that one staged piece of all 512 threads covers: 512 / (dim / 8); a tile is 4 or 2 pieces per thread
+SC_PITCH = {128: 272, 64: 160}         # bytes per staged train row in LDS
 SC_SAMPLE_DIV = 12           # runtime default of the sample divisor (APDS_L2_SAMPLE_DIV)
 SC_SAMPLE_MIN = 8192
 SC_REGION = 384 * 192        # candidate entries per block of pass B
@@ -154,11 +157,11 @@ def accept(keys, q, t, index_base, k):
 
 def accept_case(keys, case, index_base=0, k=2, sel=None):
     """`accept` on a case plus the cap: planted queries decided everywhere, filler pairs to >= 99 %, ties to the lower row, bit-equal
-    distances of copied rows. `sel`: the subset of query indices that `keys` holds (default all)."""
+    distances of copied rows; a query whose second neighbour has copies outside the sample: nearest decided, the lower row second. `sel`: the subset of query indices that `keys` holds (default all)."""
     sel = np.arange(len(case["q"])) if sel is None else np.asarray(sel)
     d = check(keys, case["q"][sel], case["t"], index_base, k)
     planted = np.isin(sel, case["planted_q"])
-    tied = np.isin(sel, [c[0] for c in case["ties"]] + list(case.get("excluded", [])))
+    tied = np.isin(sel, [c[0] for c in case["ties"]] + list(case.get("excluded", [])) + [c[0] for c in case.get("outside_copies", [])])
     assert d[planted].all(), "a planted query is not decided"
     filler = ~planted & ~tied
     if filler.any() and d.shape[1]:
@@ -175,6 +178,9 @@ def accept_case(keys, case, index_base=0, k=2, sel=None):
             assert int(rows[pos[qi], 0]) == lo, ("tie not to the lower row", qi, rows[pos[qi]], lo, hi)
             if d.shape[1] == 2:
                 assert int(rows[pos[qi], 1]) == hi and kb[pos[qi], 0] >> np.uint64(32) == kb[pos[qi], 1] >> np.uint64(32), (qi, rows[pos[qi]])
+    for qi, r0, r1, copies in case.get("outside_copies", []):      # rank 1 has exact copies at higher rows: undecided by the gaps, decided by the row
+        if qi in pos:
+            assert d[pos[qi], 0] and list(rows[pos[qi]]) == [r0, r1][:d.shape[1]], ("a copy outside the sample won over the lower row", qi, rows[pos[qi]], r0, r1, copies)
     return float(d.mean()) if d.size else 1.0
 
 
@@ -341,18 +347,19 @@ EQ_NQ, EQ_NT = 64, 128 * 5 + 37
 EQ_COPY_ROW0 = 520
 
 
-def equal_case(group):
+def equal_case(group, dim=128):
     """64 queries; query i has `group` (4 or 8) rows q_i + 1e-6 N(0, 1) at rows 8 i + (4 if group == 4 and i odd else 0) + 0..group-1: rows
     128 tile + 16 wave + 4 kc + 0..3 belong to one lane, 8 rows to two neighbouring lanes. Row EQ_COPY_ROW0 + i is an exact copy of the
-    second of them. -> dict q, t, rows [64, group + 1] (the near-duplicates of every query, the copy last)"""
-    assert group in (4, 8)
-    rng = np.random.default_rng(0x4C32B600 + group)
-    t, q = _unit(rng, EQ_NT, 128).astype(np.float32), _unit(rng, EQ_NQ, 128).astype(np.float32)
+    second of them. `dim`: 128 or 64 (the same layout; at 64 the values pass through the 64-term chain).
+    -> dict q, t, rows [64, group + 1] (the near-duplicates of every query, the copy last)"""
+    assert group in (4, 8) and dim in SC_DIMS
+    rng = np.random.default_rng((0x4C32B600 if dim == 128 else 0x4C64B600) + group)
+    t, q = _unit(rng, EQ_NT, dim).astype(np.float32), _unit(rng, EQ_NQ, dim).astype(np.float32)
     rows = np.zeros((EQ_NQ, group + 1), np.int64)
     for i in range(EQ_NQ):
         r0 = 8 * i + (4 if group == 4 and i % 2 else 0)
         rows[i, :group] = r0 + np.arange(group)
-        t[rows[i, :group]] = q[i] + (1e-6 * rng.normal(size=(group, 128))).astype(np.float32)
+        t[rows[i, :group]] = q[i] + (1e-6 * rng.normal(size=(group, dim))).astype(np.float32)
         rows[i, group] = EQ_COPY_ROW0 + i
         t[EQ_COPY_ROW0 + i] = t[r0 + 1]
     return {"q": q, "t": t, "rows": rows}
@@ -410,41 +417,67 @@ def emulate_matrix(q, t):
 # --- screen -------------------------------------------------------------------------------------------------------------------------------------
 SCREEN_NQ = [47, 48, 49, 383, 384, 385]
 SCREEN_NT = [2, 129, 8191, 8192, 8193, 140_000]
+# per row length: the same small sizes and one at which the sample is longer than 8192 and shorter than nt (11776 of 140 000 at dim 128;
+# 8448 of 100 000 at dim 64, where 100 x 100 000 x 64 is the largest product a test computes)
+SCREEN_NT_BY_DIM = {128: SCREEN_NT, 64: SCREEN_NT[:-1] + [100_000]}
+SCREEN_NT_LARGE = {dim: nts[-1] for dim, nts in SCREEN_NT_BY_DIM.items()}
 _FILLER = {}
 
 
-def _screen_filler(n, seed):
-    if seed not in _FILLER or len(_FILLER[seed]) < n:
-        _FILLER[seed] = _unit(np.random.default_rng(seed), max(n, 1000), 128).astype(np.float32)
-    return _FILLER[seed][:n]
+def _screen_filler(n, seed, dim=128):
+    key = seed if dim == 128 else (seed, dim)
+    if key not in _FILLER or len(_FILLER[key]) < n:
+        _FILLER[key] = _unit(np.random.default_rng(seed if dim == 128 else 0x4C640000 + seed), max(n, 1000), dim).astype(np.float32)
+    return _FILLER[key][:n]
 
 
-def screen_case(nq, nt):
-    """Unit filler (shared between the cases, never written to); planted pairs on the tile ends and on both candidate borders of the sample
-    (the runtime's default divisor 12 and the 16 of earlier documents); a query whose second best inside the sample has exact copies
-    outside it."""
+def screen_pairs(nt, dim=128):
+    """(f, l) row pairs that screen_case plants: the sample border (s - 1, s) (or the last two rows where the sample is the whole set), the
+    tile ends, the divisor-16 border. dim 64 adds the rows that the SECOND staged piece of a thread carries: (63, 64), the border of
+    ROWS_PER_PASS, and (127, 128), the tile's end, in the first tile (row 0 is then paired with the last row of the second tile, as row
+    127 is taken), and a pair inside the last tile where it is partial: its first row and the middle one (at 8191 rows: row 63 of it)."""
     s = screen_sample_rows(nt)
-    pairs = [(0, nt - 1)] if nt <= 129 else [(s - 1, s) if s < nt else (nt - 2, nt - 1), (0, 127)]
+    if dim == 128:
+        pairs = [(0, nt - 1)] if nt <= 129 else [(s - 1, s) if s < nt else (nt - 2, nt - 1), (0, 127)]
+    elif nt < 129:
+        pairs = [(0, nt - 1)]
+    elif nt == 129:
+        pairs = [(0, 126), (63, 64), (127, 128)]
+    else:
+        pairs = [(s - 1, s) if s < nt else (nt - 2, nt - 1), (0, 255), (SC_ROWS_PER_PASS[64] - 1, SC_ROWS_PER_PASS[64]), (SC_TM - 1, SC_TM)]
     s16 = screen_sample_rows(nt, 16)
     if s16 < s < nt:
         pairs.append((s16 - 1, s16))
-    case = {"dim": 128}
-    rng = np.random.default_rng(0x4C32B700 + nt + nq)
-    t, q = _screen_filler(nt, 11).copy(), _screen_filler(nq, 12).copy()
+    if dim == 64 and nt > 129 and nt % SC_TM >= 2:
+        last0 = nt // SC_TM * SC_TM
+        pairs.append((last0, last0 + (nt - last0 - 1) // 2))
+    return pairs
+
+
+def screen_case(nq, nt, dim=128):
+    """Unit filler (shared between the cases, never written to); planted pairs on the tile ends and on both candidate borders of the sample
+    (the runtime's default divisor 12 and the 16 of earlier documents), at dim 64 also on the rows of the second staged piece
+    (screen_pairs); a query whose second best inside the sample has exact copies outside it."""
+    assert dim in SC_DIMS
+    s = screen_sample_rows(nt)
+    pairs = screen_pairs(nt, dim)
+    case = {"dim": dim}
+    rng = np.random.default_rng((0x4C32B700 if dim == 128 else 0x4C64B700) + nt + nq)
+    t, q = _screen_filler(nt, 11, dim).copy(), _screen_filler(nq, 12, dim).copy()
     slots = query_slots(nq)
     planted, ties = [], []
     for f, l in pairs:
-        c = _unit(rng, 1, 128)[0]
-        e1 = _offset(rng, 128, 0.1)
-        e2 = _offset(rng, 128, 0.2, avoid=e1)
+        c = _unit(rng, 1, dim)[0]
+        e1 = _offset(rng, dim, 0.1)
+        e2 = _offset(rng, dim, 0.2, avoid=e1)
         a, b = slots.pop(0), slots.pop(0)
         t[f], t[l], q[a], q[b] = c, c - e1 + e2, c - e1, c + e2
         planted += [(a, f, l), (b, l, f)]
     if nt - s >= 8:  # nearest and second inside the sample; copies of the second outside it: the lower row keeps rank 1 (at 8193 the
                      # one row outside the sample belongs to the pair above)
-        c = _unit(rng, 1, 128)[0]
-        e1 = _offset(rng, 128, 0.1)
-        e2 = _offset(rng, 128, 0.2, avoid=e1)
+        c = _unit(rng, 1, dim)[0]
+        e1 = _offset(rng, dim, 0.1)
+        e2 = _offset(rng, dim, 0.2, avoid=e1)
         a = slots.pop(0)
         t[300], t[301], q[a] = c, c - e1 + e2, c - e1
         t[s + 5] = t[301]
@@ -452,6 +485,12 @@ def screen_case(nq, nt):
         ties.append((a, 300, 301, (s + 5, nt - 2)))
     case.update(q=q, t=t, planted=planted, planted_q=np.array([p[0] for p in planted], np.int64), ties=[], outside_copies=ties, sample=s)
     return case
+
+
+def screen_case_checked_queries(case):
+    """the queries of a large screen case that `accept` is run on: the planted ones and the one with copies outside the sample (among
+    100 000 unit rows of 64 elements the filler's nearest neighbours lie closer together than 2 B too often for the 99 % cap)"""
+    return np.unique(np.concatenate([case["planted_q"], np.array([c[0] for c in case["outside_copies"]], np.int64)]))
 
 
 def bf16_round(x):
@@ -465,31 +504,38 @@ BESIDE_MIDPOINT = np.float32(1.0 + 2.0 ** -9)
 ADV_QUERIES, ADV_RIVALS = 16, 6
 
 
-def adversarial_case():
+ADV_PARAMS = {128: dict(a=0.12, b=0.02, gap0=6e-4, gap_step=2e-4, raised=3, seed=0x4C32B800),
+              64: dict(a=0.12, b=0.02, gap0=3e-4, gap_step=1e-4, raised=1, seed=0x4C64B800)}
+
+
+def adversarial_case(dim=128):
     """Every element is +-m (1 + 2^-9) with m a bf16 value: bf16 rounding takes every element to m, a relative error of -2^-9 each, all in
     the same direction, so q~.t~ = q.t / (1 + 2^-9)^2 exactly: the screen value of a row is too large by ~2^-7 q.t.
-    Adversarial query (16 of them, each with its own random signs s): |q_i| = a on the first 64 axes and b on the last 64 (a = 0.12,
-    b = 0.02). Its true nearest row t0 = s * (b.., a..) and second t1 (t0 with three magnitudes one bf16 step up) have every product
-    q_i t_i > 0: their errors add up to ~2^-7 * 0.31 = 2.4e-3. Six rivals have magnitude c in pairs of axes with signs (+s, -s): q.r = 0
-    term by term, their screen value has no error; their norms are tuned (pairs at one bf16 step above c) to put them 6e-4 .. 1.6e-3
-    FARTHER than t0 in truth, so the screen ranks all six BEFORE t0 and t1. Filler rows and queries: unit Gaussian, same element form.
+    Adversarial query (16 of them, each with its own random signs s): |q_i| = a on the first dim / 2 axes and b on the last dim / 2
+    (a = 0.12, b = 0.02). Its true nearest row t0 = s * (b.., a..) and second t1 (t0 with three magnitudes one bf16 step up; one at dim 64)
+    have every product q_i t_i > 0: their errors add up to ~2^-7 * 0.31 = 2.4e-3 (half of that at dim 64). Six rivals have magnitude c in
+    pairs of axes with signs (+s, -s): q.r = 0 term by term, their screen value has no error; their norms are tuned (pairs at one bf16
+    step above c) to put them 6e-4 .. 1.6e-3 FARTHER than t0 in truth (3e-4 .. 8e-4 at dim 64, where the error that must cover them is
+    half as large), so the screen ranks all six BEFORE t0 and t1. Filler rows and queries: unit Gaussian, same element form. The
+    parameters were fixed on the CPU (test_l2_border_inputs_cpu.py asserts what they must achieve), none against a device result.
     -> dict q, t, adv [(query, t0 row, t1 row, [rival rows])]"""
-    rng = np.random.default_rng(0x4C32B800)
-    nq, nt, dim = 50, 128 * 2 + 72, 128
+    P = ADV_PARAMS[dim]
+    rng = np.random.default_rng(P["seed"])
+    nq, nt, h = 50, 128 * 2 + 72, dim // 2
     form = lambda x: (bf16_round(np.asarray(x, np.float32)) * BESIDE_MIDPOINT).astype(np.float32)
     t, q = form(_unit(rng, nt, dim)), form(_unit(rng, nq, dim))
-    a, b = bf16_round(np.float32(0.12)), bf16_round(np.float32(0.02))
+    a, b = bf16_round(np.float32(P["a"])), bf16_round(np.float32(P["b"]))
     step_a = np.float32(2.0 ** (np.floor(np.log2(a)) - 7))
     adv, row = [], 0
     s0 = rng.choice([-1.0, 1.0], size=dim).astype(np.float32)
     for i in range(ADV_QUERIES):
         # the queries' signs differ by flips of whole axis pairs: a rival of ANOTHER adversarial query then also has q.r = 0 term by term,
         # and is one more rival at the same distances, instead of landing anywhere within +-0.1 of them
-        s = s0 * np.repeat(rng.choice([-1.0, 1.0], size=64), 2).astype(np.float32)
-        qa = s * np.concatenate([np.full(64, a), np.full(64, b)]).astype(np.float32)
-        m0 = np.concatenate([np.full(64, b), np.full(64, a)]).astype(np.float32)
+        s = s0 * np.repeat(rng.choice([-1.0, 1.0], size=h), 2).astype(np.float32)
+        qa = s * np.concatenate([np.full(h, a), np.full(h, b)]).astype(np.float32)
+        m0 = np.concatenate([np.full(h, b), np.full(h, a)]).astype(np.float32)
         m1 = m0.copy()
-        m1[64:67] += step_a
+        m1[h:h + P["raised"]] += step_a
         qi = 3 * i
         q[qi] = form(qa)
         t[row], t[row + 1] = form(s * m0), form(s * m1)
@@ -497,21 +543,47 @@ def adversarial_case():
         qn = float((q[qi].astype(np.float64) ** 2).sum())
         rivals = []
         for k in range(ADV_RIVALS):
-            target = d0 - qn + 6e-4 + 2e-4 * k                      # the rival's |r|^2: q.r = 0, so d^2 = |q|^2 + |r|^2
+            target = d0 - qn + P["gap0"] + P["gap_step"] * k        # the rival's |r|^2: q.r = 0, so d^2 = |q|^2 + |r|^2
             c_lo = (np.array([np.sqrt(target / dim) / float(BESIDE_MIDPOINT)], np.float32).view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)[0]
             c_hi = np.float32(c_lo + np.float32(2.0 ** (np.floor(np.log2(c_lo)) - 7)))
             lo2, hi2 = (float(c_lo) * float(BESIDE_MIDPOINT)) ** 2, (float(c_hi) * float(BESIDE_MIDPOINT)) ** 2
-            n_hi = int(np.clip(np.ceil((target - dim * lo2) / (2 * (hi2 - lo2))), 0, 64))
-            mags = np.repeat(np.where(rng.permutation(64) < n_hi, c_hi, c_lo).astype(np.float32), 2)
-            flip = np.repeat(rng.choice([-1.0, 1.0], size=64), 2).astype(np.float32) * np.tile(np.array([1.0, -1.0], np.float32), 64)
+            n_hi = int(np.clip(np.ceil((target - dim * lo2) / (2 * (hi2 - lo2))), 0, h))
+            mags = np.repeat(np.where(rng.permutation(h) < n_hi, c_hi, c_lo).astype(np.float32), 2)
+            flip = np.repeat(rng.choice([-1.0, 1.0], size=h), 2).astype(np.float32) * np.tile(np.array([1.0, -1.0], np.float32), h)
             t[row + 2 + k] = form(s * flip * mags)
             rivals.append(row + 2 + k)
         adv.append((qi, row, row + 1, rivals))
         row += 2 + ADV_RIVALS
-    return {"q": q, "t": t, "adv": adv}
+    return {"q": q, "t": t, "adv": adv, "dim": dim}
 
 
 def screen_values(q, t):
     """float64 screen value |q|^2 + |t|^2 - 2 q~.t~ with q~, t~ rounded to bf16"""
     q64, t64 = q.astype(np.float64), t.astype(np.float64)
     return (q64 * q64).sum(1)[:, None] + (t64 * t64).sum(1)[None, :] - 2.0 * bf16_round(q).astype(np.float64) @ bf16_round(t).astype(np.float64).T
+
+
+def screen_eps(q, t):
+    """eps(q) of screen_theta_kernel in float64: 2 (2u + u^2) |q| Tmax + 2^-13 (|q|^2 + Tmax^2), u = 2^-8, Tmax the largest row norm"""
+    qn = (q.astype(np.float64) ** 2).sum(1)
+    tm = (t.astype(np.float64) ** 2).sum(1).max()
+    u = 2.0 ** -8
+    return 2.0 * (2.0 * u + u * u) * np.sqrt(qn) * np.sqrt(tm) + (qn + tm) * 2.0 ** -13
+
+
+def emulate_screen(q, t, eps_scale=1.0, whole_set_s2=False, drop_second_piece=False, exact=None):
+    """The screen in numpy: float64 screen values -> s2 of the sample -> rows with S <= s2 + 2 eps -> their exact values re-ranked.
+    `exact`: the float32 [nq, nt] values of the exact kernel (default: emulate_matrix). Three mistakes for the CPU test to reject:
+    eps_scale = 0 (no margin); whole_set_s2 (the second smallest screen value of ALL rows as the threshold, no margin: what a sample's
+    s2 is not); drop_second_piece (rows 64..127 of every tile never become candidates: the second staged piece at dim 64).
+    -> (keys [nq, 2], candidates per query)"""
+    S = screen_values(q, t)
+    n_s = len(t) if whole_set_s2 else screen_sample_rows(len(t))
+    s2 = np.sort(S[:, :n_s], axis=1)[:, 1]
+    theta = s2 + (0.0 if whole_set_s2 else 2.0 * eps_scale) * screen_eps(q, t)
+    cand = S <= theta[:, None]
+    if drop_second_piece:
+        cand[:, np.arange(len(t)) % SC_TM >= 64] = False
+    F = (emulate_matrix(q, t) if exact is None else exact).copy()
+    F[~cand] = np.inf
+    return topk_keys(F, 2), float(cand.sum(1).mean())

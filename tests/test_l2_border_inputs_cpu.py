@@ -1,7 +1,9 @@
 """CPU: the inputs, the bound and the acceptance check of test_l2_borders_gpu.py (l2_border_cases.py). Every case is shown to sit on the
 border it names, computed from the restated launch geometry; the cap (planted queries decided at both ranks, filler pairs to 99 %) is
 checked with the float64 reference alone; `accept` passes the oracle's independent f32 matcher on every case, keeps a numpy binary32
-emulation of the kernel's formula within the bound, and rejects six named mistakes applied to that emulation's keys."""
+emulation of the kernel's formula within the bound, and rejects six named mistakes applied to that emulation's keys. The screen's cases
+are shown at both row lengths it is built for (64 and 128), also for test_l2_train_borders_gpu.py; a numpy emulation of the screen
+(bf16 screen values, sample threshold, exact re-rank) is accepted by them and rejected under three mistakes of a screen."""
 import numpy as np
 import pytest
 
@@ -30,13 +32,23 @@ def small_cases():
     return dict(_small_cases())
 
 
-def test_restated_geometry():
+@pytest.mark.parametrize("dim", bc.SC_DIMS)
+def test_restated_geometry(dim):
     assert bc.L2_TM == bc.L2_TN == 128 and bc.SC_Q == 384 and bc.SC_TM == 128 and bc.SC_REGION == 73728
     assert bc.split_plan(128 * 17 - 1, 8200) == (17, 6, 3) and bc.split_plan(128 * 17, 8200) == (17, 6, 3) and bc.split_plan(128 * 17 + 1, 8200) == (18, 6, 3)
     assert bc.split_plan(385, 129) == (4, 4, 1) and bc.split_plan(257, 130) == (3, 3, 1) and bc.split_plan(385, 1) == (4, 4, 1)
     assert bc.split_plan(70_000, 384, bc.SC_TM, bc.SC_Q) == (547, 274, 2) and 2 * bc.SC_TM * 384 == 98304 > bc.SC_REGION
-    assert [bc.screen_sample_rows(n) for n in bc.SCREEN_NT] == [2, 129, 8191, 8192, 8192, 11776]
-    assert bc.screen_sample_rows(140_000, 16) == 8832          # a divisor of 16, as earlier documents state it
+    # the staging of a tile: 128 rows x dim / 8 pieces of 16 bytes over 512 threads; piece p of a thread is row ROWS_PER_PASS p + tid / (dim / 8)
+    groups = dim // 8
+    pieces = bc.SC_TM * groups // 512
+    assert bc.SC_ROWS_PER_PASS[dim] == 512 // groups == {128: 32, 64: 64}[dim] and pieces == dim // 32 == bc.SC_TM // bc.SC_ROWS_PER_PASS[dim]
+    assert bc.SC_PITCH[dim] == {128: 272, 64: 160}[dim] and bc.SC_PITCH[dim] % 16 == 0 and bc.SC_PITCH[dim] >= 2 * dim + 16      # bf16 rows, padded
+    assert 2 * bc.SC_TM * bc.SC_PITCH[dim] + 2 * bc.SC_TM * 4 <= 160 * 1024 // 2                                          # two buffers + norms
+    nts = bc.SCREEN_NT_BY_DIM[dim]
+    assert nts[:5] == [2, 129, 8191, 8192, 8193] and nts[5] == bc.SCREEN_NT_LARGE[dim] == {128: 140_000, 64: 100_000}[dim]
+    assert [bc.screen_sample_rows(n) for n in nts] == [2, 129, 8191, 8192, 8192, {128: 11776, 64: 8448}[dim]]
+    assert bc.screen_sample_rows(140_000, 16) == 8832 and bc.screen_sample_rows(100_000, 16) == 8192   # a divisor of 16, as earlier documents state it
+    assert bc.screen_sample_rows(98_304) == 8192 and bc.screen_sample_rows(98_316) == 8320           # where nt / 12 first passes the floor
 
 
 def test_tile_cases_sit_on_the_tile_borders(small_cases):
@@ -83,7 +95,32 @@ def test_split_cases_sit_on_the_split_borders():
             bc.accept_case(keys, sub, sel=sel)
 
 
-def test_the_cap_holds_by_the_reference_alone(small_cases):
+def _screen_cases(dim):
+    """(name, case, the queries `accept_case` runs on or None for all) of the screen at one row length"""
+    for nq in bc.SCREEN_NQ:
+        yield f"screen-nq{nq}", bc.screen_case(nq, 300, dim), None
+    for nt in bc.SCREEN_NT_BY_DIM[dim]:
+        case = bc.screen_case(100, nt, dim)
+        yield f"screen-nt{nt}", case, (None if nt <= 8193 else bc.screen_case_checked_queries(case))
+
+
+@pytest.mark.parametrize("dim", bc.SC_DIMS)
+def test_the_cap_holds_by_the_reference_alone(small_cases, dim):
+    """dim 128: every case of the exact kernel (all at 128 but the dimension cases). dim 64: the screen's cases at 64 elements per row: every
+    planted query decided at both ranks, the filler to 99 %, for every case of at most 8193 rows; at 100 000 rows the cap is asked of
+    the planted and outside-copy queries, the filler's decided share is printed and not conditioned on (measured: 1.000)."""
+    if dim == 64:
+        for name, case, sel in _screen_cases(64):
+            q = case["q"] if sel is None else case["q"][sel]
+            share = bc.accept_case(bc.topk_keys(bc.d2_64(q, case["t"]).astype(np.float32), 2), case, sel=sel)
+            assert share >= 0.99 or len(case["t"]) < 3 or sel is not None, (name, share)
+            if sel is not None:
+                rest = np.setdiff1d(np.arange(len(case["q"])), sel)
+                d = bc.check(bc.topk_keys(bc.d2_64(case["q"][rest], case["t"]).astype(np.float32), 2), case["q"][rest], case["t"], 0, 2)
+                print(f"dim 64, {name}: filler pairs decided {d.mean():.3f}")
+            if len(case["t"]) == 300:
+                bc.accept_case(_reference_keys(case, 1), case, k=1)
+        return
     for name, case in small_cases.items():
         for k in (1, 2):
             share = bc.accept_case(_reference_keys(case, k), case, k=k)
@@ -175,9 +212,11 @@ def test_emulated_kernel_passes_and_six_mistakes_do_not(small_cases):
     rejected(bc.topk_keys(np.maximum(Fb.astype(np.float64) - 4 * B, 0).astype(np.float32), 2), base)
 
 
-def test_equal_distance_cases_share_lanes():
+@pytest.mark.parametrize("dim", bc.SC_DIMS)
+def test_equal_distance_cases_share_lanes(dim):
     for group in (4, 8):
-        case = bc.equal_case(group)
+        case = bc.equal_case(group, dim)
+        assert case["q"].shape == (bc.EQ_NQ, dim) and case["t"].shape == (bc.EQ_NT, dim)
         rows = case["rows"]
         lane = rows[:, :group] // bc.L2_LANE_ROWS                                # (tile, wave, kc) of a row
         assert (lane[:, :4] == lane[:, :1]).all() and (rows[:, :group] % bc.L2_LANE_ROWS == np.arange(group) % 4).all()
@@ -194,39 +233,105 @@ def test_equal_distance_cases_share_lanes():
         assert D[np.arange(bc.EQ_NQ)[:, None], rows].max() < 1e-9 and far > 1.0
 
 
-def test_screen_cases_sit_on_the_sample_border():
-    for nt in bc.SCREEN_NT:
-        case = bc.screen_case(100, nt)
+@pytest.mark.parametrize("dim", bc.SC_DIMS)
+def test_screen_cases_sit_on_the_sample_border(dim):
+    large = bc.SCREEN_NT_LARGE[dim]
+    for nt in bc.SCREEN_NT_BY_DIM[dim]:
+        case = bc.screen_case(100, nt, dim)
         s = case["sample"]
-        assert s == bc.screen_sample_rows(nt)
-        if nt in (8193, 140_000):
+        assert s == bc.screen_sample_rows(nt) and case["q"].shape == (100, dim) and case["t"].shape == (nt, dim)
+        pairs = [p[1:] for p in case["planted"]]
+        assert len(np.unique([p[0] for p in case["planted"]])) == len(case["planted"])        # a query of its own per planted neighbour pair
+        assert len(np.unique([r for p in pairs[::2] for r in p])) == len(pairs)               # no row planted twice
+        if nt in (8193, large):
             a, near, second = case["planted"][0]
             assert (near, second) == (s - 1, s) and case["planted"][1][1:] == (s, s - 1)     # nearest inside / second outside, and the reverse
-        if nt == 140_000:
-            assert (8831, 8832) in [p[1:] for p in case["planted"]]
+        if nt == large:
+            assert 8192 < s < nt and s == {128: 11776, 64: 8448}[dim]
+            s16 = bc.screen_sample_rows(nt, 16)
+            assert s16 == {128: 8832, 64: 8192}[dim] and (s16 - 1, s16) in pairs and (s16, s16 - 1) in pairs
             (a, r0, r1, copies), = case["outside_copies"]
             assert r1 < s and min(copies) >= s and all(np.array_equal(case["t"][c], case["t"][r1]) for c in copies)
+            assert not set(copies) & {r for p in pairs for r in p}
+        if dim == 64 and nt >= 129:
+            # the rows of a thread's second staged piece: (63, 64) across ROWS_PER_PASS, (127, 128) across the tile's end, both orders
+            rp = bc.SC_ROWS_PER_PASS[64]
+            for f, l in ((rp - 1, rp), (bc.SC_TM - 1, bc.SC_TM)):
+                assert (f, l) in pairs and (l, f) in pairs, (nt, f, l)
+            assert any(rp <= r % bc.SC_TM for p in pairs for r in p)
+            if nt > 129 and nt % bc.SC_TM >= 2:                                                # a pair inside the last, partial tile
+                last0 = nt // bc.SC_TM * bc.SC_TM
+                inside = [p for p in pairs if min(p) >= last0 and (s >= nt or min(p) > s)]
+                assert inside and all(max(p) < nt for p in inside), (nt, pairs)
+            if nt == 8191:
+                assert (8064, 8064 + 63) in pairs                                              # the last row of the first piece, in a partial tile
         if nt <= 8193:
             bc.accept_case(_reference_keys(case), case)
     for nq in bc.SCREEN_NQ:
-        case = bc.screen_case(nq, 300)
+        case = bc.screen_case(nq, 300, dim)
         assert {0, nq - 1} <= set(case["planted_q"].tolist())
         assert any((nq + d) % 48 == 0 for d in (-1, 0, 1))             # a wave's 48 queries; 384 = a block's
+        if dim == 64:
+            pairs = [p[1:] for p in case["planted"]]
+            assert {(63, 64), (64, 63), (127, 128), (128, 127), (256, 277), (277, 256), (298, 299), (0, 255)} <= set(pairs)
+    if dim == 128:                                                     # the cases of the existing GPU tests are the default arguments
+        for a, b in ((bc.screen_case(47, 300), bc.screen_case(47, 300, 128)), (bc.adversarial_case(), bc.adversarial_case(128)), (bc.equal_case(4), bc.equal_case(4, 128))):
+            assert np.array_equal(a["q"], b["q"]) and np.array_equal(a["t"], b["t"])
 
 
-def test_adversarial_case_inverts_the_screen_order():
-    case = bc.adversarial_case()
+@pytest.mark.parametrize("dim", bc.SC_DIMS)
+def test_adversarial_case_inverts_the_screen_order(dim):
+    """Measured share of the 2 eps margin that the true second neighbour uses: 0.067 at dim 128, 0.045 at dim 64."""
+    case = bc.adversarial_case(dim)
     q, t = case["q"], case["t"]
+    assert q.shape[1] == t.shape[1] == dim
     for x in (q, t):
         m = (x.astype(np.float64) / float(bc.BESIDE_MIDPOINT)).astype(np.float32)
         assert np.array_equal(m.astype(np.float64) * float(bc.BESIDE_MIDPOINT), x.astype(np.float64))      # x = m (1 + 2^-9) exactly ...
         assert np.array_equal(bc.bf16_round(m), m) and np.array_equal(bc.bf16_round(x), m)                 # ... m is bf16, and x rounds to it
     D, S = bc.d2_64(q, t), bc.screen_values(q, t)
-    ahead = []
+    eps = bc.screen_eps(q, t)
+    assert bc.screen_sample_rows(len(t)) == len(t)                                                         # the sample is the whole set here
+    ahead, share = [], []
     for qi, r0, r1, rivals in case["adv"]:
         order = np.argsort(D[qi], kind="stable")
         assert tuple(order[:2]) == (r0, r1) and D[qi, order[2]] - D[qi, r1] > 4 * bc.bound(q[[qi]], t).max()   # the true top-2, decided
         assert (D[qi, rivals] > D[qi, r1]).all() and (S[qi, rivals] < S[qi, r0]).all()                           # truly farther, screened nearer
         assert abs(float(q[qi].astype(np.float64) @ t[rivals[0]].astype(np.float64))) < 1e-9
         ahead.append(int((S[qi] < S[qi, r0]).sum()))
+        # what gives the case its power: the true second neighbour is a candidate only through the margin of screen_theta_kernel
+        s2 = np.sort(S[qi])[1]
+        assert s2 < S[qi, r1] < s2 + 2.0 * eps[qi], (qi, s2, S[qi, r1], eps[qi])
+        share.append((S[qi, r1] - s2) / (2.0 * eps[qi]))
     assert min(ahead) >= 2 * bc.ADV_RIVALS
+    print(f"dim {dim}: {min(ahead)} rows screen ahead of t0; the true second neighbour uses {min(share):.4f} .. {max(share):.4f} of the 2 eps margin")
+
+
+def test_screen_emulation_passes_and_three_mistakes_do_not():
+    """The checks of test_l2_train_borders_gpu.py on emulated keys: a correct screen in numpy is accepted at both lengths; without eps, with
+    the whole set's second screen value as the threshold, or without rows 64..127 of every tile among the candidates it is rejected."""
+    def judge(case, keys):
+        if "adv" in case:
+            _, rows = bc.split_keys(keys)
+            for qi, r0, r1, rivals in case["adv"]:
+                assert tuple(rows[qi]) == (r0, r1), (qi, rows[qi], r0, r1)
+            bc.check(keys, case["q"], case["t"], 0, 2)
+        else:
+            bc.accept_case(keys, case)
+
+    def rejected(case, F, **mistake):
+        with pytest.raises(AssertionError):
+            judge(case, bc.emulate_screen(case["q"], case["t"], exact=F, **mistake)[0])
+
+    for dim in bc.SC_DIMS:
+        adv, tile, border = bc.adversarial_case(dim), bc.screen_case(49, 300, dim), bc.screen_case(100, 8193, dim)
+        F = {id(c): bc.emulate_matrix(c["q"], c["t"]) for c in (adv, tile, border)}
+        for c in (adv, tile, border):
+            keys, cpq = bc.emulate_screen(c["q"], c["t"], exact=F[id(c)])
+            judge(c, keys)
+            assert np.array_equal(keys, bc.topk_keys(F[id(c)], 2))                              # the screen loses nothing of the exact top-2
+            print(f"dim {dim}, {len(c['q'])} x {len(c['t'])}: {cpq:.1f} candidates per query in the emulation")
+        rejected(adv, F[id(adv)], eps_scale=0.0)
+        rejected(adv, F[id(adv)], whole_set_s2=True)
+        for c in (tile, border):
+            rejected(c, F[id(c)], drop_second_piece=True)

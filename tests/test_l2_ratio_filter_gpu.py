@@ -3,7 +3,9 @@ query order, train index, distance = sqrtf(d^2) bit for bit, kept iff d0 < d1 * 
 
 nq in 1, 1023, 1024, 1025 (SCAN_BLOCK = 1024 queries per block of the ordered compaction); a train set of exactly two rows; one of a
 single row (every second key empty: no matches, where the host front raises for want of a second neighbour); a planted exact tie
-d0 == d1 * fs (duplicate rows, fs = 1.0: dropped, the test is strict); fs = 0 and fs above 1."""
+d0 == d1 * fs (duplicate rows, fs = 1.0: dropped, the test is strict); fs = 0 and fs above 1.
+test_keys_built_by_hand needs no matcher: d^2 bit patterns a matcher rarely produces (zero, subnormal, beside perfect squares, the ends of
+the exponent range) with the second key placed beside d0 / fs^2, against the host rule restated in numpy."""
 import ctypes as C
 from importlib import import_module
 
@@ -95,6 +97,72 @@ def test_exact_tie_is_dropped(dev):
     above = dev.filtered(keys, 1.0000001)                               # the next f32 above 1: a non-zero tie passes (d1 * fs rounds above d1)
     assert k[10, 0] >> 32 != 0 and 10 in above["query_idx"]
     same_records(above, fe.get_knn_matches_l2(q, t, 2, 1.0000001))
+
+
+def hand_made_d2_bits():
+    """uint32 bit patterns of d^2: 0, the smallest and the largest subnormal, the smallest normal; n^2 and its binary32 neighbours for n in
+    1..64 (where a root that is one ulp off shows: the exact root is representable); 2^e and its neighbours for e = -126, -119 .. 126 (odd
+    and even exponents alternate); the largest finite value; 4096 random positive finite patterns"""
+    f = lambda x: int(np.float32(x).view(np.uint32))
+    bits = [0, 1, 0x007FFFFF, 0x00800000]
+    for n in range(1, 65):
+        bits += [f(n * n) - 1, f(n * n), f(n * n) + 1]
+    for e in range(-126, 127, 7):
+        b = f(2.0 ** e)
+        bits += [b - 1, b, b + 1] if e > -126 else [b, b + 1]          # (below 2^-126: the largest subnormal, listed above)
+    bits.append(0x7F7FFFFF)
+    bits += np.random.default_rng(0x4C32F0C0).integers(1, 0x7F800000, 4096).tolist()
+    return np.array(bits, np.uint32)
+
+
+@pytest.mark.parametrize("k", [2, 3])
+def test_keys_built_by_hand(dev, k):
+    """4097 queries per call; the key stride is k (the third key of k = 3 is never read). Expected: distance = the correctly rounded binary32
+    root of the key's d^2; kept iff both keys are present and root(d0) < float32(root(d1) * float32(fs)) - get_knn_matches_l2's rule."""
+    torch, NQ = dev.torch, 4097
+    d0 = hand_made_d2_bits()
+    root = lambda bits: np.sqrt(bits.view(np.float32))
+    r64 = np.sqrt(d0.view(np.float32).astype(np.float64)).astype(np.float32)
+    assert np.array_equal(root(d0).view(np.uint32), r64.view(np.uint32))           # numpy's binary32 root is the float64 root rounded once
+    n = np.arange(1, 65)
+    assert np.array_equal(root((n * n).astype(np.float32).view(np.uint32)), n.astype(np.float32))
+    rng = np.random.default_rng(0x4C32F0C1 + k)
+    seen = {"kept": 0, "dropped": 0, "equal": 0, "subnormal_product": 0}
+    for fs in (0.5, 0.8, 1.0, 1.25, 2.0 ** -60):
+        fs32 = np.float32(fs)
+        with np.errstate(over="ignore"):
+            beside = np.minimum(d0.view(np.float32).astype(np.float64) / (float(fs32) * float(fs32)), float(np.finfo(np.float32).max)).astype(np.float32).view(np.uint32)
+        a = np.repeat(d0, 3).astype(np.int64)
+        b = np.clip(np.repeat(beside, 3).astype(np.int64) + np.tile(np.array([-1, 0, 1]), len(d0)), 0, 0x7F7FFFFF)
+        for start in range(0, len(a), NQ):
+            idx = np.arange(start, start + NQ) % len(a)                            # (the last batch wraps round to the first pairs)
+            keys = np.empty((NQ, k), np.uint64)
+            low = rng.integers(0, 1 << 32, (NQ, k), dtype=np.uint64)
+            keys[:, 0] = (a[idx].astype(np.uint64) << np.uint64(32)) | low[:, 0]
+            keys[:, 1] = (b[idx].astype(np.uint64) << np.uint64(32)) | low[:, 1]
+            if k == 3:
+                keys[:, 2] = rng.integers(0, 1 << 63, NQ, dtype=np.uint64)
+            keys[5::7, 1] = np.uint64(0xFFFFFFFFFFFFFFFF)                          # no second neighbour
+            keys[11::97, :2] = np.uint64(0xFFFFFFFFFFFFFFFF)                       # no neighbour at all
+            present = (keys[:, 0] != np.uint64(0xFFFFFFFFFFFFFFFF)) & (keys[:, 1] != np.uint64(0xFFFFFFFFFFFFFFFF))
+            r0 = root((keys[:, 0] >> np.uint64(32)).astype(np.uint32))
+            with np.errstate(invalid="ignore"):
+                r1 = root((keys[:, 1] >> np.uint64(32)).astype(np.uint32))         # (nan where the key is empty: not present)
+                product = (r1.astype(np.float64) * float(fs32)).astype(np.float32)  # exact in binary64, rounded once: the binary32 product, subnormal results included
+                keep = present & (r0 < product)
+            want = np.zeros(int(keep.sum()), dev.pkg._lib.DMATCH_DTYPE)
+            want["query_idx"] = np.flatnonzero(keep)
+            want["train_idx"] = (keys[keep, 0] & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32)
+            want["distance"] = r0[keep]
+            dk = torch.from_numpy(keys.view(np.int64)).to("cuda:0")
+            torch.cuda.synchronize()
+            same_records(dev.filtered(dk, fs), want)
+            seen["kept"] += int(keep.sum())
+            seen["dropped"] += int((present & ~keep).sum())
+            seen["equal"] += int((present & (r0 == product)).sum())
+            seen["subnormal_product"] += int((present & (product > 0) & (product < np.finfo(np.float32).tiny)).sum())
+    print(f"k = {k}: {seen}")
+    assert min(seen.values()) > 0, seen                                           # both sides of the test, exact equality, a subnormal product
 
 
 def test_contract(dev):

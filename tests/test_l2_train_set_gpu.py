@@ -3,10 +3,12 @@ apds_dev_l2_topk(k = 2) on the same rows, np.array_equal, at dim 64 (the M-SURF 
 thread) and dim 128.
 
 Sizes: nt in 2, 127, 128, 129 (the 128-row tile), 8191, 8192, 8193 (the sample floor) and 20001 (more than one split: 157 tiles over the
-512-block target); nq in 1, 15, 16, 17 (a 16-query column block) and Q - 1, Q, Q + 1 for both block widths the dim-64 kernel is built
-with (Q = 384, three column blocks per wave, and Q = 512, four). With at most 20001 rows a block of pass B sees at most 128 rows, fewer
-than the 192 candidates per query its region holds: the candidate buffer cannot overflow here, so the screen must have run wherever the
-handle is screen_ready and the query pointer aligned."""
+512-block target); nq in 1, 15, 16, 17 (a 16-query column block), 383, 384, 385 (Q = 384 queries per block at both lengths: three column
+blocks per wave) and 511, 512, 513 (a block and a third; the sizes of a four-block build, Q = 512, that was measured, found slower and
+removed: kept as sizes). With at most 20001 rows a block of pass B sees at most 128 rows, fewer than the 192 candidates per query its
+region holds: the candidate buffer cannot overflow here, so the screen must have run wherever the handle is screen_ready and the query
+pointer aligned. The structural borders of the screen (sample, staged pieces, adversarial rounding, overflow, index bases) are in
+test_l2_train_borders_gpu.py."""
 import ctypes as C
 import gc
 from importlib import import_module
