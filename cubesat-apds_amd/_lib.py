@@ -57,6 +57,8 @@ SYMBOLS = [
     "apds_dev_akaze_describe_float",
     "apds_l2_train_create", "apds_l2_train_destroy", "apds_l2_train_info", "apds_dev_l2_train_top2", "apds_dev_l2_ratio_filter", "apds_pipeline_create_float",
     "apds_workspace_info",
+    "apds_db_create_float", "apds_db_info", "apds_db_insert_image_float", "apds_db_view_download_float", "apds_db_read_keypoint_from_id_float",
+    "apds_db_view_l2_train", "apds_db_l2_knn_match",
 ]
 
 RESAMPLE_NEAREST, RESAMPLE_LANCZOS = 0, 1
@@ -335,6 +337,13 @@ def lib():
             "apds_dev_akaze_extract_float": (i, [vp, i, i, i, sz, vp, sz, i, i, vp, vp, i, ip, vp]),
             "apds_dev_akaze_extract_float_batch": (i, [vp, i, sz, i, i, i, sz, vp, sz, sz, i, i, vp, vp, i, ip, vp]),
             "apds_dev_akaze_describe_float": (i, [vp, i, i, vp, i, vp, vp]),
+            "apds_db_create_float": (i, [pp, i64]),
+            "apds_db_info": (i, [vp, ip, ip]),
+            "apds_db_insert_image_float": (i, [vp, vp, vp, i, i, i, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
+            "apds_db_view_download_float": (i, [vp, vp, vp, vp, vp]),
+            "apds_db_read_keypoint_from_id_float": (i, [vp, i, vp, vp, ip, C.POINTER(i64)]),
+            "apds_db_view_l2_train": (i, [vp, pp]),
+            "apds_db_l2_knn_match": (i, [vp, vp, i, i, vp, vp]),
         }
         for name, (rt, at) in sig.items():
             fn = getattr(L, name)

@@ -321,7 +321,7 @@ int apds_mosaic_tile_extract(void* mosaic, int x0, int y0, int win_w, int win_h,
 
 // The front of the two calls below: the checks of the batch call, then window read -> band_merger -> batched extraction of n_tiles windows
 // of the resident mosaic on the calling thread's stream, in its (reset) workspace. counts[] is final on return; the rows stay on the device
-// (tile i at i * capacity rows) with the descriptor kernels still queued on `s`.
+// (tile i at i * capacity rows; 64-byte rows, or rows of 64 floats with APDS_AKAZE_DESCRIPTOR_KAZE) with the descriptor kernels still queued on `s`.
 struct MosaicBatchRows {
     apds_keypoint* kps;
     uint8_t* desc64;
@@ -329,7 +329,8 @@ struct MosaicBatchRows {
     hipStream_t s;
 };
 static MosaicBatchRows mosaic_tiles_extract_device(ThreadCtx& c, Mosaic* m, const int32_t* xy0, int n_tiles, int win_w, int win_h, int out_w, int out_h, int resample,
-                                                   const double* minmax6, int max_points, int mask_mode, int* counts) {
+                                                   const double* minmax6, int max_points, int mask_mode, int* counts,
+                                                   int descriptor = APDS_AKAZE_DESCRIPTOR_MLDB) {
     check_mask_mode(mask_mode);
     mosaic_check_window(m, 0, xy0, n_tiles, win_w, win_h, out_w, out_h, resample);
     if (max_points <= 0) max_points = APDS_MAX_POINTS;
@@ -346,11 +347,11 @@ static MosaicBatchRows mosaic_tiles_extract_device(ThreadCtx& c, Mosaic* m, cons
     uint8_t* dimg = c.alloc_n<uint8_t>(all * 4);
     const int capacity = batch_capacity(out_h, out_w, max_points);
     apds_keypoint* dk = c.alloc_n<apds_keypoint>((size_t)capacity * n_tiles);
-    uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * 64 * n_tiles);
+    uint8_t* dd = c.alloc_n<uint8_t>((size_t)capacity * device_row_bytes(descriptor) * n_tiles);
     mosaic_read_device(m, xy0, n_tiles, win_w, win_h, out_w, out_h, resample, bands, s);
     band_merger_device(bands, bands + all, bands + 2 * all, all, minmax6, /*bgra=*/1, dimg, s);
     akaze_extract_batch_device(dimg, n_tiles, px * 4, out_h, out_w, 4, (size_t)out_w * 4, tile_mask(mask_mode, dimg, out_h, out_w), tile_mask_support(mask_mode),
-                               max_points, dk, dd, capacity, counts, s);
+                               max_points, dk, dd, capacity, counts, s, descriptor);
     return MosaicBatchRows{dk, dd, capacity, s};
 }
 
@@ -383,7 +384,9 @@ int apds_mosaic_tiles_to_db(void* mosaic, void* db, const int32_t* xy0, int n_ti
         Mosaic* m = static_cast<Mosaic*>(mosaic);
         APDS_REQUIRE(mosaic_device(m) == table_device(db), APDS_ERR_BAD_ARG, "the mosaic and the keypoint table live on different devices");
         ThreadCtx& c = ctx();
-        const MosaicBatchRows r = mosaic_tiles_extract_device(c, m, xy0, n_tiles, win_w, win_h, out_w, out_h, resample, minmax6, max_points, mask_mode, counts);
+        // (the rows are of the table's kind: a float table gets the M-SURF extraction of the same keypoints)
+        const MosaicBatchRows r = mosaic_tiles_extract_device(c, m, xy0, n_tiles, win_w, win_h, out_w, out_h, resample, minmax6, max_points, mask_mode, counts,
+                                                              table_descriptor(db));
         table_insert_batch_device(db, r.kps, r.desc64, n_tiles, r.capacity, counts, first_image_id, level_of_detail, columns_rows, (uint64_t)out_w, (uint64_t)out_h,
                                   r.s);
     });

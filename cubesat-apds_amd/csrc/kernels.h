@@ -103,6 +103,7 @@ void undistort_image_device(const uint8_t* src, int rows, int cols, int channels
 // tile order by one launch on s (checks first, then writes; takes its small tile table from the calling thread's workspace WITHOUT
 // resetting it; synchronises s)
 int table_device(const void* db);
+int table_descriptor(const void* db);   // APDS_AKAZE_DESCRIPTOR_MLDB (64-byte rows) or APDS_AKAZE_DESCRIPTOR_KAZE (rows of 64 floats): the rows the inserts take
 void table_insert_batch_device(void* db, const void* kps_dev, const void* desc64_dev, int n_tiles, int capacity, const int32_t* counts, int first_image_id,
                                int lod, const uint32_t* columns_rows, uint64_t tile_w, uint64_t tile_h, hipStream_t s);
 
@@ -137,6 +138,7 @@ struct L2Train {
     float* norms = nullptr;          // n floats: row_norms_kernel's values
     uint16_t* rows_bf = nullptr;     // n x dim bf16 of -2 * row (screen_ready)
     unsigned int* tmax_bits = nullptr;   // bits of the largest |t|^2 (screen_ready)
+    bool borrowed = false;               // a member of a table view (apds_db_view_l2_train): its buffers are the view's, apds_l2_train_destroy refuses it
 };
 L2Train* l2_train_create(const float* t, long long nt, int dim, uint32_t index_base, hipStream_t s);   // synchronises s
 void l2_train_destroy(L2Train* set);

@@ -35,22 +35,26 @@ __global__ __launch_bounds__(TB) void delete_count_kernel(TableColumns c, int n,
     if (f && pos == 0) atomicMin(first_row, (int)i);
 }
 
-static constexpr int DELETE_CHUNK_ROWS = 1 << 20;   // rows one gather / scatter pair moves: a multiple of TB
+// rows one gather / scatter pair moves, a multiple of TB: 2^20 of a byte table (128-byte staging rows), 2^18 of a float table (320-byte
+// staging rows), so the staging buffer of either stays near 128 MB
+static constexpr int DELETE_CHUNK_ROWS = 1 << 20, DELETE_CHUNK_ROWS_FLOAT = 1 << 18;
 static constexpr int MOVE_COLUMNS = 10;             // x, y, size, angle, response, octave, class_id, image_id, lod, id: one dword each
-static constexpr int STAGE_ROW_DWORDS = MOVE_COLUMNS + 16 + 6;   // + the descriptor row + the world point: 128 bytes
+// dwords of a staging row: the columns + the descriptor row (16 or 64 dwords) + the world point
+static constexpr int stage_row_dwords(int desc_dwords) { return MOVE_COLUMNS + desc_dwords + 6; }
 
 struct MoveColumns {
     uint32_t* col[MOVE_COLUMNS];
-    uint32_t* desc;   // 16 dwords per row
+    uint32_t* desc;   // 1 << desc_shift dwords per row
     uint32_t* xyz;    // 6 dwords per row, or null (no valid world points: nothing to move)
+    int desc_shift;   // 4 or 6: log2 of the dwords of a descriptor row
 };
-// the staging buffer: MOVE_COLUMNS planes of `rows` dwords, then rows x 16 descriptor dwords, then rows x 6 world point dwords
+// the staging buffer: MOVE_COLUMNS planes of `rows` dwords, then rows x desc_dwords descriptor dwords, then rows x 6 world point dwords
 struct StageColumns {
     uint32_t* base;
-    int rows;
+    int rows, desc_dwords;
     __device__ __forceinline__ uint32_t* col(int k) const { return base + (size_t)k * rows; }
     __device__ __forceinline__ uint32_t* desc() const { return base + (size_t)MOVE_COLUMNS * rows; }
-    __device__ __forceinline__ uint32_t* xyz() const { return base + (size_t)(MOVE_COLUMNS + 16) * rows; }
+    __device__ __forceinline__ uint32_t* xyz() const { return base + (size_t)(MOVE_COLUMNS + desc_dwords) * rows; }
 };
 
 // Chunk = blocks [block0, block0 + gridDim.x) of TB rows. Its survivors go to consecutive staging slots in row order: slot = survivors of
@@ -75,8 +79,9 @@ __global__ __launch_bounds__(TB) void delete_gather_kernel(MoveColumns m, int n,
         }
     }
     __syncthreads();
-    uint32_t* sd = st.desc() + before * 16;
-    for (int e = skip * 16 + threadIdx.x; e < total * 16; e += TB) sd[e] = m.desc[(size_t)(r0 + src_of[e >> 4]) * 16 + (e & 15)];
+    const int W = 1 << m.desc_shift;
+    uint32_t* sd = st.desc() + before * W;
+    for (int e = skip * W + threadIdx.x; e < total * W; e += TB) sd[e] = m.desc[(size_t)(r0 + src_of[e >> m.desc_shift]) * W + (e & (W - 1))];
     if (m.xyz) {
         uint32_t* sx = st.xyz() + before * 6;
         for (int e = skip * 6 + threadIdx.x; e < total * 6; e += TB) {
@@ -97,16 +102,16 @@ __global__ __launch_bounds__(256) void delete_scatter_kernel(StageColumns st, co
     const long long survivors = (end - start) - (victim_offsets[block_end] - victims_before);
     const long long dst0 = start - victims_before;
     const long long skip = std::max<long long>(first_row - dst0, 0);   // slots of rows that did not move (never staged)
-    const long long R = region_rows, g0 = (long long)blockIdx.x * 256;
-    if (g0 < R * 16) {
+    const long long R = region_rows, g0 = (long long)blockIdx.x * 256, W = 1 << m.desc_shift;
+    if (g0 < R * W) {
         const long long e = g0 + threadIdx.x;
-        if (e >= skip * 16 && e < survivors * 16) m.desc[dst0 * 16 + e] = st.desc()[e];
-    } else if (g0 < R * (16 + MOVE_COLUMNS)) {
-        const int k = (int)((g0 - R * 16) / R);
-        const long long j = g0 - R * (16 + k) + threadIdx.x;
+        if (e >= skip * W && e < survivors * W) m.desc[dst0 * W + e] = st.desc()[e];
+    } else if (g0 < R * (W + MOVE_COLUMNS)) {
+        const int k = (int)((g0 - R * W) / R);
+        const long long j = g0 - R * (W + k) + threadIdx.x;
         if (j >= skip && j < survivors) m.col[k][dst0 + j] = st.col(k)[j];
     } else {
-        const long long e = g0 - R * (16 + MOVE_COLUMNS) + threadIdx.x;
+        const long long e = g0 - R * (W + MOVE_COLUMNS) + threadIdx.x;
         if (e >= skip * 6 && e < survivors * 6) m.xyz[dst0 * 6 + e] = st.xyz()[e];
     }
 }
@@ -136,8 +141,8 @@ int64_t table_delete_rows(KeypointTable* t, ThreadCtx& c, const SelectArgs& a, u
     const bool xyz_valid = t->xyz && t->xyz_rows == t->n;
     if ((int64_t)first_row + m < n) {   // a survivor sits behind a victim: rows move (a deleted tail moves nothing)
         if (!t->stage) {
-            t->stage_rows = (int)std::min<int64_t>(DELETE_CHUNK_ROWS, (int64_t)ceil_div(t->capacity, TB) * TB);
-            dev_alloc(t->stage, (size_t)t->stage_rows * STAGE_ROW_DWORDS);
+            t->stage_rows = (int)std::min<int64_t>(t->is_float() ? DELETE_CHUNK_ROWS_FLOAT : DELETE_CHUNK_ROWS, (int64_t)ceil_div(t->capacity, TB) * TB);
+            dev_alloc(t->stage, (size_t)t->stage_rows * stage_row_dwords(t->row_dwords));
         }
         MoveColumns mv;
         uint32_t* const planes[MOVE_COLUMNS] = {reinterpret_cast<uint32_t*>(t->x), reinterpret_cast<uint32_t*>(t->y), reinterpret_cast<uint32_t*>(t->size),
@@ -147,8 +152,9 @@ int64_t table_delete_rows(KeypointTable* t, ThreadCtx& c, const SelectArgs& a, u
         for (int k = 0; k < MOVE_COLUMNS; k++) mv.col[k] = planes[k];
         mv.desc = reinterpret_cast<uint32_t*>(t->desc64);
         mv.xyz = xyz_valid ? reinterpret_cast<uint32_t*>(t->xyz) : nullptr;
-        const StageColumns st{t->stage, t->stage_rows};
-        const int chunk_blocks = t->stage_rows / TB, segments = xyz_valid ? STAGE_ROW_DWORDS : STAGE_ROW_DWORDS - 6;
+        mv.desc_shift = cols.row_shift;
+        const StageColumns st{t->stage, t->stage_rows, t->row_dwords};
+        const int chunk_blocks = t->stage_rows / TB, segments = stage_row_dwords(t->row_dwords) - (xyz_valid ? 0 : 6);
         for (int b0 = first_row / TB; b0 < nb; b0 += chunk_blocks) {
             const int b1 = std::min(b0 + chunk_blocks, nb), region_rows = (b1 - b0) * TB;
             hipLaunchKernelGGL(delete_gather_kernel, dim3(b1 - b0), dim3(TB), 0, s, mv, n, (const uint8_t*)flags, (const int*)counts, b0, first_row, st);

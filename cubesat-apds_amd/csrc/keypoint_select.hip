@@ -5,9 +5,12 @@
 // row gather. Ties in response are ordered by insertion order (row), which SQL leaves unspecified. Two fronts hand it their buffers:
 // apds_db_select (the table's current view, scratch from the thread's workspace, synchronised) and apds_db_view_select (a view object
 // that owns outputs and scratch, on the caller's stream). A selection is directly usable as a train set: 64-byte descriptor rows, and
-// `train_idx` = position in the selection (the index the reference would get from the returned Vec).
+// `train_idx` = position in the selection (the index the reference would get from the returned Vec). On a float table the rows are 64
+// floats, and a view object's gather also writes the L2 screen's train side of the selection (apds_db_view_l2_train).
+#include <cstring>
 #include <vector>
 
+#include "bf16_round.h"
 #include "keypoint_table.h"
 #include "topk_keys.h"
 
@@ -190,17 +193,45 @@ __global__ __launch_bounds__(256) void select_merge_step_kernel(uint64_t* __rest
     }
 }
 
-// everything a selection holds, in one launch: 16 lanes per row, one descriptor dword each; lane 0 also writes the keypoint, row id and
-// image id, lanes 1..3 one coordinate of the world point each when xyz is asked for
+// the train side of an L2 screen over a selection of float rows (kernels.h: L2Train), written by the gather; all null on a byte table
+struct TrainSideOut {
+    float* norms;              // |row|^2, row_norms_kernel's value bit for bit
+    uint16_t* rows_bf;         // bf16 of -2 * row, 64 per row
+    unsigned int* tmax_bits;   // bits of the largest norm: cleared on the stream in front of the launch
+};
+
+// everything a selection holds, in one launch: a lane per dword of a descriptor row (16 lanes per row of a byte table, one whole wave per
+// row of a float table: the row is read as one coalesced 256 bytes); lane 0 also writes the keypoint, row id and image id, lanes 1..3 one
+// coordinate of the world point each when xyz is asked for.
+// A float view (ts.norms != null; a wave per row) also gets its train side here, from the row it holds in registers: the norm is
+// row_norms_kernel's at dim 64 - one element per lane squared (its `0 + v * v` is v * v), then the same xor butterfly 32, 16, .., 1 -
+// the bf16 value is to_bf16_rows_kernel's at scale -2, and the largest norm max_norm_kernel's (fmaxf from 0 drops a NaN norm as it does).
 __global__ __launch_bounds__(256) void select_gather_kernel(const uint64_t* __restrict__ keys, int m, TableColumns c, const double* __restrict__ xyz,
                                                             int* __restrict__ rows, apds_keypoint* __restrict__ kps, int* __restrict__ out_img,
-                                                            uint32_t* __restrict__ out_desc, double* __restrict__ out_xyz) {
+                                                            uint32_t* __restrict__ out_desc, double* __restrict__ out_xyz, TrainSideOut ts) {
     APDS_RAISE_WAVE_PRIORITY();
+    const int W = c.row_dwords();
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= (long long)m * 16) return;
-    const int i = (int)(t >> 4), w = (int)(t & 15);
+    if (t >= (long long)m * W) return;   // (a float row: the whole wave leaves together)
+    const int i = (int)(t >> c.row_shift), w = (int)(t & (W - 1));
     const uint32_t r = (uint32_t)keys[i];
-    out_desc[(size_t)i * 16 + w] = c.desc64[(size_t)r * 16 + w];
+    const uint32_t bits = c.desc64[(size_t)r * W + w];
+    out_desc[(size_t)i * W + w] = bits;
+    if (ts.norms) {
+        const float v = __uint_as_float(bits);
+        float s = v * v;
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        const uint32_t h = f32_to_bf16_rne(v * -2.0f);
+        const uint32_t up = (uint32_t)__shfl_down((int)h, 1);
+        if ((w & 1) == 0) reinterpret_cast<uint32_t*>(ts.rows_bf)[((size_t)i * 64 + w) >> 1] = h | (up << 16);
+        if (w == 0) {
+            ts.norms[i] = s;
+            // non-negative floats order like their bits. The value only grows, so a row that a relaxed read shows to be no larger has
+            // nothing to add: all but a few of a large selection's rows skip the atomic on the one shared word.
+            const unsigned int nb = __float_as_uint(fmaxf(0.f, s));
+            if (nb > __atomic_load_n(ts.tmax_bits, __ATOMIC_RELAXED)) atomicMax(ts.tmax_bits, nb);
+        }
+    }
     if (w == 0) {
         rows[i] = (int)r;
         kps[i] = load_keypoint(c, r);
@@ -226,8 +257,9 @@ struct SelectScratch {
 struct SelectOutputs {
     int *rows = nullptr, *image_id = nullptr;
     apds_keypoint* kps = nullptr;
-    uint8_t* desc64 = nullptr;   // 64-byte rows
+    uint8_t* desc64 = nullptr;   // rows of the table's kind: 64 bytes, or 64 floats
     double* xyz = nullptr;       // null: the world points are not gathered
+    TrainSideOut train{nullptr, nullptr, nullptr};   // a float view's L2 train side; all null: not written
 };
 
 // keys the sort buffer of a selection of at most m rows holds: the power of two that holds them, at least one LDS block
@@ -275,8 +307,10 @@ static int select_rows(KeypointTable* t, const SelectArgs& a, int limit, hipStre
             hipLaunchKernelGGL(select_merge_step_kernel, dim3(p2 / 2 / 256), dim3(256), 0, s, w.sorted, p2 / 2, k, j);
         hipLaunchKernelGGL(select_merge_tail_kernel, dim3(p2 / SORT_B), dim3(SORT_B / 2), 0, s, w.sorted, k);
     }
-    hipLaunchKernelGGL(select_gather_kernel, dim3(ceil_div((long long)m * 16, 256)), dim3(256), 0, s, (const uint64_t*)w.sorted, m, c,
-                       (const double*)(o.xyz ? t->xyz : nullptr), o.rows, o.kps, o.image_id, reinterpret_cast<uint32_t*>(o.desc64), o.xyz);
+    if (o.train.norms) HIP_CHECK(hipMemsetAsync(o.train.tmax_bits, 0, 16, s));
+    KernelTimer timer("db_select_gather", s);   // (apds_dev_last_kernel_ms; free unless timing is on)
+    hipLaunchKernelGGL(select_gather_kernel, dim3(ceil_div((long long)m * t->row_dwords, 256)), dim3(256), 0, s, (const uint64_t*)w.sorted, m, c,
+                       (const double*)(o.xyz ? t->xyz : nullptr), o.rows, o.kps, o.image_id, reinterpret_cast<uint32_t*>(o.desc64), o.xyz, o.train);
     HIP_CHECK(hipGetLastError());
     return m;
 }
@@ -289,6 +323,9 @@ struct TableView {
     bool has_xyz = false;
     SelectScratch scratch;   // host_count: pinned
     SelectOutputs out;       // xyz always allocated; a selection without world points does not write it
+    // a float table's view: the train side of the current selection as the handle apds_dev_l2_train_top2 takes (apds_db_view_l2_train).
+    // rows = out.desc64 and the three buffers of out.train, all allocated at create for `limit` rows; n and screen_ready follow each select.
+    L2Train train;
 };
 
 }  // namespace apds
@@ -300,7 +337,7 @@ void view_free(TableView* v) {
     const SelectScratch& w = v->scratch;
     const SelectOutputs& o = v->out;
     for (void* p : {(void*)w.block_counts, (void*)w.cut_counts, (void*)w.keys, (void*)w.sorted, (void*)w.state, (void*)o.rows, (void*)o.image_id,
-                    (void*)o.kps, (void*)o.desc64, (void*)o.xyz})
+                    (void*)o.kps, (void*)o.desc64, (void*)o.xyz, (void*)o.train.norms, (void*)o.train.rows_bf, (void*)o.train.tmax_bits})
         if (p) (void)hipFree(p);
     if (w.host_count) (void)hipHostFree(w.host_count);
     delete v;
@@ -332,7 +369,7 @@ int apds_db_select(void* db, int mode, int value, float x_start, float y_start, 
         w.cut_counts = c.alloc_n<int>(nblocks);
         w.host_count = &count;
         const int m = select_rows(t, select_args(mode, value, x_start, y_start, x_end, y_end), limit, s, w,
-                                  SelectOutputs{t->view_rows, t->view_image_id, t->view_kps, t->view_desc64, nullptr});
+                                  SelectOutputs{t->view_rows, t->view_image_id, t->view_kps, t->view_desc64, nullptr, {}});
         if (!m) return;
         HIP_CHECK(hipStreamSynchronize(s));
         t->view_n = m;
@@ -358,6 +395,7 @@ int apds_db_knn_match(void* db, const uint8_t* query_desc, int n_query, int desc
     return guarded([&] {
         KeypointTable* t = static_cast<KeypointTable*>(db);
         APDS_REQUIRE(t && idx && dist && n_query >= 0, APDS_ERR_BAD_ARG, "bad argument");
+        require_table_kind(t, false);
         APDS_REQUIRE(desc_bytes >= 1 && desc_bytes <= 64, APDS_ERR_ASSERT, "descriptor length must be 1..64 bytes");
         APDS_REQUIRE(k >= 1, APDS_ERR_ASSERT, "k >= 1");   // (any k apds_dev_hamming_topk serves: the keys come from the same scan)
         if (!n_query) return;
@@ -380,12 +418,50 @@ int apds_db_knn_match(void* db, const uint8_t* query_desc, int n_query, int desc
     });
 }
 
-// host copy of the current view: what the reference's Vec<models::Keypoint> holds (id: the table's id column, a SERIAL column's values:
-// row + 1 on a table that never saw a delete)
-int apds_db_view_download(void* db, apds_keypoint* kps, uint8_t* desc61, int32_t* ids, int32_t* image_ids) {
+// apds_l2_knn_match of host query rows (64 floats each) against the CURRENT VIEW of a float table: the exact kernel over the view's rows
+int apds_db_l2_knn_match(void* db, const float* query, int n_query, int k, int32_t* idx, float* dist) {
+    return guarded([&] {
+        KeypointTable* t = static_cast<KeypointTable*>(db);
+        APDS_REQUIRE(t && idx && dist && n_query >= 0 && (query || !n_query), APDS_ERR_BAD_ARG, "bad argument");
+        require_table_kind(t, true);
+        APDS_REQUIRE(k >= 1, APDS_ERR_ASSERT, "bad sizes");
+        APDS_REQUIRE(k <= 2, APDS_ERR_ASSERT, "k > 2 is not implemented");
+        if (!n_query) return;
+        if (!t->view_n) {
+            for (long long i = 0; i < (long long)n_query * k; i++) idx[i] = -1, dist[i] = INFINITY;
+            return;
+        }
+        ThreadCtx& c = ctx();
+        require_table_device(t);
+        c.ws_reset();
+        hipStream_t s = c.stream;
+        float* dq = c.alloc_n<float>((size_t)n_query * APDS_DESC_FLOAT_DIM);
+        uint64_t* keys = c.alloc_n<uint64_t>((size_t)n_query * k);
+        HIP_CHECK(hipMemcpyAsync(dq, query, (size_t)n_query * APDS_DESC_FLOAT_DIM * sizeof(float), hipMemcpyHostToDevice, s));
+        l2_topk_device(dq, n_query, reinterpret_cast<const float*>(t->view_desc64), t->view_n, APDS_DESC_FLOAT_DIM, 0, k, keys, s);
+        std::vector<uint64_t> h((size_t)n_query * k);
+        HIP_CHECK(hipMemcpyAsync(h.data(), keys, h.size() * 8, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        for (size_t i = 0; i < h.size(); i++) {
+            if (h[i] == EMPTY_KEY) idx[i] = -1, dist[i] = INFINITY;
+            else {
+                const uint32_t d2_bits = (uint32_t)(h[i] >> 32);
+                float d2;
+                memcpy(&d2, &d2_bits, sizeof(d2));
+                idx[i] = (int32_t)(uint32_t)h[i];
+                dist[i] = sqrtf(d2);   // BFMatcher(NORM_L2) reports the distance, not its square
+            }
+        }
+    });
+}
+
+namespace {
+// both downloads of the current view: desc receives host_row bytes of every row (61 of a byte row, 256 of a float row)
+int view_download(void* db, bool want_float, apds_keypoint* kps, void* desc, int32_t* ids, int32_t* image_ids) {
     return guarded([&] {
         KeypointTable* t = static_cast<KeypointTable*>(db);
         APDS_REQUIRE(t, APDS_ERR_BAD_ARG, "null table");
+        require_table_kind(t, want_float);
         const int m = (int)t->view_n;
         if (!m) return;
         ThreadCtx& c = ctx();
@@ -399,13 +475,26 @@ int apds_db_view_download(void* db, apds_keypoint* kps, uint8_t* desc61, int32_t
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipMemcpyAsync(ids, view_ids, (size_t)m * 4, hipMemcpyDeviceToHost, s));
         }
-        if (desc61) {
+        if (desc && want_float) {
+            HIP_CHECK(hipMemcpyAsync(desc, t->view_desc64, (size_t)m * t->row_bytes(), hipMemcpyDeviceToHost, s));
+        } else if (desc) {
             uint8_t* d61 = c.alloc_n<uint8_t>((size_t)m * 61);
             HIP_CHECK(hipMemcpy2DAsync(d61, 61, t->view_desc64, 64, 61, m, hipMemcpyDeviceToDevice, s));
-            HIP_CHECK(hipMemcpyAsync(desc61, d61, (size_t)m * 61, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(desc, d61, (size_t)m * 61, hipMemcpyDeviceToHost, s));
         }
         HIP_CHECK(hipStreamSynchronize(s));
     });
+}
+}  // namespace
+
+// host copy of the current view: what the reference's Vec<models::Keypoint> holds (id: the table's id column, a SERIAL column's values:
+// row + 1 on a table that never saw a delete)
+int apds_db_view_download(void* db, apds_keypoint* kps, uint8_t* desc61, int32_t* ids, int32_t* image_ids) {
+    return view_download(db, false, kps, desc61, ids, image_ids);
+}
+
+int apds_db_view_download_float(void* db, apds_keypoint* kps, float* desc64f, int32_t* ids, int32_t* image_ids) {
+    return view_download(db, true, kps, desc64f, ids, image_ids);
 }
 
 // ---- view objects: keypointdb.rs:50-90 once per frame, on the caller's stream ------------------------------------------------------
@@ -417,6 +506,7 @@ int apds_db_view_create(void* db, int capacity, void** view) {
         require_table_device(t);
         TableView* v = new TableView();
         v->t = t;
+        v->train.borrowed = true;
         v->limit = (int)(capacity <= 0 ? std::min<int64_t>(APDS_MAX_POINTS, t->capacity) : std::min<int64_t>(capacity, APDS_MAX_POINTS));
         const size_t nblocks = (size_t)ceil_div(t->capacity, TB) + 1, lim = (size_t)v->limit;
         SelectScratch& w = v->scratch;
@@ -425,7 +515,16 @@ int apds_db_view_create(void* db, int capacity, void** view) {
             dev_alloc(w.block_counts, nblocks); dev_alloc(w.cut_counts, nblocks);
             dev_alloc(w.keys, (size_t)t->capacity); dev_alloc(w.sorted, (size_t)sort_capacity(v->limit));
             dev_alloc(w.state, 1);
-            dev_alloc(o.rows, lim); dev_alloc(o.image_id, lim); dev_alloc(o.kps, lim); dev_alloc(o.desc64, lim * 64); dev_alloc(o.xyz, lim * 3);
+            dev_alloc(o.rows, lim); dev_alloc(o.image_id, lim); dev_alloc(o.kps, lim); dev_alloc(o.desc64, lim * t->row_bytes()); dev_alloc(o.xyz, lim * 3);
+            if (t->is_float()) {
+                dev_alloc(o.train.norms, lim); dev_alloc(o.train.rows_bf, lim * APDS_DESC_FLOAT_DIM); dev_alloc(o.train.tmax_bits, 4);
+                v->train.device = t->device;
+                v->train.rows = reinterpret_cast<const float*>(o.desc64);
+                v->train.dim = APDS_DESC_FLOAT_DIM;
+                v->train.norms = o.train.norms;
+                v->train.rows_bf = o.train.rows_bf;
+                v->train.tmax_bits = o.train.tmax_bits;
+            }
             HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&w.host_count), sizeof(int), hipHostMallocDefault));
         } catch (...) {
             view_free(v);
@@ -456,10 +555,14 @@ int apds_db_view_select(void* view, int mode, int value, float x_start, float y_
         hipStream_t s = pick_stream(stream);
         v->n = 0;
         v->has_xyz = false;
+        v->train.n = 0;
+        v->train.screen_ready = false;
         SelectOutputs o = v->out;
         if (!with_xyz) o.xyz = nullptr;
         const int m = select_rows(t, select_args(mode, value, x_start, y_start, x_end, y_end), v->limit, s, v->scratch, o);
         v->n = m;
+        v->train.n = m;
+        v->train.screen_ready = t->is_float() && m >= 2;   // (what l2_train_create asks of a handle: dim 64, rows from hipMalloc, two rows)
         v->has_xyz = m && with_xyz;
         *n_out = m;
     });
@@ -476,6 +579,18 @@ int apds_db_view_pointers(const void* view, void** rows64_dev, void** kps_dev, v
         if (image_ids_dev) *image_ids_dev = v->out.image_id;
         if (xyz_dev) *xyz_dev = v->has_xyz ? v->out.xyz : nullptr;
         if (n) *n = v->n;
+    });
+}
+
+// The train side of a float view's current selection as an L2 train set: borrowed (never apds_l2_train_destroy), valid until the view is
+// destroyed, contents those of the last select once its stream has run. Index base 0: a key's row is the position in the view.
+int apds_db_view_l2_train(void* view, void** set) {
+    return guarded([&] {
+        TableView* v = static_cast<TableView*>(view);
+        APDS_REQUIRE(v && set, APDS_ERR_BAD_ARG, "null argument");
+        *set = nullptr;
+        require_table_kind(v->t, true);
+        *set = &v->train;
     });
 }
 

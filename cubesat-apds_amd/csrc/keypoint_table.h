@@ -16,6 +16,9 @@ struct KeypointTable {
     int64_t capacity = 0, n = 0;
     float *x = nullptr, *y = nullptr, *size = nullptr, *angle = nullptr, *response = nullptr;
     int *octave = nullptr, *class_id = nullptr, *image_id = nullptr, *lod = nullptr;
+    // the descriptor column: rows of row_dwords dwords, 16 (M-LDB, 64 bytes) or 64 (M-SURF, 64 x f32 = 256 bytes). The kind is fixed at
+    // create (apds_db_create / apds_db_create_float); every kernel that touches a descriptor row receives the width with the columns.
+    int row_dwords = 16;
     uint8_t* desc64 = nullptr;
     // the reference's SERIAL column: the id of every row, and the next id to give. Ids are never reused, so they ascend with the row.
     int* id = nullptr;
@@ -35,6 +38,9 @@ struct KeypointTable {
     // staging buffer of a delete's compaction (one chunk of rows, every moved column), allocated on the first delete that moves a row
     uint32_t* stage = nullptr;
     int stage_rows = 0;
+
+    bool is_float() const { return row_dwords == 64; }
+    size_t row_bytes() const { return (size_t)row_dwords * 4; }
 };
 
 struct TableColumns {
@@ -42,10 +48,19 @@ struct TableColumns {
     int *octave, *class_id, *image_id, *lod;
     uint32_t* desc64;
     int* id;
+    int row_shift;   // log2 of the dwords of a descriptor row: 4 (16 dwords) or 6 (64); a kernel gives a row that many lanes, one dword each
+    __host__ __device__ __forceinline__ int row_dwords() const { return 1 << row_shift; }
 };
 
 inline TableColumns columns_of(KeypointTable* t) {
-    return TableColumns{t->x, t->y, t->size, t->angle, t->response, t->octave, t->class_id, t->image_id, t->lod, reinterpret_cast<uint32_t*>(t->desc64), t->id};
+    return TableColumns{t->x, t->y, t->size, t->angle, t->response, t->octave, t->class_id, t->image_id, t->lod, reinterpret_cast<uint32_t*>(t->desc64), t->id,
+                        t->is_float() ? 6 : 4};
+}
+
+// the typed entries: a byte-typed call serves byte tables only, a float-typed call float tables only
+inline void require_table_kind(const KeypointTable* t, bool want_float) {
+    APDS_REQUIRE(t->is_float() == want_float, APDS_ERR_BAD_ARG,
+                 want_float ? "this call takes a float table (apds_db_create_float)" : "this call takes a byte table (apds_db_create); a float table has a _float twin");
 }
 
 template <class T>

@@ -4,7 +4,9 @@
 //   read    : feature_database/src/keypointdb.rs:28-90 - by id here; the ordered, limited selections in keypoint_select.hip
 //   delete  : keypointdb.rs:92-97, in keypoint_delete.hip
 // Columns are stored SoA (coalesced predicate scans); descriptors as 64-byte rows, i.e. already in the layout the
-// Hamming kernel streams. The table, its columns and what the three sources share: keypoint_table.h.
+// Hamming kernel streams - or, on a float table (apds_db_create_float), as rows of 64 floats, the layout the L2 matchers read. The kind
+// is fixed at create; the kernels receive the row width with the columns. The table, its columns and what the three sources share:
+// keypoint_table.h.
 #include <cstring>
 #include <vector>
 
@@ -42,21 +44,22 @@ __global__ void table_insert_kernel(const apds_keypoint* __restrict__ kps, const
     if (w == 0) store_keypoint_columns(c, base + i, kps[i], scale, xoff, yoff, image_id, lod, first_id + i);
 }
 
-// The same rows from the device buffers an extraction has written (28-byte keypoints, 64-byte descriptor rows; tile i at i * capacity
-// rows), every tile of a batch in one launch: 16 lanes per table row, one dword each. tile_offsets[i] = rows of the tiles < i
-// (tile_offsets[n_tiles] = all rows), copied to LDS; a row group finds its tile by binary search (empty tiles repeat an offset: the last
-// tile whose offset is <= the row is the one that holds it). tile_xy_off[i] = that tile's (xoff, yoff). Bytes 61-63 of a source row are
-// not trusted: word 15 keeps byte 60 alone.
-__global__ __launch_bounds__(256) void table_insert_dev_kernel(const apds_keypoint* __restrict__ kps, const uint32_t* __restrict__ desc64_src, int n_tiles,
+// The same rows from the device buffers an extraction has written (28-byte keypoints, descriptor rows of the table's kind: 64 bytes or
+// 64 floats; tile i at i * capacity rows), every tile of a batch in one launch: a lane per dword of a table row (16 or 64 of them).
+// tile_offsets[i] = rows of the tiles < i (tile_offsets[n_tiles] = all rows), copied to LDS; a row group finds its tile by binary search
+// (empty tiles repeat an offset: the last tile whose offset is <= the row is the one that holds it). tile_xy_off[i] = that tile's
+// (xoff, yoff). Bytes 61-63 of a 64-byte source row are not trusted: word 15 keeps byte 60 alone. A float row is stored whole.
+__global__ __launch_bounds__(256) void table_insert_dev_kernel(const apds_keypoint* __restrict__ kps, const uint32_t* __restrict__ desc_src, int n_tiles,
                                                                int capacity, const int* __restrict__ tile_offsets, const float2* __restrict__ tile_xy_off,
                                                                int first_image_id, int lod, float scale, long long base, int first_id, TableColumns c) {
     APDS_RAISE_WAVE_PRIORITY();
     extern __shared__ int offs[];   // n_tiles + 1
     for (int i = threadIdx.x; i <= n_tiles; i += blockDim.x) offs[i] = tile_offsets[i];
     __syncthreads();
+    const int W = c.row_dwords();
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long long)offs[n_tiles] * 16) return;
-    const int r = (int)(t >> 4), w = (int)(t & 15);
+    if (t >= (long long)offs[n_tiles] * W) return;
+    const int r = (int)(t >> c.row_shift), w = (int)(t & (W - 1));
     int lo = 0, hi = n_tiles - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -64,9 +67,9 @@ __global__ __launch_bounds__(256) void table_insert_dev_kernel(const apds_keypoi
         else hi = mid - 1;
     }
     const long long src = (long long)lo * capacity + (r - offs[lo]);
-    uint32_t v = desc64_src[src * 16 + w];
-    if (w == 15) v &= 0xFFu;
-    c.desc64[(base + r) * 16 + w] = v;
+    uint32_t v = desc_src[src * W + w];
+    if (W == 16 && w == 15) v &= 0xFFu;
+    c.desc64[(base + r) * W + w] = v;
     if (w == 0) {
         const float2 o = tile_xy_off[lo];
         store_keypoint_columns(c, base + r, kps[src], scale, o.x, o.y, first_image_id + lo, lod, first_id + r);
@@ -86,10 +89,10 @@ struct FoundRow {
     long long row;   // -1: no row has the id
     apds_keypoint kp;
     int image_id;
-    uint32_t desc[16];
+    uint32_t desc[64];   // the row's dwords: the first 16 of a byte table, all 64 of a float table
 };
 
-// one wave: lane 0 searches the id column, 16 lanes copy the descriptor row
+// one wave: lane 0 searches the id column, a lane per dword copies the descriptor row
 __global__ __launch_bounds__(64) void table_read_id_kernel(TableColumns c, long long n, int id, FoundRow* __restrict__ out) {
     __shared__ long long found;
     if (threadIdx.x == 0) found = find_id_row(c.id, n, id);
@@ -97,7 +100,8 @@ __global__ __launch_bounds__(64) void table_read_id_kernel(TableColumns c, long 
     const long long r = found;
     if (threadIdx.x == 0) out->row = r;
     if (r < 0) return;
-    if (threadIdx.x < 16) out->desc[threadIdx.x] = c.desc64[r * 16 + threadIdx.x];
+    const int W = c.row_dwords();
+    if ((int)threadIdx.x < W) out->desc[threadIdx.x] = c.desc64[r * W + threadIdx.x];
     if (threadIdx.x == 0) {
         out->kp = load_keypoint(c, r);
         out->image_id = c.image_id[r];
@@ -129,9 +133,10 @@ int table_device(const void* db) {
 // n_tiles tiles of an extraction's device output appended in tile order by one launch on s; the small tile table comes from the calling
 // thread's workspace (no ws_reset here: the extraction's buffers may live there). Everything is checked before anything is written.
 // Synchronises s.
-void table_insert_batch_device(void* db, const void* kps_dev, const void* desc64_dev, int n_tiles, int capacity, const int32_t* counts, int first_image_id,
-                               int lod, const uint32_t* columns_rows, uint64_t tile_w, uint64_t tile_h, hipStream_t s) {
-    KeypointTable* t = static_cast<KeypointTable*>(db);
+// (Index: u32 for the batch entries, u64 for apds_db_insert_image_float's one tile, which takes the column and row apds_db_insert_image takes)
+template <class Index>
+static void table_insert_tiles(KeypointTable* t, const void* kps_dev, const void* desc64_dev, int n_tiles, int capacity, const int32_t* counts, int first_image_id,
+                               int lod, const Index* columns_rows, uint64_t tile_w, uint64_t tile_h, hipStream_t s) {
     APDS_REQUIRE(t && lod >= 0 && lod < 31 && capacity >= 0, APDS_ERR_BAD_ARG, "bad argument");
     APDS_REQUIRE(n_tiles >= 1 && n_tiles <= 4096, APDS_ERR_BAD_ARG, "batch must hold 1 .. 4096 tiles");
     APDS_REQUIRE(counts && columns_rows, APDS_ERR_BAD_ARG, "null argument");
@@ -157,7 +162,7 @@ void table_insert_batch_device(void* db, const void* kps_dev, const void* desc64
                  "device keypoints and descriptor rows must be 4-byte aligned");
     int* dtab = ctx().alloc_n<int>(table.size());
     HIP_CHECK(hipMemcpyAsync(dtab, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(table_insert_dev_kernel, dim3(ceil_div(total * 16, 256)), dim3(256), ((size_t)n_tiles + 1) * sizeof(int), s,
+    hipLaunchKernelGGL(table_insert_dev_kernel, dim3(ceil_div(total * t->row_dwords, 256)), dim3(256), ((size_t)n_tiles + 1) * sizeof(int), s,
                        static_cast<const apds_keypoint*>(kps_dev), static_cast<const uint32_t*>(desc64_dev), n_tiles, capacity, (const int*)dtab,
                        reinterpret_cast<const float2*>(dtab + xy_at), first_image_id, lod, ldexpf(1.0f, lod), (long long)t->n, (int)t->next_id, columns_of(t));
     HIP_CHECK(hipGetLastError());
@@ -166,30 +171,57 @@ void table_insert_batch_device(void* db, const void* kps_dev, const void* desc64
     t->next_id += total;
 }
 
+void table_insert_batch_device(void* db, const void* kps_dev, const void* desc64_dev, int n_tiles, int capacity, const int32_t* counts, int first_image_id,
+                               int lod, const uint32_t* columns_rows, uint64_t tile_w, uint64_t tile_h, hipStream_t s) {
+    table_insert_tiles(static_cast<KeypointTable*>(db), kps_dev, desc64_dev, n_tiles, capacity, counts, first_image_id, lod, columns_rows, tile_w, tile_h, s);
+}
+
+int table_descriptor(const void* db) {
+    APDS_REQUIRE(db, APDS_ERR_BAD_ARG, "null table");
+    return static_cast<const KeypointTable*>(db)->is_float() ? APDS_AKAZE_DESCRIPTOR_KAZE : APDS_AKAZE_DESCRIPTOR_MLDB;
+}
+
 }  // namespace apds
 
 extern "C" {
 
-int apds_db_create(void** db, int64_t capacity) {
+namespace {
+int table_create(void** db, int64_t capacity, int row_dwords) {
     return guarded([&] {
         APDS_REQUIRE(db && capacity > 0 && capacity < (1ll << 31), APDS_ERR_BAD_ARG, "bad capacity");
         ThreadCtx& c = ctx();
         KeypointTable* t = new KeypointTable();
         t->device = c.device;
         t->capacity = capacity;
+        t->row_dwords = row_dwords;
         try {
             dev_alloc(t->x, capacity); dev_alloc(t->y, capacity); dev_alloc(t->size, capacity); dev_alloc(t->angle, capacity);
             dev_alloc(t->response, capacity); dev_alloc(t->octave, capacity); dev_alloc(t->class_id, capacity);
-            dev_alloc(t->image_id, capacity); dev_alloc(t->lod, capacity); dev_alloc(t->desc64, (size_t)capacity * 64);
+            dev_alloc(t->image_id, capacity); dev_alloc(t->lod, capacity); dev_alloc(t->desc64, (size_t)capacity * t->row_bytes());
             dev_alloc(t->id, capacity);
             t->view_cap = std::min<int64_t>(capacity, APDS_MAX_POINTS);
             dev_alloc(t->view_rows, t->view_cap); dev_alloc(t->view_kps, t->view_cap); dev_alloc(t->view_image_id, t->view_cap);
-            dev_alloc(t->view_desc64, (size_t)t->view_cap * 64);
+            dev_alloc(t->view_desc64, (size_t)t->view_cap * t->row_bytes());
         } catch (...) {
             table_free(t);
             throw;
         }
         *db = t;
+    });
+}
+}  // namespace
+
+int apds_db_create(void** db, int64_t capacity) { return table_create(db, capacity, 16); }
+
+// the same table with a descriptor column of 64 x f32 (M-SURF rows, APDS_AKAZE_DESCRIPTOR_KAZE)
+int apds_db_create_float(void** db, int64_t capacity) { return table_create(db, capacity, APDS_DESC_FLOAT_DIM); }
+
+int apds_db_info(const void* db, int* descriptor, int* row_bytes) {
+    return guarded([&] {
+        const KeypointTable* t = static_cast<const KeypointTable*>(db);
+        APDS_REQUIRE(t, APDS_ERR_BAD_ARG, "null table");
+        if (descriptor) *descriptor = table_descriptor(t);
+        if (row_bytes) *row_bytes = (int)t->row_bytes();
     });
 }
 
@@ -207,6 +239,7 @@ int apds_db_insert_image(void* db, const apds_keypoint* kps, const uint8_t* desc
     return guarded([&] {
         KeypointTable* t = static_cast<KeypointTable*>(db);
         APDS_REQUIRE(t && n >= 0 && lod >= 0 && lod < 31, APDS_ERR_BAD_ARG, "bad argument");
+        require_table_kind(t, false);
         APDS_REQUIRE(t->n + n <= t->capacity, APDS_ERR_NOMEM, "keypoint table is full");
         APDS_REQUIRE(t->next_id + n <= (1ll << 31), APDS_ERR_NOMEM, "keypoint table has given out every 32-bit id");
         if (!n) return;
@@ -229,7 +262,33 @@ int apds_db_insert_image(void* db, const apds_keypoint* kps, const uint8_t* desc
     });
 }
 
+// The float table's host insert: n rows of 64 floats. The rows are uploaded as they are and go through the device insert's launch, so a
+// row reaches the table by one path whichever side it comes from.
+int apds_db_insert_image_float(void* db, const apds_keypoint* kps, const float* desc64f, int n, int image_id, int lod, uint64_t column, uint64_t row,
+                               uint64_t tile_w, uint64_t tile_h) {
+    return guarded([&] {
+        KeypointTable* t = static_cast<KeypointTable*>(db);
+        APDS_REQUIRE(t && n >= 0 && lod >= 0 && lod < 31, APDS_ERR_BAD_ARG, "bad argument");
+        require_table_kind(t, true);
+        APDS_REQUIRE(t->n + n <= t->capacity, APDS_ERR_NOMEM, "keypoint table is full");
+        APDS_REQUIRE(t->next_id + n <= (1ll << 31), APDS_ERR_NOMEM, "keypoint table has given out every 32-bit id");
+        if (!n) return;
+        APDS_REQUIRE(kps && desc64f, APDS_ERR_BAD_ARG, "null argument");
+        ThreadCtx& c = ctx();
+        c.ws_reset();
+        hipStream_t s = c.stream;
+        apds_keypoint* dk = c.alloc_n<apds_keypoint>(n);
+        float* dd = c.alloc_n<float>((size_t)n * APDS_DESC_FLOAT_DIM);
+        HIP_CHECK(hipMemcpyAsync(dk, kps, (size_t)n * sizeof(apds_keypoint), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(dd, desc64f, (size_t)n * APDS_DESC_FLOAT_DIM * sizeof(float), hipMemcpyHostToDevice, s));
+        const int32_t counts[1] = {n};
+        const uint64_t cr[2] = {column, row};
+        table_insert_tiles(t, dk, dd, 1, n, counts, image_id, lod, cr, tile_w, tile_h, s);
+    });
+}
+
 // the same rows from what apds_dev_akaze_extract has written on the device (no upload, no repack): one tile, then a batch of them
+// (a float table: from what apds_dev_akaze_extract_float has written)
 int apds_db_insert_batch_dev(void* db, const void* kps_dev, const void* desc64_dev, int n_tiles, int capacity, const int32_t* counts, int first_image_id,
                              int lod, const uint32_t* columns_rows, uint64_t tile_w, uint64_t tile_h, void* stream) {
     return guarded([&] {
@@ -317,10 +376,13 @@ int apds_db_ids(void* db, void** ids_dev) {
     });
 }
 
-int apds_db_read_keypoint_from_id(void* db, int id, apds_keypoint* kp, uint8_t* desc61, int* image_id, int64_t* row) {
+namespace {
+// both reads by id: desc receives desc_bytes of the row (61 of a byte row, 256 of a float row)
+int table_read_id(void* db, bool want_float, int id, apds_keypoint* kp, void* desc, size_t desc_bytes, int* image_id, int64_t* row) {
     return guarded([&] {
         KeypointTable* t = static_cast<KeypointTable*>(db);
         APDS_REQUIRE(t, APDS_ERR_BAD_ARG, "null table");
+        require_table_kind(t, want_float);
         APDS_REQUIRE(t->n > 0 && id >= 1, APDS_ERR_OUT_OF_RANGE, "no keypoint has this id");
         ThreadCtx& c = ctx();
         require_table_device(t);
@@ -334,10 +396,19 @@ int apds_db_read_keypoint_from_id(void* db, int id, apds_keypoint* kp, uint8_t* 
         HIP_CHECK(hipStreamSynchronize(s));
         APDS_REQUIRE(h.row >= 0, APDS_ERR_OUT_OF_RANGE, "no keypoint has this id");
         if (kp) *kp = h.kp;
-        if (desc61) memcpy(desc61, h.desc, 61);
+        if (desc) memcpy(desc, h.desc, desc_bytes);
         if (image_id) *image_id = h.image_id;
         if (row) *row = h.row;
     });
+}
+}  // namespace
+
+int apds_db_read_keypoint_from_id(void* db, int id, apds_keypoint* kp, uint8_t* desc61, int* image_id, int64_t* row) {
+    return table_read_id(db, false, id, kp, desc61, APDS_DESC_BYTES, image_id, row);
+}
+
+int apds_db_read_keypoint_from_id_float(void* db, int id, apds_keypoint* kp, float* desc64f, int* image_id, int64_t* row) {
+    return table_read_id(db, true, id, kp, desc64f, APDS_DESC_FLOAT_DIM * sizeof(float), image_id, row);
 }
 
 }  // extern "C"

@@ -383,7 +383,11 @@ int apds_l2_train_create(void** set, const void* train, int64_t nt, int dim, uin
 }
 
 int apds_l2_train_destroy(void* set) {
-    return guarded([&] { l2_train_destroy(static_cast<L2Train*>(set)); });
+    return guarded([&] {
+        L2Train* t = static_cast<L2Train*>(set);
+        APDS_REQUIRE(!t || !t->borrowed, APDS_ERR_BAD_ARG, "this train set belongs to a table view (apds_db_view_l2_train): apds_db_view_destroy releases it");
+        l2_train_destroy(t);
+    });
 }
 
 int apds_l2_train_info(const void* set, int64_t* n_train, int* dim, int* screen_ready) {

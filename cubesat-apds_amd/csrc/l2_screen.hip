@@ -42,6 +42,7 @@
 #include <memory>
 #include <vector>
 
+#include "bf16_round.h"
 #include "config.h"
 #include "kernels.h"
 #include "topk_keys.h"
@@ -77,13 +78,6 @@ struct ScShape {
     static constexpr int ROWS_PER_PASS = 512 / GROUPS;   // rows one piece index of all threads covers (32 / 64)
     static constexpr size_t LDS = (size_t)2 * SC_TM * PITCH + 2 * SC_TM * sizeof(float);
 };
-
-__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
-    uint32_t x = __float_as_uint(f);
-    if ((x & 0x7F800000u) == 0x7F800000u) return (uint16_t)(x >> 16) | ((x & 0xFFFFu) ? 0x40 : 0);   // inf / nan
-    x += 0x7FFFu + ((x >> 16) & 1u);
-    return (uint16_t)(x >> 16);
-}
 
 // rows of f32 -> bf16 (scaled by `scale`, a power of two: exact), and |row|^2 in f32 exactly as row_norms_kernel of l2_match.hip
 // (n_elems = rows x dim, a multiple of 4)
@@ -374,6 +368,7 @@ struct ScTrainSide {
 // the train side from the rows (the one-shot entry does this per call in the workspace, a train set once into memory of its own)
 static void sc_prepare_train(const float* t, long long nt, int dim, float* tn, uint16_t* tb, unsigned int* tmax, hipStream_t s) {
     HIP_CHECK(hipMemsetAsync(tmax, 0, 16, s));
+    KernelTimer timer("l2_train_prepare", s);   // the three launches a fused gather replaces (tools/db_view_probe.py --float)
     l2_row_norms_device(t, nt, dim, tn, s);
     hipLaunchKernelGGL(to_bf16_rows_kernel, dim3(ceil_div(nt * dim / 4, 256)), dim3(256), 0, s, t, nt * dim, -2.0f, tb);
     hipLaunchKernelGGL(max_norm_kernel, dim3(256), dim3(256), 0, s, (const float*)tn, nt, tmax);

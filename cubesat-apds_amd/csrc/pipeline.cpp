@@ -112,6 +112,7 @@ struct Slot {
     const void* view_rows64 = nullptr;
     const apds_keypoint* view_kps = nullptr;
     const void* view_xyz = nullptr;
+    void* view_l2_train = nullptr;   // a float table: the view's train side (apds_db_view_l2_train), contents those of the frame's select
     int n_view = 0;
     int owner = 0;
     // the job
@@ -341,6 +342,8 @@ struct Pipeline {
                         s->status = APDS_ERR_ASSERT;
                         s->error = "the frame's selection has fewer than two rows: a train set of at least two rows is required";
                     }
+                } else if (K > 0 && float_rows) {   // the train side the select's gather has just queued on this stream
+                    PIPE_OK(apds_dev_l2_train_top2(s->view_l2_train, s->desc, K, APDS_L2_SCREEN, s->keys, st_match, nullptr, nullptr));
                 } else if (K > 0 && crosscheck) {
                     PIPE_OK(apds_dev_hamming_topk(s->view_rows64, s->n_view, s->desc, K, 0, 1, s->train_best, st_match));
                 } else if (K > 0) {
@@ -692,7 +695,7 @@ int create_pipeline(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint
             HIP_CHECK(hipStreamCreateWithPriority(&P->st_gather, hipStreamNonBlocking, hp));
             HIP_CHECK(hipStreamCreateWithPriority(&P->st_counts, hipStreamNonBlocking, hp));
         }
-        if (float_rows) P->l2_train = l2_train_create(static_cast<const float*>(db_rows64_dev), n_rows, 64, index_base, P->st_match);
+        if (float_rows && !table) P->l2_train = l2_train_create(static_cast<const float*>(db_rows64_dev), n_rows, 64, index_base, P->st_match);
         if (P->world == 1 && !shard && !table && !float_rows && cfg.match_mfma) P->db_expanded = hm_train_create(P->db_rows, P->n_rows, P->st_match);
         const size_t cap = (size_t)P->cap;
         for (int i = 0; i < n_slots; i++) {
@@ -720,6 +723,7 @@ int create_pipeline(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint
                 int rc = apds_db_view_create(table, view_capacity, &s->view);
                 void *rows64 = nullptr, *kps = nullptr;
                 if (rc == APDS_OK) rc = apds_db_view_pointers(s->view, &rows64, &kps, nullptr, nullptr, nullptr, nullptr);
+                if (rc == APDS_OK && float_rows) rc = apds_db_view_l2_train(s->view, &s->view_l2_train);   // (borrowed: the view owns it)
                 if (rc != APDS_OK) {
                     const std::string why = apds_last_error();
                     P->slots.push_back(std::move(s));   // (destroy releases what this slot already holds)
@@ -799,7 +803,11 @@ int apds_pipeline_create_float(void** pipe, const void* db_rows_f32_dev, int64_t
 
 int apds_pipeline_create_table(void** pipe, void* db, int view_capacity, const apds_pipeline_params* params) {
     if (!db) return guarded([] { fail(APDS_ERR_BAD_ARG, "null table"); });
-    return create_pipeline(pipe, nullptr, 0, 0, nullptr, nullptr, 0, db, view_capacity, params);
+    // a float table makes a float pipeline: M-SURF extraction, the L2 matcher for life, each frame's train side from its slot's view
+    int descriptor = APDS_AKAZE_DESCRIPTOR_MLDB;
+    const int rc = apds_db_info(db, &descriptor, nullptr);
+    if (rc != APDS_OK) return rc;
+    return create_pipeline(pipe, nullptr, 0, 0, nullptr, nullptr, 0, db, view_capacity, params, descriptor == APDS_AKAZE_DESCRIPTOR_KAZE);
 }
 
 int apds_pipeline_submit(void* pipe, const void* frame, size_t stride_bytes, int on_device, int64_t* frame_id) {
@@ -898,7 +906,7 @@ int apds_pipeline_set_matcher(void* pipe, int matcher) {
                      "matcher: APDS_PIPELINE_MATCH_RATIO (0), APDS_PIPELINE_MATCH_CROSSCHECK (1) or, on a float pipeline, APDS_PIPELINE_MATCH_L2_RATIO (2)");
         Pipeline* P = pipe_handle(pipe);
         APDS_REQUIRE(P->float_rows == (matcher == APDS_PIPELINE_MATCH_L2_RATIO), APDS_ERR_BAD_ARG,
-                     P->float_rows ? "a float pipeline's matcher is APDS_PIPELINE_MATCH_L2_RATIO for life" : "APDS_PIPELINE_MATCH_L2_RATIO needs a float pipeline (apds_pipeline_create_float)");
+                     P->float_rows ? "a float pipeline's matcher is APDS_PIPELINE_MATCH_L2_RATIO for life" : "APDS_PIPELINE_MATCH_L2_RATIO needs a float pipeline (apds_pipeline_create_float, or apds_pipeline_create_table on a float table)");
         APDS_REQUIRE(matcher == APDS_PIPELINE_MATCH_RATIO || !(P->shard || P->world > 1), APDS_ERR_NOT_IMPLEMENTED,
                      "the cross-check over a row-sharded train set (the per-query minimum across shards) is not built");
         std::lock_guard<std::mutex> one(P->submit_m);

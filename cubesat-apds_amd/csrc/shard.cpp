@@ -559,7 +559,10 @@ int apds_db_shard(void* db, int rank, int world, int transport, const apds_comm_
         APDS_REQUIRE(db && shard, APDS_ERR_BAD_ARG, "null argument");
         APDS_REQUIRE(world >= 1 && rank >= 0 && rank < world, APDS_ERR_BAD_ARG, "rank outside [0, world)");
         void *rows = nullptr, *kps = nullptr, *ids = nullptr, *img = nullptr;
-        int n = 0;
+        int n = 0, descriptor = 0;
+        const int rc0 = apds_db_info(db, &descriptor, nullptr);
+        if (rc0 != APDS_OK) fail(rc0, apds_last_error());
+        APDS_REQUIRE(descriptor == APDS_AKAZE_DESCRIPTOR_MLDB, APDS_ERR_BAD_ARG, "a float table cannot be sharded: the sharded matcher is Hamming on 64-byte rows");
         const int rc = apds_db_view(db, &rows, &kps, &ids, &img, &n);
         if (rc != APDS_OK) fail(rc, apds_last_error());
         // block partition of the view's rows: rank r holds [r * n / world, (r + 1) * n / world); trainIdx stays the position in the view

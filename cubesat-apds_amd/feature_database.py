@@ -22,9 +22,19 @@ class KeypointRows:
 
 
 class KeypointTable:
-    def __init__(self, capacity):
+    """descriptor: "mldb" (a byte table: 61-byte M-LDB descriptors in 64-byte rows) or "kaze" (a float table: M-SURF rows of 64 floats, the
+    L2 matcher's input). Every method serves both kinds; descriptors go in and come out as uint8 [n, 61] or float32 [n, 64]."""
+
+    def __init__(self, capacity, descriptor="mldb"):
+        if descriptor not in _lib.AKAZE_DESCRIPTORS:
+            raise _lib.ApdsError(_lib.ERR_BAD_ARG, f"unknown descriptor {descriptor!r}: 'mldb' or 'kaze'")
+        self.descriptor = descriptor
+        self.is_float = descriptor == "kaze"
         self._h = C.c_void_p()
-        check(lib().apds_db_create(C.byref(self._h), int(capacity)))
+        check((lib().apds_db_create_float if self.is_float else lib().apds_db_create)(C.byref(self._h), int(capacity)))
+
+    def _empty_descriptors(self, n):
+        return np.zeros((n, _lib.DESC_FLOAT_DIM), np.float32) if self.is_float else np.zeros((n, 61), np.uint8)
 
     def close(self):
         if self._h:
@@ -44,13 +54,17 @@ class KeypointTable:
         """preprocessor/src/main.rs:296-324: insert every keypoint of one tile (`keypoints.to_db_type(image_id)` with x, y
         lifted to level-of-detail-0 pixels) — one INSERT ... VALUES in the reference (keypointdb.rs:100-109)."""
         kp = np.ascontiguousarray(extracted.keypoints, KEYPOINT_DTYPE)
-        d = np.ascontiguousarray(extracted.descriptors, np.uint8)
-        check(lib().apds_db_insert_image(self._h, ptr(kp), ptr(d), len(kp), int(image_id), int(level_of_detail), int(column), int(row),
-                                         int(tile_size[0]), int(tile_size[1])))
+        d = extracted.descriptors
+        if self.is_float != (np.asarray(d).dtype == np.float32):     # (the library's own check, made before the array is converted)
+            raise _lib.ApdsError(_lib.ERR_BAD_ARG, "a float table takes float32 descriptors (a 'kaze' extraction), a byte table uint8 ones")
+        d = np.ascontiguousarray(d, np.float32 if self.is_float else np.uint8)
+        insert = lib().apds_db_insert_image_float if self.is_float else lib().apds_db_insert_image
+        check(insert(self._h, ptr(kp), ptr(d), len(kp), int(image_id), int(level_of_detail), int(column), int(row), int(tile_size[0]), int(tile_size[1])))
 
     def create_keypoints_device(self, kps_ptr, desc64_ptr, n, image_id, level_of_detail=0, column=0, row=0, tile_size=(0, 0), stream=None):
         """create_keypoints for rows that are already on the device: kps_ptr / desc64_ptr are what apds_dev_akaze_extract wrote (28-byte
-        keypoints, 64-byte descriptor rows), `stream` the stream it was issued on (None: the calling thread's own). Same stored rows."""
+        keypoints, 64-byte descriptor rows; on a float table what apds_dev_akaze_extract_float wrote: rows of 64 floats), `stream` the
+        stream it was issued on (None: the calling thread's own). Same stored rows."""
         check(lib().apds_db_insert_dev(self._h, kps_ptr, desc64_ptr, int(n), int(image_id), int(level_of_detail), int(column), int(row),
                                        int(tile_size[0]), int(tile_size[1]), stream))
 
@@ -84,11 +98,12 @@ class KeypointTable:
         check(lib().apds_db_select(self._h, mode, int(value), float(box[0]), float(box[1]), float(box[2]), float(box[3]), C.byref(n)))
         m = n.value
         kp = np.zeros(m, KEYPOINT_DTYPE)
-        d = np.zeros((m, 61), np.uint8)
+        d = self._empty_descriptors(m)
         ids = np.zeros(m, np.int32)
         img = np.zeros(m, np.int32)
         if m:
-            check(lib().apds_db_view_download(self._h, ptr(kp), ptr(d), ptr(ids), ptr(img)))
+            download = lib().apds_db_view_download_float if self.is_float else lib().apds_db_view_download
+            check(download(self._h, ptr(kp), ptr(d), ptr(ids), ptr(img)))
         return KeypointRows(ids, kp, d, img)
 
     def read_keypoints_from_image_id(self, image_id):
@@ -107,9 +122,10 @@ class KeypointTable:
         """keypointdb.rs:28-36 -> KeypointRows of one row (ids, keypoints, descriptors, image_ids of length 1). Raises
         ApdsError(ERR_OUT_OF_RANGE) where the reference returns Err(NotFound): an id that was deleted or never given."""
         kp = np.zeros(1, KEYPOINT_DTYPE)
-        d = np.zeros((1, 61), np.uint8)
+        d = self._empty_descriptors(1)
         img = C.c_int(0)
-        check(lib().apds_db_read_keypoint_from_id(self._h, int(id), ptr(kp), ptr(d), C.byref(img), None))
+        read = lib().apds_db_read_keypoint_from_id_float if self.is_float else lib().apds_db_read_keypoint_from_id
+        check(read(self._h, int(id), ptr(kp), ptr(d), C.byref(img), None))
         return KeypointRows(np.array([id], np.int32), kp, d, np.array([img.value], np.int32))
 
     def ids(self):
@@ -163,7 +179,14 @@ class KeypointTable:
         return TableView(self, capacity)
 
     def knn_match_view(self, query_desc, k=2):
-        """BFMatcher.knnMatch of host query descriptors against the last selection, which stays resident on the device."""
+        """BFMatcher.knnMatch of host query descriptors against the last selection, which stays resident on the device. A float table:
+        NORM_L2 on float32 [n, 64] queries, k 1 or 2, distances float32."""
+        if self.is_float:
+            q = np.ascontiguousarray(query_desc, np.float32).reshape(-1, _lib.DESC_FLOAT_DIM)
+            idx = np.zeros((q.shape[0], k), np.int32)
+            dist = np.zeros((q.shape[0], k), np.float32)
+            check(lib().apds_db_l2_knn_match(self._h, ptr(q), q.shape[0], int(k), ptr(idx), ptr(dist)))
+            return idx, dist
         q = np.ascontiguousarray(query_desc, np.uint8)
         idx = np.zeros((q.shape[0], k), np.int32)
         dist = np.zeros((q.shape[0], k), np.int32)
@@ -217,6 +240,13 @@ class TableView:
         r, k, i, g, x, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
         check(lib().apds_db_view_pointers(self._h, C.byref(r), C.byref(k), C.byref(i), C.byref(g), C.byref(x), C.byref(n)))
         return r.value, k.value, i.value, g.value, x.value, n.value
+
+    def l2_train(self):
+        """A float table's view: the handle of the L2 train set over the last selection (apds_db_view_l2_train), as a c_void_p for
+        apds_dev_l2_train_top2 / apds_l2_train_info. Borrowed: it lives as long as the view and follows every select; never destroy it."""
+        h = C.c_void_p()
+        check(lib().apds_db_view_l2_train(self._h, C.byref(h)))
+        return h
 
 
 class ElevationTable:

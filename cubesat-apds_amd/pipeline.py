@@ -321,7 +321,18 @@ class L2TrainSet:
         n, dim = int(rows_f32.shape[0]), int(rows_f32.shape[1])
         check(lib().apds_l2_train_create(C.byref(h), rows_f32.data_ptr() if n else None, n, dim, self.index_base))
         self._h = h
+        self._owner = None
         self.mode_used, self.candidates_per_query = None, 0.0     # of the last top2()
+
+    @classmethod
+    def of_view(cls, view):
+        """The train set a float KeypointTable's TableView keeps over its last selection (TableView.l2_train()): borrowed from the view, which
+        it keeps alive; it follows every select of the view, and close() only lets go of it."""
+        self = cls.__new__(cls)
+        self.rows, self.index_base = None, 0
+        self._h, self._owner = view.l2_train(), view
+        self.mode_used, self.candidates_per_query = None, 0.0
+        return self
 
     def info(self):
         """(n_train, dim, screen_ready)"""
@@ -342,7 +353,8 @@ class L2TrainSet:
 
     def close(self):
         h, self._h = self._h, None
-        if h is not None:
+        owner, self._owner = self._owner, None
+        if h is not None and owner is None:     # (a view's train set is the view's)
             check(lib().apds_l2_train_destroy(h))
 
     def __del__(self):
@@ -566,10 +578,14 @@ class StreamedFramePipeline:
         self.lens = None if lens is None else (_lib.lens_args(lens[0], lens[1]), int(lens[2]) if len(lens) > 2 else 5)
         self.matcher_mode = _matcher_code(matcher)   # "ratio" | "crosscheck" (apds_pipeline_set_matcher; one GPU and per-frame-view pipelines)
         # "l2": the float pipeline (apds_pipeline_create_float) - db_rows64 is then [N, 64] float32; one GPU, a fixed train set
+        # (or a per-frame view of a float KeypointTable: from_table chooses it)
         self.float_rows = self.matcher_mode == _lib.PIPELINE_MATCH_L2_RATIO
-        if self.float_rows and (per_frame_table is not None or group is not None or db_rows64 is None or db_rows64.dtype != torch.float32
-                                or db_rows64.dim() != 2 or db_rows64.shape[1] != 64 or not db_rows64.is_contiguous()):
-            raise ValueError('matcher "l2": a contiguous [N, 64] float32 device tensor of train rows, one GPU, no per-frame table')
+        float_table = per_frame_table is not None and getattr(per_frame_table, "is_float", False)
+        if float_table != self.float_rows and per_frame_table is not None:
+            raise ValueError('a float table\'s pipeline runs matcher "l2", a byte table\'s "ratio" or "crosscheck"')
+        if self.float_rows and not float_table and (group is not None or db_rows64 is None or db_rows64.dtype != torch.float32
+                                                    or db_rows64.dim() != 2 or db_rows64.shape[1] != 64 or not db_rows64.is_contiguous()):
+            raise ValueError('matcher "l2": a contiguous [N, 64] float32 device tensor of train rows (or a float table\'s per-frame view), one GPU')
         self.dev = torch.device(device)
         self.per_frame_table = per_frame_table     # a KeypointTable: the train set is selected from it per frame (from_table)
         self.view_capacity = int(view_capacity) if view_capacity else 0
@@ -615,6 +631,10 @@ class StreamedFramePipeline:
         the pose stage on the table's world points.
         per_frame_view=True: every frame is matched against the rows ITS selection returns (keypointdb.rs:50-90, at most view_capacity
         rows, default 262143) instead of the whole table: run(frames, count, selections=[...]) / submit_select(). One GPU."""
+        if getattr(table, "is_float", False):     # a float table: the L2 matcher on each frame's view (apds_db_view_l2_train), the only one it has
+            if not per_frame_view:
+                raise ValueError("a float table's pipeline selects its train set per frame: per_frame_view=True")
+            kw.setdefault("matcher", "l2")
         if per_frame_view:
             self = cls(None, None, device=device, per_frame_table=table, view_capacity=view_capacity, **kw)
             self._table = table

@@ -192,8 +192,17 @@ def replace_tiles(table, images, dataset, amount_lod, lod, cells, batch=1, resam
     return list(zip(ids, deleted, inserted))
 
 
-def process_lod_from_mosaic(table, images, dataset, lod, workers=1, fused=True, batch=1, resample="nearest", mask_nodata=False, device_insert=False):
-    """main.rs:175-194 — all levels 0 .. lod-1."""
+def process_lod_from_mosaic(table, images, dataset, lod, workers=1, fused=True, batch=1, resample="nearest", mask_nodata=False, device_insert=False,
+                            descriptor=None):
+    """main.rs:175-194 — all levels 0 .. lod-1.
+    descriptor: None (the table's own kind), "mldb" or "kaze": it must be the kind of `table` (KeypointTable(.., descriptor=..)). A float
+    ("kaze") table is built through device_insert only: apds_mosaic_tiles_to_db extracts rows of the table's kind, and the keypoint columns
+    are the ones a byte table gets from the same tiles."""
+    kind = getattr(table, "descriptor", "mldb")
+    if descriptor is not None and descriptor != kind:
+        raise ValueError(f"descriptor={descriptor!r} but the table holds {kind!r} rows: make it with KeypointTable(capacity, descriptor={descriptor!r})")
+    if kind == "kaze" and not device_insert:
+        raise ValueError('a float ("kaze") table is built with device_insert=True')
     if device_insert and not isinstance(dataset, DeviceMosaic):
         raise ValueError("device_insert=True needs a DeviceMosaic dataset: the rows go from the extraction to the table on the device")
     return [downscale_from_lod(table, images, dataset, lod, i, workers, fused, batch, resample, mask_nodata, device_insert) for i in range(lod)]

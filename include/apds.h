@@ -430,6 +430,23 @@ int apds_dev_l2_train_top2(void* set, const void* query_f32_dev, int n_query, in
 int apds_db_create(void** db, int64_t capacity);
 int apds_db_destroy(void* db);
 int64_t apds_db_rows(const void* db);
+/* A table has a KIND, fixed at create: apds_db_create makes a byte table (descriptor column of 64-byte M-LDB rows), apds_db_create_float a
+ * float table (descriptor column of 64 x f32 = 256 bytes, the M-SURF rows of apds_akaze_extract_float). apds_db_info reports
+ * APDS_AKAZE_DESCRIPTOR_MLDB / 64 or APDS_AKAZE_DESCRIPTOR_KAZE / 256 (either output may be NULL). Every other column, the ids, the
+ * selections, the deletes and the world points are the same for both kinds, from the same kernels.
+ * ROWS OF THE TABLE'S KIND: every call that takes or returns descriptor rows through a void* device pointer (apds_db_insert_dev,
+ * apds_db_insert_batch_dev, apds_db_view, apds_db_view_pointers, apds_db_table) means rows of the table's kind: 64-byte rows on a byte
+ * table, rows of 64 floats on a float table (what apds_dev_akaze_extract_float(_batch) writes; stored whole, nothing zeroed). Calls with a
+ * TYPED host pointer come in twins (apds_db_insert_image / _float, apds_db_view_download / _float, apds_db_read_keypoint_from_id /
+ * _float, apds_db_knn_match / apds_db_l2_knn_match): the byte-typed call on a float table and the float-typed call on a byte table
+ * return APDS_ERR_BAD_ARG and leave the table unchanged. apds_db_shard on a float table is APDS_ERR_BAD_ARG (the sharded matcher is
+ * Hamming). apds_mosaic_tiles_to_db extracts rows of the table's kind; the keypoint columns of a float table are those a byte table gets
+ * from the same tiles, bit for bit. */
+int apds_db_create_float(void** db, int64_t capacity);
+int apds_db_info(const void* db, int* descriptor, int* row_bytes);
+/* apds_db_insert_image on a float table: desc64f = n rows of 64 floats. */
+int apds_db_insert_image_float(void* db, const apds_keypoint* kps, const float* desc64f, int n, int image_id, int level_of_detail, uint64_t column,
+                               uint64_t row, uint64_t tile_w, uint64_t tile_h);
 int apds_db_insert_image(void* db, const apds_keypoint* kps, const uint8_t* desc61, int n, int image_id, int level_of_detail, uint64_t column,
                          uint64_t row, uint64_t tile_w, uint64_t tile_h);
 int apds_db_select(void* db, int mode, int value, float x_start, float y_start, float x_end, float y_end, int* n_out);
@@ -437,6 +454,11 @@ int apds_db_view(void* db, void** rows64_dev, void** kps_dev, void** row_ids_dev
 int apds_db_view_download(void* db, apds_keypoint* kps, uint8_t* desc61, int32_t* ids, int32_t* image_ids);
 /* knnMatch (any k >= 1 that apds_dev_hamming_topk serves) of host query descriptors against the current view; idx = position in the view (= trainIdx of the Vec the reference would hold) */
 int apds_db_knn_match(void* db, const uint8_t* query_desc, int n_query, int desc_bytes, int k, int32_t* idx, int32_t* dist);
+/* The float table's twins. apds_db_view_download_float: desc64f receives 64 floats per row of the current view. apds_db_l2_knn_match:
+ * apds_l2_knn_match (k 1 or 2, the exact f32 kernel, dist = the distance, idx -1 / dist +inf where the view has fewer than k rows) of
+ * n_query host rows of 64 floats against the current view, idx = position in the view. */
+int apds_db_view_download_float(void* db, apds_keypoint* kps, float* desc64f, int32_t* ids, int32_t* image_ids);
+int apds_db_l2_knn_match(void* db, const float* query, int n_query, int k, int32_t* idx, float* dist);
 /* apds_db_insert_image for rows that are already on the device: kps_dev (28-byte keypoints) and desc64_dev (64-byte descriptor rows) are
  * exactly what apds_dev_akaze_extract writes, n of them; no upload, no repack. The stored rows are apds_db_insert_image's bit for bit:
  * x = k.x * 2^lod + (float)(column * tile_w * 2^lod) (the u64 product first), the same for y, the other fields copied, bytes 61-63 of
@@ -499,6 +521,16 @@ int apds_db_view_select(void* view, int mode, int value, float x_start, float y_
  * be NULL. The pointers hold until apds_db_view_destroy; their contents until the next select. */
 int apds_db_view_pointers(const void* view, void** rows64_dev, void** kps_dev, void** row_ids_dev, void** image_ids_dev, void** xyz_dev,
                           int* n);
+/* A view of a FLOAT table also owns the train side of its current selection for the L2 matcher: per row |t|^2, the bf16 copy scaled by
+ * -2 and the largest norm (what apds_l2_train_create derives from resident rows), allocated at create for the view's capacity and written
+ * by the select's own gather launch from the rows it moves - no further pass over the selection, no further synchronisation. *set = a
+ * BORROWED train set over the view's rows with index base 0 (a key's row is the position in the view): pass it to
+ * apds_dev_l2_train_top2 / apds_l2_train_info; apds_l2_train_destroy refuses it (APDS_ERR_BAD_ARG, nothing released). The handle is valid until apds_db_view_destroy; its
+ * contents are those of the view's last select, complete when that select's stream has run, so a top-2 queued on the same stream (or
+ * ordered behind it) reads them safely. The keys are those of apds_dev_l2_topk over the view's rows bit for bit, in either mode; a
+ * selection of 0 or 1 rows is served by the exact kernel (screen_ready = 0), from 2 rows on the screen is ready. One thread at a time
+ * per view, as for selects. APDS_ERR_BAD_ARG on a view of a byte table. */
+int apds_db_view_l2_train(void* view, void** set);
 /* Ids and deletes: the two access paths of the reference's KeypointDatabase trait that take an id, read_keypoint_from_id
  * (keypointdb.rs:28-36) and delete_keypoint (keypointdb.rs:92-97), and the deletes by image, level of detail and region that replacing
  * imagery needs. Every row has an id that behaves like the reference's SERIAL column: the first row ever inserted gets 1, every insert
@@ -519,6 +551,8 @@ int apds_db_ids(void* db, void** ids_dev);
  * first 61 bytes of its descriptor, its image id and its current row. Any output may be NULL. An id no row has - deleted, never given,
  * below 1 - is APDS_ERR_OUT_OF_RANGE (the reference returns Err(NotFound)). */
 int apds_db_read_keypoint_from_id(void* db, int id, apds_keypoint* kp, uint8_t* desc61, int* image_id, int64_t* row);
+/* The same on a float table: desc64f receives the row's 64 floats. */
+int apds_db_read_keypoint_from_id_float(void* db, int id, apds_keypoint* kp, float* desc64f, int* image_id, int64_t* row);
 /* Deletes every row apds_db_select qualifies for the same mode, value and box (mode 0: an image's keypoints; 1: a level of detail; 2: a
  * region at a level of detail, floor(start) <= v <= ceil(end)) - all of them: no 262143-row limit, no ordering. *n_deleted (may be
  * NULL) = the exact number of rows removed. */
@@ -697,7 +731,13 @@ int apds_pipeline_poll_pose(void* pipe, apds_frame_result* result, apds_frame_po
  * (anything else is APDS_ERR_BAD_ARG) and requires the table's world points to be current (APDS_ERR_BAD_ARG otherwise).
  * A frame whose view has fewer than two rows gets the status the one-call matcher gives for such a train set (APDS_ERR_ASSERT), no
  * matches and no homography; the pipeline goes on. apds_pipeline_submit on a table pipeline and apds_pipeline_submit_select on any
- * other are APDS_ERR_BAD_ARG; so are a NULL sel and a mode outside 0..2, before any device work. */
+ * other are APDS_ERR_BAD_ARG; so are a NULL sel and a mode outside 0..2, before any device work.
+ * On a FLOAT table (apds_db_create_float) this makes a float pipeline, as apds_pipeline_create_float does for a fixed train set: the
+ * workers extract M-SURF rows, the matcher is APDS_PIPELINE_MATCH_L2_RATIO for life (apds_pipeline_set_matcher with anything else is
+ * APDS_ERR_BAD_ARG), and each frame's train set is its slot's view through apds_db_view_l2_train: the screen's train side comes out
+ * of the select's own gather. Everything else - the selections, the status of a view of fewer than two rows, pose from the view's world
+ * points - is the byte table's. For both kinds, keeping inserts and deletes away from the table while a pipeline holds it is the CALLER'S
+ * obligation: the library does not check it. */
 typedef struct apds_db_selection {
     int mode, value;                         /* apds_db_select's: 0 image id, 1 level of detail, 2 level of detail and bounding box */
     float x_start, y_start, x_end, y_end;    /* mode 2: floor(start) <= v <= ceil(end) */

@@ -7,6 +7,8 @@
                 queries = the descriptors of shifted views of the first tiles
   screen128     the dim-128 screen through apds_dev_l2_topk_ex at --q128 x 1 000 000 x 128 (the shape of profiles/r04), before / after
   pipeline      frames/s of StreamedFramePipeline(matcher="l2") beside the Hamming pipeline's, same frames (4096 x 4096), same session
+  pipeline-table  the same frames and rows with the rows in a float keypoint table and a region select per frame (262143 rows of the view):
+                what selecting per frame costs beside the fixed-train-set figure of `pipeline`
 
 (The committed match_synth_nc4.jsonl is the same probe on a build that also instantiated four column blocks per wave at dim 64, picked
 per process; that variant lost and is gone, so every record made now says nc64 = 3.)"""
@@ -157,9 +159,47 @@ def pipeline(args):
         del db, xy
 
 
+def pipeline_table(args):
+    """the float pipeline's frame and rows, the rows in a FLOAT keypoint table and the train set selected per frame: a region select that
+    qualifies every row and returns the 262143 best (the frames' own rows among them: the random rows' responses lie below theirs)"""
+    fe, synth, fd = pkg.feature_extraction, pkg.synth, pkg.feature_database
+    T = args.tile
+    tiles = [synth.make_tile(T, T, frame_index=i) for i in range(2)]
+    frames = [torch.from_numpy(t).to(DEV) for t in tiles]
+    ex = [fe.akaze_keypoint_descriptor_extraction(np.roll(t, (19, 23), axis=(0, 1)).copy(), descriptor="kaze") for t in tiles]
+    kps_real = np.concatenate([np.asarray(e.keypoints) for e in ex])
+    n_real = len(kps_real)
+    g = torch.Generator(device=DEV)
+    g.manual_seed(11)
+    kps = torch.zeros((NT, 7), dtype=torch.float32, device=DEV)
+    kps[:, 0:2] = torch.rand((NT, 2), device=DEV, generator=g) * (T - 1)
+    kps[:, 4] = torch.rand(NT, device=DEV, generator=g) * 1e-9
+    kps[:n_real] = torch.from_numpy(kps_real.view(np.float32).reshape(n_real, 7)).to(DEV)
+    db = unit_rows(NT, 64, g)
+    db[:n_real] = torch.from_numpy(np.concatenate([np.asarray(e.descriptors, np.float32) for e in ex])).to(DEV)
+    torch.cuda.synchronize()
+    table = fd.KeypointTable(NT, descriptor="kaze")
+    table.create_keypoints_device(kps.data_ptr(), db.data_ptr(), NT, 1, 0)
+    del db, kps
+    sel = pl.StreamedFramePipeline.selection(2, 0, (0.0, 0.0, float(T), float(T)))
+    pipe = pl.StreamedFramePipeline.from_table(table, per_frame_view=True)
+    try:
+        pipe.run(frames, args.warmup + 1, filter_strength=args.fs, selections=[sel])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res, _ = pipe.run(frames, args.frames, filter_strength=args.fs, selections=[sel])
+        dt = time.perf_counter() - t0
+    finally:
+        pipe.close()
+        table.close()
+    emit(args, probe="pipeline-table", matcher="l2", l2_mode="screen", train_set="per-frame region select of a float table: 262143 of %d rows" % NT, tile=T,
+         db_rows=NT, view_rows=(1 << 18) - 1, frames=args.frames, frames_per_s=args.frames / dt, n_keypoints=res[0]["n_keypoints"], n_matches=res[0]["n_matches"],
+         n_inliers=res[0]["n_inliers"], filter_strength=args.fs)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", nargs="+", choices=["match-synth", "match-real", "screen128", "pipeline"])
+    ap.add_argument("what", nargs="+", choices=["match-synth", "match-real", "screen128", "pipeline", "pipeline-table"])
     ap.add_argument("--out", default=None)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
@@ -172,7 +212,7 @@ def main():
     args = ap.parse_args()
     torch.cuda.set_stream(torch.cuda.Stream(DEV))
     for w in args.what:
-        {"match-synth": match_synth, "match-real": match_real, "screen128": screen128, "pipeline": pipeline}[w](args)
+        {"match-synth": match_synth, "match-real": match_real, "screen128": screen128, "pipeline": pipeline, "pipeline-table": pipeline_table}[w](args)
 
 
 if __name__ == "__main__":
