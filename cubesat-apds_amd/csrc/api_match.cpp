@@ -284,7 +284,7 @@ int apds_dev_cross_check(const void* train_best, int64_t n_train, int nq, void* 
 
 // apds_get_bruteforce_matches on device rows: the roles-swapped top-1 (every train row's nearest query, ties to the lower query), then per
 // query the closest train row that chose it (ties to the lower train row), in query order. The streamed pipeline's cross-check mode runs
-// the same two steps on two stage threads (csrc/pipeline.cpp).
+// the same two steps on two stage threads (csrc/pipeline_match.cpp, csrc/pipeline_stages.cpp).
 int apds_dev_crosscheck_match(const void* q, int nq, const void* t, int64_t nt, uint32_t index_base, void* out_matches, int* n_matches, void* stream) {
     APDS_RANGE("apds_dev_crosscheck_match");
     return guarded([&] {

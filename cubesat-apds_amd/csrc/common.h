@@ -116,6 +116,22 @@ unsigned stream_event_flags();   // flags for events that only order GPU streams
 
 inline hipStream_t pick_stream(void* s) { return s ? static_cast<hipStream_t>(s) : ctx().stream; }
 
+// hipSetDevice(a handle's device) for the length of a destroy or configure path, then the caller's device again: a thread bound to GPU A
+// may destroy a handle living on GPU B (a thread-per-GPU host; a finaliser running on an arbitrary thread) and must keep launching on A
+// afterwards - its thread context (stream, workspace) belongs there.
+struct DeviceGuard {
+    int previous = -1;
+    explicit DeviceGuard(int device) {
+        if (hipGetDevice(&previous) != hipSuccess) previous = -1;
+        (void)hipSetDevice(device);
+    }
+    ~DeviceGuard() {
+        if (previous >= 0) (void)hipSetDevice(previous);
+    }
+    DeviceGuard(const DeviceGuard&) = delete;
+    DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+
 // The frame of an entry that RETURNS WITH KERNELS QUEUED on s that use the thread's workspace: the workspace is reset with s ordered behind
 // the thread's previous tail, and what the entry has queued when it leaves - with a result or with an error - is the thread's new tail
 // (one event record per call). Entries that synchronise s before they return need ws_reset(s) only.

@@ -690,14 +690,11 @@ void* hm_train_create(const void* rows64, long long n, hipStream_t s) {
 void hm_train_destroy(void* h) {
     HmTrain* t = static_cast<HmTrain*>(h);
     if (!t) return;
-    int previous = -1;
-    if (hipGetDevice(&previous) != hipSuccess) previous = -1;
-    (void)hipSetDevice(t->device);
+    DeviceGuard on(t->device);
     (void)hipDeviceSynchronize();
     if (t->rows) (void)hipFree(t->rows);
     if (t->pc) (void)hipFree(t->pc);
     delete t;
-    if (previous >= 0) (void)hipSetDevice(previous);
 }
 
 // Top-k (1 <= k <= 8) of nq 64-byte query rows against expanded train rows (t4 / tp: hm_expand_device's output, or an HmTrain's).

@@ -499,12 +499,9 @@ L2Train* l2_train_create(const float* t, long long nt, int dim, uint32_t index_b
 
 void l2_train_destroy(L2Train* set) {
     if (!set) return;
-    int previous = -1;
-    if (hipGetDevice(&previous) != hipSuccess) previous = -1;
-    (void)hipSetDevice(set->device);
+    DeviceGuard on(set->device);
     for (void* p : {(void*)set->norms, (void*)set->rows_bf, (void*)set->tmax_bits})
         if (p) (void)hipFree(p);
-    if (previous >= 0 && previous != set->device) (void)hipSetDevice(previous);
     delete set;
 }
 

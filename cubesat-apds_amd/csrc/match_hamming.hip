@@ -694,13 +694,10 @@ void* topk_split_create() {
 void topk_split_destroy(void* h) {
     TopkSplitState* st = static_cast<TopkSplitState*>(h);
     if (!st) return;
-    int previous = -1;   // the caller's device is put back: its thread context (stream, workspace) belongs there
-    if (hipGetDevice(&previous) != hipSuccess) previous = -1;
-    (void)hipSetDevice(st->device);
+    DeviceGuard on(st->device);
     (void)hipDeviceSynchronize();
     if (st->buf) (void)hipFree(st->buf);
     delete st;
-    if (previous >= 0) (void)hipSetDevice(previous);
 }
 void topk_split_prepass(void* h, const void* q, int nq, const void* t, long long nt, uint32_t index_base, int k, hipStream_t s) {
     APDS_REQUIRE(h, APDS_ERR_BAD_ARG, "null scan state");

@@ -28,544 +28,67 @@
 // through HIP events, results leave in frame order. The reference only chains these steps inside unit tests
 // (feature_extraction/src/lib.rs:197-249) and never calls find_homography_mat on the result; this is the composed path the
 // north-star metric (frames/s) is measured on. The Python class cubesat-apds_amd/pipeline.py:StreamedFramePipeline is a front of this.
-#include <chrono>
 #include <climits>
 #include <cmath>
-#include <condition_variable>
 #include <cstring>
-#include <deque>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <thread>
 
-#include "config.h"
-#include "kernels.h"
+#include "pipeline.h"
 
 using namespace apds;
 
-namespace {
-
-// a blocking queue; close() wakes every waiter (pop then returns false once the queue is empty)
-template <class T>
-class Chan {
-    std::mutex m;
-    std::condition_variable cv;
-    std::deque<T> q;
-    bool closed = false;
-
-public:
-    void push(T v) {
-        {
-            std::lock_guard<std::mutex> g(m);
-            q.push_back(std::move(v));
-        }
-        cv.notify_one();
-    }
-    bool pop(T& out) {
-        std::unique_lock<std::mutex> g(m);
-        cv.wait(g, [&] { return !q.empty() || closed; });
-        if (q.empty()) return false;
-        out = std::move(q.front());
-        q.pop_front();
-        return true;
-    }
-    void close() {
-        {
-            std::lock_guard<std::mutex> g(m);
-            closed = true;
-        }
-        cv.notify_all();
-    }
-};
-
-struct StageError {
-    int code;
-    std::string msg;
-};
-[[noreturn]] void stage_fail(int rc) { throw StageError{rc, apds_last_error()}; }
-#define PIPE_OK(call)                       \
-    do {                                    \
-        const int rc_ = (call);             \
-        if (rc_ != APDS_OK) stage_fail(rc_); \
-    } while (0)
-
-struct Slot {
-    // device buffers of one frame in flight
-    apds_keypoint* kps = nullptr;
-    uint8_t* desc = nullptr;
-    uint64_t* keys = nullptr;
-    apds_dmatch* matches = nullptr;
-    float *p1 = nullptr, *p2 = nullptr;
-    uint8_t* mask = nullptr;
-    uint8_t* frame_dev = nullptr;   // staging buffer of a host frame
-    size_t frame_dev_bytes = 0;
-    hipEvent_t ev_extract = nullptr, ev_pre = nullptr, ev_scan = nullptr, ev_match = nullptr;
-    hipEvent_t ev_mstart = nullptr, ev_mend = nullptr;   // (timing enabled) the match stream's idle gaps: starvation watch
-    void* topk_state = nullptr;   // split scan (one GPU)
-    uint64_t* train_best = nullptr;   // cross-check mode (apds_pipeline_set_matcher): every train row's nearest query of this slot's frame
-    void* shard_slot = nullptr;   // exchange slot (sharded DB)
-    // a table pipeline (apds_pipeline_create_table): this slot's view of the table, the frame's selection and what it gave. The later
-    // stages read the train side from here (the view's pointers never change; its contents hold until the slot's next frame).
-    void* view = nullptr;
-    apds_db_selection sel{};
-    const void* view_rows64 = nullptr;
-    const apds_keypoint* view_kps = nullptr;
-    const void* view_xyz = nullptr;
-    void* view_l2_train = nullptr;   // a float table: the view's train side (apds_db_view_l2_train), contents those of the frame's select
-    int n_view = 0;
-    int owner = 0;
-    // the job
-    const void* src = nullptr;
-    size_t stride = 0;
-    bool on_device = false;
-    int64_t index = 0;
-    int K = 0, status = APDS_OK;
-    std::string error;
-    std::vector<int> counts;
-    // the pose stage (apds_pipeline_enable_pose): the frame's 2D-3D pairs, and the homography stage's result handed on with the slot
-    float *pose_img = nullptr, *pose_obj = nullptr;
-    hipEvent_t ev_homography = nullptr;
-    apds_frame_result res{};
-    std::string res_why;
-};
-
-struct Pipeline {
-    apds_pipeline_params p{};
-    int device = 0;
-    const void* db_rows = nullptr;
-    void* db_expanded = nullptr;   // the train rows as matrix-core operands (hm_train_create), made once: the DB is resident for the pipeline's life
-    int64_t n_rows = 0;
-    uint32_t index_base = 0;
-    void* shard = nullptr;
-    int world = 1;
-    const apds_keypoint* db_kps = nullptr;
-    int64_t n_db_total = 0;
-    void* table = nullptr;   // the train set is selected per frame from this keypoint table (borrowed)
-    int cap = 0, E = 2;
-    bool split = true, adaptive_cap = true, own_match_stream = true;
-    double extract_delay_s = 0;
-
-    std::vector<std::unique_ptr<Slot>> slots;
-    std::vector<std::unique_ptr<Chan<Slot*>>> q_free, q_jobs, q_ext;
-    Chan<int> q_any;          // which worker finished a frame (arrival order; one GPU)
-    Chan<Slot*> q_homography, q_pose;
-    std::vector<std::thread> threads;
-    hipStream_t st_extract[8] = {}, st_match = nullptr, st_pre = nullptr, st_merge = nullptr, st_homography = nullptr, st_gather = nullptr, st_counts = nullptr;
-    hipStream_t st_pose = nullptr;
-    std::atomic<bool> pose_on{false};   // set once, before the first submit
-    std::atomic<int> matcher{APDS_PIPELINE_MATCH_RATIO};   // set before the first submit (apds_pipeline_set_matcher)
-    bool float_rows = false;        // apds_pipeline_create_float: M-SURF rows (256 bytes), the L2 matcher (matcher == APDS_PIPELINE_MATCH_L2_RATIO for life)
-    L2Train* l2_train = nullptr;    // ... its resident train set, made at create
-    float* db_plain_pc = nullptr;   // cross-check mode on the expanded copy: the train rows' popcounts as the swapped scan's column side takes them
-    int view_capacity = 0;
-    apds_pipeline_pose_params pose{};
-    std::atomic<bool> lens_on{false};   // set before the first submit (apds_pipeline_set_lens), and only for a lens that distorts
-    lens::Lens lens{};
-    int lens_iters = lens::DEFAULT_ITERS;
-
-    std::mutex m;   // results, counters, errors
-    std::condition_variable cv;
-    std::map<int64_t, apds_frame_result> results;
-    std::map<int64_t, std::string> result_errors;
-    std::map<int64_t, apds_frame_pose> poses;
-    int64_t next_submit = 0, next_result = 0, done = 0;
-    bool failed = false, closing = false;
-    int fail_code = 0;
-    std::string fail_msg;
-    // statistics (timing enabled)
-    std::map<std::string, std::pair<double, int>> timers;
-    std::vector<float> gaps;
-    int cap_bytes = 0, cap_frame = -1;
-    std::vector<float> cap_gaps;   // the six gaps that triggered the cap
-    int harvest_acks = 0;
-    std::mutex submit_m;   // one submitter at a time keeps frame numbers and slot hand-out in step
-
-    void fail(int code, const std::string& msg) {
-        {
-            std::lock_guard<std::mutex> g(m);
-            if (!failed) {
-                failed = true;
-                fail_code = code;
-                fail_msg = msg;
-            }
-        }
-        close_all();
-        cv.notify_all();
-    }
-    void close_all() {
-        for (auto& q : q_free) q->close();
-        for (auto& q : q_jobs) q->close();
-        for (auto& q : q_ext) q->close();
-        q_any.close();
-        q_homography.close();
-        q_pose.close();
-    }
-    void add_timer(const char* name, double ms, int n) {
+void Pipeline::fail(int code, const std::string& msg) {
+    {
         std::lock_guard<std::mutex> g(m);
-        auto& t = timers[name];
+        if (!failed) {
+            failed = true;
+            fail_code = code;
+            fail_msg = msg;
+        }
+    }
+    close_all();
+    cv.notify_all();
+}
+void Pipeline::close_all() {
+    for (auto& q : q_free) q->close();
+    for (auto& q : q_jobs) q->close();
+    for (auto& q : q_ext) q->close();
+    q_any.close();
+    q_homography.close();
+    q_pose.close();
+}
+void Pipeline::collect(std::initializer_list<const char*> names) {
+    if (!p.timing) return;
+    for (const char* n : names) {
+        float ms = 0;
+        int k = 0;
+        if (apds_dev_last_kernel_ms(n, &ms, &k) != APDS_OK || k <= 0) continue;
+        std::lock_guard<std::mutex> g(m);
+        auto& t = timers[n];
         t.first += ms;
-        t.second += n;
+        t.second += k;
     }
-    // this worker thread's event timers of the named kernels -> the pipeline's totals (the events were recorded on the launch streams)
-    void collect(std::initializer_list<const char*> names) {
-        if (!p.timing) return;
-        for (const char* n : names) {
-            float ms = 0;
-            int k = 0;
-            if (apds_dev_last_kernel_ms(n, &ms, &k) == APDS_OK && k > 0) add_timer(n, ms, k);
-        }
+}
+void Pipeline::harvest(std::initializer_list<const char*> names) {
+    collect(names);
+    {
+        std::lock_guard<std::mutex> g(m);
+        harvest_acks++;
     }
+    cv.notify_all();
+}
+void Pipeline::finish(Slot* s, const apds_frame_result& r, const std::string& why, const apds_frame_pose* fp) {
+    {
+        std::lock_guard<std::mutex> g(m);
+        results[s->index] = r;
+        if (fp) poses[s->index] = *fp;
+        if (r.status != APDS_OK) result_errors[s->index] = why;
+        done++;
+    }
+    cv.notify_all();
+    q_free[(size_t)s->owner]->push(s);
+}
 
-    void harvest(std::initializer_list<const char*> names) {
-        collect(names);
-        {
-            std::lock_guard<std::mutex> g(m);
-            harvest_acks++;
-        }
-        cv.notify_all();
-    }
-
-    template <class F>
-    void worker(const char* what, F body) {
-        try {
-            PIPE_OK(apds_set_device(device));
-            PIPE_OK(apds_dev_timing_enable(p.timing ? 1 : 0));
-            body();
-        } catch (const StageError& e) {
-            fail(e.code, std::string(what) + ": " + e.msg);
-        } catch (const Error& e) {
-            fail(e.code, std::string(what) + ": " + e.msg);
-        } catch (const std::exception& e) {
-            fail(APDS_ERR_INTERNAL, std::string(what) + ": " + e.what());
-        }
-        (void)apds_dev_timing_enable(0);
-        (void)apds_thread_release();   // this worker's stream + workspace go back to the process-wide cache
-    }
-
-    void finish(Slot* s, const apds_frame_result& r, const std::string& why, const apds_frame_pose* fp = nullptr) {
-        {
-            std::lock_guard<std::mutex> g(m);
-            results[s->index] = r;
-            if (fp) poses[s->index] = *fp;
-            if (r.status != APDS_OK) result_errors[s->index] = why;
-            done++;
-        }
-        cv.notify_all();
-        q_free[(size_t)s->owner]->push(s);
-    }
-
-    // ---- stage 1: extraction ----------------------------------------------------------------------------------------------------------
-    void extract_worker(int e) {
-        hipStream_t st = st_extract[e];
-        Slot* s = nullptr;
-        while (q_jobs[(size_t)e]->pop(s)) {
-            if (!s) {   // apds_pipeline_stats on the idle pipeline: this thread's event timers -> the totals
-                harvest({"akaze_extract"});
-                continue;
-            }
-            const void* img = s->src;
-            s->status = APDS_OK;
-            s->K = 0;
-            if (!s->on_device) {
-                // a host frame: uploaded on THIS worker's stream in front of the extraction, into the slot's own buffer; the other
-                // extraction worker and the match run meanwhile, so the PCIe copy is hidden (pinned memory makes it a true async copy)
-                const size_t bytes = s->stride * (size_t)p.rows;
-                if (s->frame_dev_bytes < bytes) {
-                    if (s->frame_dev) HIP_CHECK(hipFree(s->frame_dev));
-                    s->frame_dev = nullptr;
-                    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->frame_dev), bytes));
-                    s->frame_dev_bytes = bytes;
-                }
-                HIP_CHECK(hipMemcpyAsync(s->frame_dev, s->src, bytes, hipMemcpyHostToDevice, st));
-                img = s->frame_dev;
-            }
-            int n = 0;
-            const int rc = float_rows ? apds_dev_akaze_extract_float(img, p.rows, p.cols, p.channels, s->stride, nullptr, 0, 0, cap, s->kps, s->desc, cap, &n, st)
-                                      : apds_dev_akaze_extract(img, p.rows, p.cols, p.channels, s->stride, cap, s->kps, s->desc, cap, &n, st);
-            if (rc != APDS_OK) {   // this frame fails, the pipeline goes on (a sharded run contributes zero queries for it)
-                s->status = rc;
-                s->error = apds_last_error();
-                n = 0;
-            }
-            s->K = n;
-            HIP_CHECK(hipEventRecord(s->ev_extract, st));
-            if (extract_delay_s > 0) std::this_thread::sleep_for(std::chrono::duration<double>(extract_delay_s));   // test hook: a box on which extraction cannot keep up
-            q_ext[(size_t)e]->push(s);
-            if (world == 1) q_any.push(e);
-        }
-        collect({"akaze_extract"});
-    }
-
-    // ---- stage 2: match (one GPU) ------------------------------------------------------------------------------------------------------
-    // Starvation watch: the match stream should never wait for a frame. On some boxes the short extraction kernels are dispatched so late
-    // under the match kernel, which owns every wave slot, that extraction paces the pipeline. The gap on the match stream between one
-    // frame's last match kernel and the next frame's first is measured with events; if three of six consecutive gaps exceed 4 ms (healthy:
-    // 0.01 / 1.2 ms alternating) the main scan's occupancy is capped at two workgroups per CU (apds_dev_match_lds_cap), which leaves
-    // wave slots for the other stages at ~1.5 % of match throughput. The cap is scoped to THIS thread's scan launches (set_thread_scan_cap):
-    // other matchers of the process are not touched and nothing has to be restored.
-    void match_worker() {
-        bool watch = adaptive_cap;
-        if (p.match_lds_cap > 0 && !float_rows) set_thread_scan_cap(p.match_lds_cap), watch = false;   // the caller asked for a cap from the first frame on
-        std::deque<std::pair<Slot*, Slot*>> pending;   // (previous frame, this frame): gap = prev.ev_mend -> this.ev_mstart
-        std::vector<float> recent;
-        Slot* prev = nullptr;
-        int e = 0;
-        int64_t seen = 0;
-        while (q_any.pop(e)) {
-            // cross-check mode: one roles-swapped top-1 per frame (every train row's nearest query) on the single-stream branch; the split
-            // scan, the threshold pre-pass and the starvation watch belong to the ratio matcher
-            const bool crosscheck = matcher == APDS_PIPELINE_MATCH_CROSSCHECK;
-            if (e < 0) {
-                harvest({"hamming_topk", "hamming_topk_sample"});
-                continue;
-            }
-            // One GPU: nothing requires frame order on the match stream (results are stored by frame index), so frames are matched first come,
-            // first served: one of the two extraction workers tends to finish just after a match ends, and in frame order the match stream
-            // then waited ~1.2 ms for every second frame
-            Slot* s = nullptr;
-            if (!q_ext[(size_t)e]->pop(s)) break;
-            const int K = s->K;
-            if (table) {
-                // the frame's train set first: the select needs nothing from the extraction. Its one synchronisation waits for the previous
-                // frame's scan on this stream; the cut, sort and gather it queues run in front of this frame's scan.
-                s->n_view = 0;
-                PIPE_OK(apds_db_view_select(s->view, s->sel.mode, s->sel.value, s->sel.x_start, s->sel.y_start, s->sel.x_end, s->sel.y_end, pose_on ? 1 : 0,
-                                            st_match, &s->n_view));
-                void* xyz = nullptr;
-                PIPE_OK(apds_db_view_pointers(s->view, nullptr, nullptr, nullptr, nullptr, &xyz, nullptr));
-                s->view_xyz = xyz;
-                HIP_CHECK(hipStreamWaitEvent(st_match, s->ev_extract, 0));
-                HIP_CHECK(hipEventRecord(s->ev_mstart, st_match));
-                if (s->n_view < 2) {   // what a train set of that size is to apds_pipeline_create
-                    if (s->status == APDS_OK) {
-                        s->status = APDS_ERR_ASSERT;
-                        s->error = "the frame's selection has fewer than two rows: a train set of at least two rows is required";
-                    }
-                } else if (K > 0 && float_rows) {   // the train side the select's gather has just queued on this stream
-                    PIPE_OK(apds_dev_l2_train_top2(s->view_l2_train, s->desc, K, APDS_L2_SCREEN, s->keys, st_match, nullptr, nullptr));
-                } else if (K > 0 && crosscheck) {
-                    PIPE_OK(apds_dev_hamming_topk(s->view_rows64, s->n_view, s->desc, K, 0, 1, s->train_best, st_match));
-                } else if (K > 0) {
-                    PIPE_OK(apds_dev_hamming_topk(s->desc, K, s->view_rows64, s->n_view, 0, 2, s->keys, st_match));
-                }
-                HIP_CHECK(hipEventRecord(s->ev_match, st_match));
-                HIP_CHECK(hipEventRecord(s->ev_mend, st_match));
-            } else if (K > 0 && split && !crosscheck) {
-                HIP_CHECK(hipStreamWaitEvent(st_pre, s->ev_extract, 0));   // threshold pre-pass: beside the previous frame's main scan
-                PIPE_OK(apds_dev_topk_prepass(s->topk_state, s->desc, K, db_rows, n_rows, index_base, 2, st_pre));
-                HIP_CHECK(hipEventRecord(s->ev_pre, st_pre));
-                HIP_CHECK(hipStreamWaitEvent(st_match, s->ev_pre, 0));
-                HIP_CHECK(hipEventRecord(s->ev_mstart, st_match));
-                PIPE_OK(apds_dev_topk_scan(s->topk_state, s->desc, db_rows, st_match));
-                HIP_CHECK(hipEventRecord(s->ev_scan, st_match));
-                HIP_CHECK(hipEventRecord(s->ev_mend, st_match));
-                HIP_CHECK(hipStreamWaitEvent(st_merge, s->ev_scan, 0));    // record merge: beside the next frame's main scan
-                PIPE_OK(apds_dev_topk_merge(s->topk_state, index_base, s->keys, st_merge));
-                HIP_CHECK(hipEventRecord(s->ev_match, st_merge));
-            } else {
-                HIP_CHECK(hipStreamWaitEvent(st_match, s->ev_extract, 0));
-                HIP_CHECK(hipEventRecord(s->ev_mstart, st_match));
-                if (K > 0 && float_rows) {   // the resident L2 train set, screen mode: 3.1 ms against 16.0 ms exact on M-SURF rows (the screen reads its candidate counts back: this thread waits for the frame's passes)
-                    PIPE_OK(apds_dev_l2_train_top2(l2_train, s->desc, K, APDS_L2_SCREEN, s->keys, st_match, nullptr, nullptr));
-                } else if (K > 0 && crosscheck && db_expanded) {   // the resident expanded copy as the searching side: only the frame's rows are expanded
-                    PIPE_OK(guarded([&] {
-                        QueuedWorkspaceCall call(st_match);
-                        hamming_mfma_swapped_top1_device(s->desc, K, db_expanded, db_plain_pc, s->train_best, st_match);
-                    }));
-                } else if (K > 0 && crosscheck) {   // (vector-ALU matcher: the swapped scan directly)
-                    PIPE_OK(apds_dev_hamming_topk(db_rows, (int)n_rows, s->desc, K, 0, 1, s->train_best, st_match));
-                } else if (K > 0 && db_expanded) {   // the matrix-core matcher on the DB's expanded copy
-                    PIPE_OK(guarded([&] {
-                        QueuedWorkspaceCall call(st_match);   // (as apds_dev_hamming_topk does: the scan's scratch is this thread's workspace, and it is queued on return)
-                        hamming_mfma_topk_train_device(s->desc, K, db_expanded, index_base, 2, static_cast<uint64_t*>(s->keys), st_match);
-                    }));
-                } else if (K > 0) {
-                    PIPE_OK(apds_dev_hamming_topk(s->desc, K, db_rows, n_rows, index_base, 2, s->keys, st_match));
-                }
-                HIP_CHECK(hipEventRecord(s->ev_match, st_match));
-                HIP_CHECK(hipEventRecord(s->ev_mend, st_match));
-            }
-            if (watch && !crosscheck) {
-                if (prev && seen >= 4) pending.emplace_back(prev, s);   // the first frames are the pipeline filling up
-                while (!pending.empty() && hipEventQuery(pending.front().second->ev_mstart) == hipSuccess) {
-                    float g = -1;
-                    // (a slot that was re-used in the meantime re-recorded its events: the sample is skipped)
-                    if (hipEventElapsedTime(&g, pending.front().first->ev_mend, pending.front().second->ev_mstart) != hipSuccess) (void)hipGetLastError(), g = -1;
-                    pending.pop_front();
-                    if (g >= 0 && g < 1000) {
-                        recent.push_back(g);
-                        std::lock_guard<std::mutex> lk(m);
-                        gaps.push_back(g);
-                    }
-                }
-                (void)hipGetLastError();   // hipEventQuery's hipErrorNotReady is not an error
-                int late = 0;
-                for (size_t i = recent.size() >= 6 ? recent.size() - 6 : 0; i < recent.size(); i++) late += recent[i] > 4.0f;
-                if (recent.size() >= 6 && late >= 3 && cap_bytes == 0) {
-                    set_thread_scan_cap(55000);
-                    std::lock_guard<std::mutex> lk(m);
-                    cap_bytes = 55000;
-                    cap_frame = (int)s->index;
-                    for (size_t i = recent.size() - 6; i < recent.size(); i++) cap_gaps.push_back(recent[i]);
-                    watch = false;
-                }
-            }
-            prev = s;
-            seen++;
-            q_homography.push(s);
-        }
-        collect({"hamming_topk", "hamming_topk_sample"});
-        q_homography.close();
-    }
-
-    // ---- stage 2: match (row-sharded DB) -----------------------------------------------------------------------------------------------
-    // This thread issues ALL collectives of the pipeline, in frame order, the same order on every rank: counts(i) [a tiny all-gather on its
-    // own stream; the only host synchronisation, and frame i-1's scan is already queued behind it], gather(i) [its own stream, after that
-    // frame's extraction] BEFORE exchange(i-1) [match stream, after scan(i-1)]: the query all-gather of a frame travels under the previous
-    // frame's scan. Deferring exchange(i-1) until frame i has arrived is only safe when frame i is certain to arrive on EVERY rank, and the
-    // choice must be the same everywhere (the collectives' order is at stake): each rank adds to its count a flag "frame i+1 is already
-    // submitted here", and frame i's exchange is deferred iff every rank set it. A host that streams (submits ahead of the results) gets
-    // the overlap on all frames but its last; a host that submits one frame and waits gets that frame's result without a successor.
-    void sharded_match_worker() {
-        constexpr int NEXT_FLAG = 1 << 30;
-        Slot* prev = nullptr;
-        for (int64_t i = 0;; i++) {
-            Slot* s = nullptr;
-            if (!q_ext[(size_t)(i % E)]->pop(s)) break;
-            if (!s) {   // apds_pipeline_stats on the idle pipeline (no frame is between gather and exchange)
-                harvest({"hamming_topk", "hamming_topk_sample"});
-                i--;
-                continue;
-            }
-            bool next_here;
-            {
-                std::lock_guard<std::mutex> g(m);
-                next_here = next_submit > i + 1;
-            }
-            s->counts.assign((size_t)world, 0);
-            PIPE_OK(apds_shard_counts(shard, s->K | (next_here ? NEXT_FLAG : 0), s->counts.data(), st_counts));
-            bool next_everywhere = true;
-            for (int& c : s->counts) {
-                next_everywhere = next_everywhere && (c & NEXT_FLAG);
-                c &= NEXT_FLAG - 1;
-            }
-            HIP_CHECK(hipStreamWaitEvent(st_gather, s->ev_extract, 0));
-            PIPE_OK(apds_shard_gather(shard, s->shard_slot, s->K ? s->desc : nullptr, s->K, s->counts.data(), st_gather));
-            auto finish_exchange = [&](Slot* f) {
-                PIPE_OK(apds_shard_exchange_merge(shard, f->shard_slot, 2, f->keys, st_match));
-                HIP_CHECK(hipEventRecord(f->ev_match, st_match));
-                q_homography.push(f);
-            };
-            if (prev) finish_exchange(prev);
-            prev = nullptr;
-            PIPE_OK(apds_shard_scan(shard, s->shard_slot, 2, st_match));
-            if (next_everywhere) prev = s;   // frame i+1 is on its way on every rank: its gather goes out first
-            else finish_exchange(s);
-        }
-        collect({"hamming_topk", "hamming_topk_sample"});
-        q_homography.close();
-    }
-
-    // ---- stage 3: ratio filter, matched points, homography ---------------------------------------------------------------------------
-    void homography_worker() {
-        hipStream_t st = st_homography;
-        Slot* s = nullptr;
-        int* count_dev = nullptr;
-        HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&count_dev), 256));
-        while (q_homography.pop(s)) {
-            if (!s) {
-                harvest({"ransac_score"});
-                continue;
-            }
-            apds_frame_result r{};
-            r.frame = s->index;
-            r.status = s->status;
-            r.n_keypoints = s->K;
-            std::string why = s->status != APDS_OK ? s->error : std::string();
-            try {
-                HIP_CHECK(hipStreamWaitEvent(st, s->ev_match, 0));
-                int M = 0;
-                const bool matched = s->K > 0 && !(table && s->n_view < 2);
-                const apds_keypoint* train_kps = table ? s->view_kps : db_kps;
-                const int n_train = table ? s->n_view : (int)n_db_total;
-                if (matched && matcher == APDS_PIPELINE_MATCH_CROSSCHECK) {
-                    // per query the closest train row that chose it, in query order; train_idx = row + index_base (a view: its position)
-                    PIPE_OK(guarded([&] {
-                        ctx().ws_reset(st);
-                        M = cross_check_base_device(s->train_best, table ? (long long)s->n_view : (long long)n_rows, s->K, table ? 0u : index_base, s->matches, st);
-                    }));
-                } else if (matched && float_rows) {
-                    PIPE_OK(apds_dev_l2_ratio_filter(s->keys, s->K, 2, p.filter_strength, s->matches, &M, st));
-                } else if (matched) {
-                    PIPE_OK(apds_dev_ratio_filter(s->keys, s->K, 2, p.filter_strength, s->matches, &M, st));
-                }
-                r.n_matches = M;
-                if (M >= 4) {
-                    // query_idx -> this frame's keypoints, train_idx -> the DB rows' keypoints (the intended gather: lib.rs:161-180 has two bugs)
-                    PIPE_OK(apds_dev_points_from_matches(s->kps, s->K, train_kps, n_train, s->matches, M, 0, s->p1, s->p2, st));
-                    // the frame side of the matches to ideal pixels (the train side is map geometry): one launch on this stream, no workspace
-                    if (lens_on) PIPE_OK(guarded([&] { lens_undistort_points_f32_device(s->p1, M, 2 * sizeof(float), lens, lens_iters, st); }));
-                    const int rc = apds_dev_find_homography(s->p1, s->p2, M, p.homography_method, p.reproj_threshold, p.max_iters, p.confidence, r.H, s->mask, st);
-                    if (rc == APDS_OK) {
-                        r.homography_found = 1;
-                        r.n_inliers = count_nonzero_device(s->mask, M, count_dev, st);
-                    } else if (rc != APDS_ERR_EMPTY) {
-                        stage_fail(rc);
-                    }
-                }
-            } catch (const StageError& e) {   // this frame's failure: reported with the frame, the pipeline goes on
-                r.status = e.code;
-                why = e.msg;
-            }
-            if (pose_on) {   // the pose worker finishes the frame: its ratio-filtered matches are ordered on this stream
-                s->res = r;
-                s->res_why = why;
-                HIP_CHECK(hipEventRecord(s->ev_homography, st));
-                q_pose.push(s);
-            } else {
-                finish(s, r, why);
-            }
-        }
-        (void)hipFree(count_dev);
-        collect({"ransac_score"});
-        q_pose.close();
-    }
-
-    // ---- stage 4 (opt-in): world-point gather, PnP RANSAC ------------------------------------------------------------------------------
-    // Frame i's pose runs here while frame i + 1's homography runs on the stage before. Both calls start from an empty workspace of this
-    // thread (they reset it themselves), so nothing grows with the frame count. A frame whose pose fails reports it in its pose status.
-    void pose_worker() {
-        hipStream_t st = st_pose;
-        Slot* s = nullptr;
-        while (q_pose.pop(s)) {
-            const apds_frame_result& r = s->res;
-            apds_frame_pose fp{};
-            fp.frame = s->index;
-            fp.status = r.status;
-            if (r.status == APDS_OK) {
-                const int M = r.n_matches;
-                fp.n_correspondences = M;
-                try {
-                    HIP_CHECK(hipStreamWaitEvent(st, s->ev_homography, 0));
-                    PIPE_OK(apds_dev_pnp_correspondences(s->kps, s->K, table ? s->view_xyz : pose.db_xyz_dev, table ? (int64_t)s->n_view : n_db_total, pose.origin, s->matches, M, s->pose_img, s->pose_obj, st));
-                    if (lens_on) PIPE_OK(guarded([&] { lens_undistort_points_f32_device(s->pose_img, M, 2 * sizeof(float), lens, lens_iters, st); }));
-                    // fewer than four pairs: the one-call entry's APDS_ERR_ASSERT, without device work
-                    fp.status = apds_dev_pnp_solver_ransac(s->pose_obj, s->pose_img, M, pose.camera_intrinsic, pose.iter_count, pose.reproj_thres, pose.confidence,
-                                                          pose.method, fp.rvec, fp.tvec, nullptr, &fp.n_inliers, &fp.found, st);
-                } catch (const StageError& e) {
-                    fp.status = e.code;
-                }
-                if (fp.status != APDS_OK) {   // (as the serial front reports a failed solve: nothing but the status and the pair count)
-                    fp.found = fp.n_inliers = 0;
-                    std::memset(fp.rvec, 0, sizeof(fp.rvec));
-                    std::memset(fp.tvec, 0, sizeof(fp.tvec));
-                }
-            }
-            finish(s, r, s->res_why, &fp);
-        }
-    }
-};
+namespace {
 
 void destroy_pipeline(Pipeline* P) {
     {
@@ -582,9 +105,7 @@ void destroy_pipeline(Pipeline* P) {
     P->q_any.close();
     for (auto& t : P->threads)
         if (t.joinable()) t.join();
-    int previous = -1;
-    if (hipGetDevice(&previous) != hipSuccess) previous = -1;
-    (void)hipSetDevice(P->device);
+    DeviceGuard on(P->device);
     (void)hipDeviceSynchronize();
     for (auto& up : P->slots) {
         Slot* s = up.get();
@@ -599,8 +120,8 @@ void destroy_pipeline(Pipeline* P) {
     }
     if (P->db_expanded) hm_train_destroy(P->db_expanded);
     P->db_expanded = nullptr;
-    l2_train_destroy(P->l2_train);
-    P->l2_train = nullptr;
+    l2_train_destroy(P->train.l2);
+    P->train.l2 = nullptr;
     if (P->db_plain_pc) (void)hipFree(P->db_plain_pc);
     P->db_plain_pc = nullptr;
     if (!P->own_match_stream) P->st_match = nullptr;
@@ -608,7 +129,6 @@ void destroy_pipeline(Pipeline* P) {
         if (st) (void)hipStreamDestroy(st);
     for (hipStream_t st : P->st_extract)
         if (st) (void)hipStreamDestroy(st);
-    if (previous >= 0) (void)hipSetDevice(previous);
     delete P;
 }
 
@@ -617,13 +137,15 @@ Pipeline* pipe_handle(void* h) {
     return static_cast<Pipeline*>(h);
 }
 
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
+// The frame of a setter, configure before the first submit: the submitter's lock (the caller holds it for the rest of its body), a failed
+// pipeline's error again, and no frame submitted yet (too_late: the setter's own text for that).
+std::unique_lock<std::mutex> configure_lock(Pipeline* P, const char* too_late) {
+    std::unique_lock<std::mutex> one(P->submit_m);
+    std::lock_guard<std::mutex> g(P->m);
+    if (P->failed) fail(P->fail_code, P->fail_msg);
+    APDS_REQUIRE(P->next_submit == 0, APDS_ERR_BAD_ARG, too_late);
+    return one;
+}
 
 // table != null: the train set is a per-frame view of that keypoint table (view_capacity rows at most); the rows arguments are unused
 // float_rows: db_rows64_dev are rows of 64 floats (apds_pipeline_create_float; no shard, no table)
@@ -647,12 +169,12 @@ int create_pipeline(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint
         P->device = c.device;
         P->table = table;
         P->view_capacity = view_capacity;
-        P->db_rows = db_rows64_dev;
-        P->n_rows = n_rows;
-        P->index_base = index_base;
+        P->train.rows = db_rows64_dev;
+        P->train.n_rows = n_rows;
+        P->train.index_base = index_base;
+        P->train.kps = static_cast<const apds_keypoint*>(db_kps_dev);
+        P->train.n_kps = n_db_total;
         P->shard = shard;
-        P->db_kps = static_cast<const apds_keypoint*>(db_kps_dev);
-        P->n_db_total = n_db_total;
         P->float_rows = float_rows;
         if (float_rows) P->matcher = APDS_PIPELINE_MATCH_L2_RATIO;
         const Config& cfg = config();
@@ -663,8 +185,8 @@ int create_pipeline(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint
             const int rc = apds_shard_info(shard, nullptr, &w, &nr, &base, nullptr, nullptr);
             if (rc != APDS_OK) fail(rc, apds_last_error());
             P->world = w;
-            P->n_rows = nr;
-            P->index_base = base;
+            P->train.n_rows = nr;
+            P->train.index_base = base;
         }
         P->cap = in.max_points > 0 ? std::min(in.max_points, APDS_MAX_POINTS) : APDS_MAX_POINTS;
         P->E = std::max(1, std::min(8, in.extract_workers > 0 ? in.extract_workers : cfg.pipe_extract_workers));
@@ -695,12 +217,13 @@ int create_pipeline(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint
             HIP_CHECK(hipStreamCreateWithPriority(&P->st_gather, hipStreamNonBlocking, hp));
             HIP_CHECK(hipStreamCreateWithPriority(&P->st_counts, hipStreamNonBlocking, hp));
         }
-        if (float_rows && !table) P->l2_train = l2_train_create(static_cast<const float*>(db_rows64_dev), n_rows, 64, index_base, P->st_match);
-        if (P->world == 1 && !shard && !table && !float_rows && cfg.match_mfma) P->db_expanded = hm_train_create(P->db_rows, P->n_rows, P->st_match);
+        if (float_rows && !table) P->train.l2 = l2_train_create(static_cast<const float*>(db_rows64_dev), n_rows, 64, index_base, P->st_match);
+        if (P->world == 1 && !shard && !table && !float_rows && cfg.match_mfma) P->db_expanded = hm_train_create(P->train.rows, P->train.n_rows, P->st_match);
         const size_t cap = (size_t)P->cap;
         for (int i = 0; i < n_slots; i++) {
             auto s = std::make_unique<Slot>();
             s->owner = i % P->E;
+            s->train = P->train;
             HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->kps), cap * sizeof(apds_keypoint)));
             HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->desc), cap * (float_rows ? 256 : 64)));
             HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->keys), cap * 2 * 8));
@@ -721,16 +244,18 @@ int create_pipeline(void** pipe, const void* db_rows64_dev, int64_t n_rows, uint
             }
             if (table) {
                 int rc = apds_db_view_create(table, view_capacity, &s->view);
-                void *rows64 = nullptr, *kps = nullptr;
+                void *rows64 = nullptr, *kps = nullptr, *l2 = nullptr;
                 if (rc == APDS_OK) rc = apds_db_view_pointers(s->view, &rows64, &kps, nullptr, nullptr, nullptr, nullptr);
-                if (rc == APDS_OK && float_rows) rc = apds_db_view_l2_train(s->view, &s->view_l2_train);   // (borrowed: the view owns it)
+                if (rc == APDS_OK && float_rows) rc = apds_db_view_l2_train(s->view, &l2);   // (borrowed: the view owns it)
                 if (rc != APDS_OK) {
                     const std::string why = apds_last_error();
                     P->slots.push_back(std::move(s));   // (destroy releases what this slot already holds)
                     fail(rc, why);
                 }
-                s->view_rows64 = rows64;
-                s->view_kps = static_cast<const apds_keypoint*>(kps);
+                // the slot's train side is its view: the counts and xyz come with each frame's select (index_base 0: a match's train index is the view position)
+                s->train.rows = rows64;
+                s->train.kps = static_cast<const apds_keypoint*>(kps);
+                s->train.l2 = static_cast<L2Train*>(l2);
             }
             P->slots.push_back(std::move(s));
         }
@@ -865,13 +390,8 @@ int apds_pipeline_enable_pose(void* pipe, const apds_pipeline_pose_params* pose)
         APDS_REQUIRE(pose->method >= APDS_SOLVEPNP_ITERATIVE && pose->method <= APDS_SOLVEPNP_SQPNP, APDS_ERR_NOT_IMPLEMENTED,
                      "unknown cv::SolvePnPMethod (MAX_COUNT and beyond)");
         Pipeline* P = pipe_handle(pipe);
-        std::lock_guard<std::mutex> one(P->submit_m);
-        {
-            std::lock_guard<std::mutex> g(P->m);
-            if (P->failed) fail(P->fail_code, P->fail_msg);
-            APDS_REQUIRE(P->next_submit == 0, APDS_ERR_BAD_ARG, "the pose stage is enabled before the first submit");
-            APDS_REQUIRE(!P->pose_on, APDS_ERR_BAD_ARG, "the pose stage is already enabled");
-        }
+        const auto one = configure_lock(P, "the pose stage is enabled before the first submit");
+        APDS_REQUIRE(!P->pose_on, APDS_ERR_BAD_ARG, "the pose stage is already enabled");
         if (P->table) {   // the views gather the table's xyz column: it has to cover every row now (the table is frozen from here on)
             void* xyz = nullptr;
             const int rc = apds_db_table(P->table, nullptr, nullptr, &xyz, nullptr);
@@ -882,17 +402,15 @@ int apds_pipeline_enable_pose(void* pipe, const apds_pipeline_pose_params* pose)
         if (P->pose.iter_count <= 0) P->pose.iter_count = 100;
         if (P->pose.reproj_thres <= 0) P->pose.reproj_thres = 8.0f;
         if (!(P->pose.confidence > 0 && P->pose.confidence < 1)) P->pose.confidence = 0.99;
-        int previous = -1;
-        if (hipGetDevice(&previous) != hipSuccess) previous = -1;
-        HIP_CHECK(hipSetDevice(P->device));
+        DeviceGuard on(P->device);
         if (!P->st_pose) HIP_CHECK(hipStreamCreateWithPriority(&P->st_pose, hipStreamNonBlocking, config().pipe_prio));
         const size_t cap = (size_t)P->cap;
         for (auto& s : P->slots) {
             if (!s->pose_img) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->pose_img), cap * 2 * sizeof(float)));
             if (!s->pose_obj) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->pose_obj), cap * 3 * sizeof(float)));
             if (!s->ev_homography) HIP_CHECK(hipEventCreateWithFlags(&s->ev_homography, hipEventDisableTiming));
+            if (!P->table) s->train.xyz = pose->db_xyz_dev;   // (a table pipeline: each frame's select gives its view's)
         }
-        if (previous >= 0 && previous != P->device) (void)hipSetDevice(previous);
         P->pose_on = true;
         Pipeline* raw = P;
         P->threads.emplace_back([raw] { raw->worker("pose", [&] { raw->pose_worker(); }); });
@@ -909,28 +427,20 @@ int apds_pipeline_set_matcher(void* pipe, int matcher) {
                      P->float_rows ? "a float pipeline's matcher is APDS_PIPELINE_MATCH_L2_RATIO for life" : "APDS_PIPELINE_MATCH_L2_RATIO needs a float pipeline (apds_pipeline_create_float, or apds_pipeline_create_table on a float table)");
         APDS_REQUIRE(matcher == APDS_PIPELINE_MATCH_RATIO || !(P->shard || P->world > 1), APDS_ERR_NOT_IMPLEMENTED,
                      "the cross-check over a row-sharded train set (the per-query minimum across shards) is not built");
-        std::lock_guard<std::mutex> one(P->submit_m);
-        {
-            std::lock_guard<std::mutex> g(P->m);
-            if (P->failed) fail(P->fail_code, P->fail_msg);
-            APDS_REQUIRE(P->next_submit == 0, APDS_ERR_BAD_ARG, "the matcher is chosen before the first submit");
-        }
+        const auto one = configure_lock(P, "the matcher is chosen before the first submit");
         if (matcher == APDS_PIPELINE_MATCH_CROSSCHECK) {
             // every slot's train_best: one key per train row (a table pipeline: per row a view can hold); the swapped scan's searching side
             // counts its rows in an int
-            APDS_REQUIRE(P->table || P->n_rows <= (int64_t)INT_MAX, APDS_ERR_ASSERT, "the train rows are the searching side of the swapped scan: at most INT_MAX of them");
-            const size_t rows = P->table ? (size_t)(P->view_capacity > 0 ? std::min(P->view_capacity, APDS_MAX_POINTS) : APDS_MAX_POINTS) : (size_t)P->n_rows;
-            int previous = -1;
-            if (hipGetDevice(&previous) != hipSuccess) previous = -1;
-            HIP_CHECK(hipSetDevice(P->device));
+            APDS_REQUIRE(P->table || P->train.n_rows <= (int64_t)INT_MAX, APDS_ERR_ASSERT, "the train rows are the searching side of the swapped scan: at most INT_MAX of them");
+            const size_t rows = P->table ? (size_t)(P->view_capacity > 0 ? std::min(P->view_capacity, APDS_MAX_POINTS) : APDS_MAX_POINTS) : (size_t)P->train.n_rows;
+            DeviceGuard on(P->device);
             for (auto& s : P->slots)
                 if (!s->train_best) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s->train_best), rows * sizeof(uint64_t)));
             if (P->db_expanded && !P->db_plain_pc) {
-                HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&P->db_plain_pc), (size_t)P->n_rows * sizeof(float)));
+                HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&P->db_plain_pc), (size_t)P->train.n_rows * sizeof(float)));
                 hm_train_plain_popcounts_device(P->db_expanded, P->db_plain_pc, P->st_match);
                 HIP_CHECK(hipStreamSynchronize(P->st_match));
             }
-            if (previous >= 0 && previous != P->device) (void)hipSetDevice(previous);
         }
         P->matcher = matcher;
     });
@@ -941,12 +451,7 @@ int apds_pipeline_set_lens(void* pipe, const double* K, const double* dist, int 
         lens::Lens L;
         const bool distorts = lens_from_args(K, dist, n_dist, &L);   // the argument checks first, before the handle is touched
         Pipeline* P = pipe_handle(pipe);
-        std::lock_guard<std::mutex> one(P->submit_m);
-        {
-            std::lock_guard<std::mutex> g(P->m);
-            if (P->failed) fail(P->fail_code, P->fail_msg);
-            APDS_REQUIRE(P->next_submit == 0, APDS_ERR_BAD_ARG, "the lens is set before the first submit");
-        }
+        const auto one = configure_lock(P, "the lens is set before the first submit");
         P->lens = L;
         P->lens_iters = iters > 0 ? iters : lens::DEFAULT_ITERS;
         P->lens_on = distorts;   // no distortion: the stages launch what they launched without a lens

@@ -32,19 +32,6 @@ namespace {
         if (r_ != ncclSuccess && r_ != ncclInProgress) throw ShardError(APDS_ERR_INTERNAL, std::string(#x " failed: ") + ncclGetErrorString(r_)); \
     } while (0)
 
-// hipSetDevice(handle's device) for the length of a destroy path, then the caller's device again: a thread bound to GPU A may destroy a
-// handle living on GPU B (a thread-per-GPU host; a finaliser running on an arbitrary thread) and must keep launching on A afterwards.
-struct DeviceGuard {
-    int previous = -1;
-    explicit DeviceGuard(int device) {
-        if (hipGetDevice(&previous) != hipSuccess) previous = -1;
-        (void)hipSetDevice(device);
-    }
-    ~DeviceGuard() {
-        if (previous >= 0) (void)hipSetDevice(previous);
-    }
-};
-
 struct HipDevice final : Device {
     static hipStream_t st(void* s) { return pick_stream(s); }
     void* alloc(size_t bytes) override {

@@ -670,21 +670,19 @@ class StreamedFramePipeline:
         else:
             check(lib().apds_pipeline_create(C.byref(h), m.rows.data_ptr(), int(m.rows.shape[0]), m.index_base, m.handle, self.db_kp.data_ptr(), self.n_db, C.byref(p)))
         self._pipe, self._key = h, key
-        if self.matcher_mode not in (_lib.PIPELINE_MATCH_RATIO, _lib.PIPELINE_MATCH_L2_RATIO):     # (a pipeline that never asks runs the ratio matcher)
-            rc = lib().apds_pipeline_set_matcher(h, self.matcher_mode)
+
+        def configured(rc):     # a setter that failed: its error text first, then no handle is left behind
             if rc != 0:
                 why = lib().apds_last_error().decode("utf-8", "replace")
                 self._pipe = None
                 lib().apds_pipeline_destroy(h)
                 raise _lib.ApdsError(rc, why)
+
+        if self.matcher_mode not in (_lib.PIPELINE_MATCH_RATIO, _lib.PIPELINE_MATCH_L2_RATIO):     # (a pipeline that never asks runs the ratio matcher)
+            configured(lib().apds_pipeline_set_matcher(h, self.matcher_mode))
         if self.lens is not None:
             (K, d, pK, pd, nd), iters = self.lens
-            rc = lib().apds_pipeline_set_lens(h, pK, pd, nd, iters)
-            if rc != 0:
-                why = lib().apds_last_error().decode("utf-8", "replace")
-                self._pipe = None
-                lib().apds_pipeline_destroy(h)
-                raise _lib.ApdsError(rc, why)
+            configured(lib().apds_pipeline_set_lens(h, pK, pd, nd, iters))
         if self.pose is not None:
             pp = self.pose.params()
             if self.per_frame_table is not None:

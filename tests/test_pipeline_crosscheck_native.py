@@ -1,4 +1,4 @@
-"""The pipeline's cross-check mode (apds_pipeline_set_matcher, csrc/pipeline.cpp) driven by a host that is not Python:
+"""The pipeline's cross-check mode (apds_pipeline_set_matcher, csrc/pipeline.cpp; the swapped scan in csrc/pipeline_match.cpp) driven by a host that is not Python:
 tests/cpp/pipeline_crosscheck_test.cpp, built by g++ against libapds_hip.so (no torch, no HIP headers). It builds a train set on the
 device, sets the matcher, streams 10 frames and compares every result with the one-call functions (apds_dev_crosscheck_match, itself
 compared with apds_get_bruteforce_matches, then the point gather and apds_dev_find_homography)."""

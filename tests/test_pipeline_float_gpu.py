@@ -1,4 +1,4 @@
-"""GPU: the float pipeline (apds_pipeline_create_float, APDS_PIPELINE_MATCH_L2_RATIO; csrc/pipeline.cpp): M-SURF descriptors, the resident L2
+"""GPU: the float pipeline (apds_pipeline_create_float, APDS_PIPELINE_MATCH_L2_RATIO; csrc/pipeline.cpp, csrc/pipeline_match.cpp): M-SURF descriptors, the resident L2
 train set's top-2, the L2 ratio filter, then matched points, homography, pose and lens as in every pipeline.
 
 Frames are 256 x 256 (synth.py; about 190 keypoints). Every streamed frame is compared with the serial composition of the public device

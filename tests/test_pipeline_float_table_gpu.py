@@ -1,4 +1,4 @@
-"""GPU: apds_pipeline_create_table on a FLOAT keypoint table (csrc/pipeline.cpp): workers extract M-SURF rows, the matcher is the L2 ratio
+"""GPU: apds_pipeline_create_table on a FLOAT keypoint table (csrc/pipeline.cpp, csrc/pipeline_match.cpp): workers extract M-SURF rows, the matcher is the L2 ratio
 matcher for life, and each frame's train set is its slot's view of the table, the screen's train side written by the select's gather
 (apds_db_view_l2_train).
 

@@ -1,4 +1,4 @@
-"""GPU: the streamed pipeline with a lens (apds_pipeline_set_lens, csrc/pipeline.cpp).
+"""GPU: the streamed pipeline with a lens (apds_pipeline_set_lens, csrc/pipeline.cpp; the stages in csrc/pipeline_stages.cpp).
 
 The frame and DB shapes of tests/test_pipeline_pose_gpu.py (768 x 768 frames, a 60000-row DB holding every frame rolled by (19, 23)), pose
 enabled, coefficient set A with a camera of f = 2000 (4.8 px of distortion at the frame's corners: enough to move every matched point,

@@ -1,4 +1,4 @@
-"""The streamed frame pipeline behind the C ABI (apds_pipeline_*, csrc/pipeline.cpp) driven by a host that is not Python:
+"""The streamed frame pipeline behind the C ABI (apds_pipeline_*, csrc/pipeline.cpp and its stage files csrc/pipeline_match.cpp, csrc/pipeline_stages.cpp) driven by a host that is not Python:
 tests/cpp/pipeline_test.cpp, built by g++ against libapds_hip.so (no torch, no HIP headers). CPU: it compiles and links, and the three
 structs of the pipeline ABI have the layout the python front (ctypes) assumes. GPU: it runs - 24 + 9 frames streamed (device and host
 frames alternating, blank frames among them), every result equal to what the one-call entry points give for that frame (keypoint,

@@ -1,4 +1,4 @@
-"""GPU: the pose stage of the streamed pipeline (apds_pipeline_enable_pose / apds_pipeline_poll_pose, csrc/pipeline.cpp) and the two device entry
+"""GPU: the pose stage of the streamed pipeline (apds_pipeline_enable_pose / apds_pipeline_poll_pose, csrc/pipeline.cpp; pose_worker in csrc/pipeline_stages.cpp) and the two device entry
 points it is made of - apds_dev_pnp_correspondences (matches -> 2D-3D pairs, re-centred on an origin) and apds_dev_pnp_solver_ransac (the
 RANSAC loop of apds_pnp_solver_ransac on device floats).
 

@@ -1,5 +1,5 @@
 """GPU: the pipeline whose train set is selected per frame from a keypoint table (apds_pipeline_create_table /
-apds_pipeline_submit_select, csrc/pipeline.cpp; keypointdb.rs:50-90 is the read it repeats).
+apds_pipeline_submit_select, csrc/pipeline.cpp; the select per frame in csrc/pipeline_match.cpp; keypointdb.rs:50-90 is the read it repeats).
 
 Frames and tiles are 256 x 256 (synth.py). The table holds two frames rolled by (19, 23) at two levels of detail and two tile columns,
 one single-row image at a third level, and random filler. Every frame's result is compared bit for bit with a serial composition of

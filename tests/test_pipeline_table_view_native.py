@@ -1,4 +1,4 @@
-"""The per-frame-view pipeline (apds_pipeline_create_table / apds_pipeline_submit_select, csrc/pipeline.cpp) driven by a host that is not
+"""The per-frame-view pipeline (apds_pipeline_create_table / apds_pipeline_submit_select, csrc/pipeline.cpp; the select per frame in csrc/pipeline_match.cpp) driven by a host that is not
 Python: tests/cpp/pipeline_table_view_test.cpp, built by g++ against libapds_hip.so (no torch, no HIP headers). It fills a table on the
 device, streams 12 frames with six different selections (two of them empty) and compares every result with the serial composition of the
 one-call entry points on apds_db_select's view."""

@@ -1,4 +1,4 @@
-"""GPU: the library's streamed pipeline (apds_pipeline_*, csrc/pipeline.cpp; bench.py's default path: extract | match | homography on
+"""GPU: the library's streamed pipeline (apds_pipeline_*, csrc/pipeline.cpp with csrc/pipeline_match.cpp and csrc/pipeline_stages.cpp; bench.py's default path: extract | match | homography on
 their own host threads and streams inside libapds_hip.so, two extraction workers) through its python front must give, frame by frame,
 what the one-frame-at-a-time FramePipeline gives; and its starvation watch must cap the occupancy of ITS scans when extraction is made
 artificially late. (tests/cpp/pipeline_test.cpp drives the same four calls from a g++-built host.)"""
@@ -52,6 +52,35 @@ def test_streamed_results_equal_the_serial_pipeline(gpu_pkg):
     want = [serial.step(frames[i % len(frames)], filter_strength=0.3) for i in range(7)]
     streamed = pl.StreamedFramePipeline(db, db_xy)
     got, _ = streamed.run(frames, 7, filter_strength=0.3)
+    assert len(got) == 7
+    for a, b in zip(want, got):
+        assert a["n_keypoints"] == b["n_keypoints"] > 500 and a["n_matches"] == b["n_matches"] > 100 and a["n_inliers"] == b["n_inliers"] > 50
+        assert a["H"] is not None and np.array_equal(a["H"], b["H"])
+        assert abs(a["H"][0, 2] - 23) < 0.5 and abs(a["H"][1, 2] - 19) < 0.5      # the planted translation
+
+
+@pytest.mark.parametrize("switches, split_scan", [({"APDS_MATCH_SPLIT": "2"}, 1), ({"APDS_MATCH_MFMA": "0", "APDS_MATCH_SPLIT": "0"}, 0)],
+                         ids=["matrix_cores_on_three_streams", "vector_alu_on_one_stream"])
+def test_forced_scan_layouts_equal_the_serial_pipeline(gpu_pkg, request, switches, split_scan):
+    """The two scan layouts of a fixed train set that no default reaches: the three-stream split scan over the resident expanded copy
+    (APDS_MATCH_SPLIT=2 with the matrix-core matcher: topk_split_use_train), and the vector-ALU matcher's one-call scan on the match stream
+    alone (APDS_MATCH_MFMA=0 with APDS_MATCH_SPLIT=0). The switches are read once per process, so each case runs itself again in a child
+    process that has them set."""
+    if any(os.environ.get(k) != v for k, v in switches.items()):
+        r = subprocess.run([sys.executable, "-m", "pytest", __file__ + "::" + request.node.name, "-q", "-m", "gpu", "-x", "-p", "no:cacheprovider"],
+                           env=dict(os.environ, **switches), cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0 and " passed" in r.stdout, (r.stdout[-3000:], r.stderr[-1000:])
+        return
+    pl, frames, db, db_xy = _setup(gpu_pkg)
+    serial = pl.FramePipeline(db, db_xy)
+    want = [serial.step(frames[i % len(frames)], filter_strength=0.3) for i in range(7)]
+    streamed = pl.StreamedFramePipeline(db, db_xy)
+    try:
+        got, _ = streamed.run(frames, 7, filter_strength=0.3)
+        assert streamed.stats().split_scan == split_scan
+    finally:
+        streamed.close()
     assert len(got) == 7
     for a, b in zip(want, got):
         assert a["n_keypoints"] == b["n_keypoints"] > 500 and a["n_matches"] == b["n_matches"] > 100 and a["n_inliers"] == b["n_inliers"] > 50
